@@ -19,6 +19,12 @@ scalar per step; `value` = L=256-latent ELBO evaluations per second of the whole
 restates it in the N = 1 line's unit).  `--scaling weak` keeps 32 latents per GPU (a 32*N-latent model) instead.
 Inputs are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the steps and prints the headline line.  `--full` adds everything else the
+benchmark measures: per-kernel HIP-event timings and rooflines of the timed steps, the engine clock, the training legs
+(forward + backward) and the configs[1] record, the CPU-port baseline and its parity check.  `--dump-outputs DIR`
+writes what the last timed step handed its caller (q(F) mean and scale, per-latent KL and expected log-likelihood,
+the ELBO) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -90,10 +96,16 @@ def parse():
                          "csrc/gemmp.hip): the selectable path of DESIGN.md section 5, not the default")
     ap.add_argument("--cpu-sample", type=int, default=8192, help="spots in the CPU-baseline sample (SURVEY §8d: 8192)")
     ap.add_argument("--with-backward", action="store_true",
-                    help="(kept for old command lines: the training legs now run by default on one GPU)")
+                    help="(kept for old command lines: the training legs run with --full on one GPU)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the legs outside the timed region: forward + backward of this workload and the "
-                         "BASELINE configs[1] record (`small_m`); they never run with more than one rank")
+                    help="with --full: skip the legs outside the timed region: forward + backward of this workload and "
+                         "the BASELINE configs[1] record (`small_m`); they never run with more than one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: per-kernel timings and rooflines of the timed steps, the engine "
+                         "clock, the training legs, the configs[1] record and the CPU baseline (unless switched off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (rank 0; at most 64 MB, "
+                         "a fixed seeded sample of the spots beyond that)")
     return ap.parse_args()
 
 
@@ -370,6 +382,33 @@ def plan_latents(cfg_id: int, world: int, rank: int, L, Ltotal: int, scaling):
     return model, "weak", Lper * world, range(rank * Lper, (rank + 1) * Lper), [Lper] * world
 
 
+DUMP_BYTES = 60_000_000    # --dump-outputs: array bytes of all files together (under 64 MB with the .npy headers)
+DUMP_SEED = 20240          # which spots a sample keeps when the (L, N) arrays exceed DUMP_BYTES
+
+
+def dump_outputs(d: str, out: dict, elbo: torch.Tensor) -> dict:
+    """--dump-outputs: the floating-point arrays of one svgp_forward result (mean, scale: (L, N); kl, loglik: (L,)) and
+    the ELBO the step returned (all-reduced when several ranks run), each as d/<name>.npy in the dtype computed.  When
+    they exceed DUMP_BYTES the (L, N) arrays keep the same fixed, seeded, sorted set of spots (columns).  Returns
+    {name: shape} of what was written."""
+    import numpy as np
+    arrs = {k: v for k, v in out.items() if isinstance(v, torch.Tensor) and v.is_floating_point()}
+    arrs["elbo"] = elbo
+    total = sum(v.numel() * v.element_size() for v in arrs.values())
+    if total > DUMP_BYTES:
+        wide = [k for k, v in arrs.items() if v.dim() == 2]
+        N = arrs[wide[0]].shape[1]
+        per_spot = sum(arrs[k].shape[0] * arrs[k].element_size() for k in wide)
+        keep = max(1, (DUMP_BYTES - (total - per_spot * N)) // per_spot)
+        cols = torch.randperm(N, generator=torch.Generator().manual_seed(DUMP_SEED))[:keep].sort().values
+        for k in wide:
+            arrs[k] = arrs[k][:, cols.to(arrs[k].device)]
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), v.detach().cpu().numpy())
+    return {k: list(v.shape) for k, v in arrs.items()}
+
+
 def self_launch(a) -> int:
     """`python bench.py --gpus N` typed without a launcher: start the N ranks as a child torch.distributed.run
     job (this process has not touched the GPU: device_count() does not initialise it) and return its exit
@@ -430,7 +469,7 @@ def main():
 
     path = {}
 
-    def step():
+    def step(keep=False):
         out = ops.svgp_forward(spec, g["X"], g["Z"], g["mu"], g["Lu_raw"], c["jitter"], c["whitened"],
                                y=g["y"], noise_sd=c["noise_sd"], chunk=a.chunk, want_Lu=False,
                                materialize_kzx=False if a.generate_kzx else None, panel_products=a.panel_products, **extra)
@@ -438,6 +477,8 @@ def main():
         e = out["elbo"]
         if grouped:
             e = _allreduce_scalar(e)      # RCCL on the device scalar (nccl); through the host for gloo rehearsals
+        if keep:                          # the last timed step: what its caller received, for --dump-outputs
+            path["out"] = out
         return e
 
     def fence():
@@ -448,108 +489,115 @@ def main():
     for _ in range(a.warmup):
         step()
     fence()
-    ops.profile_enable(True)
-    clock = ClockSampler(local) if rank == 0 else None
+    clock = None
+    if a.full:
+        ops.profile_enable(True)
+        clock = ClockSampler(local) if rank == 0 else None
     if clock:
         clock.start()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        elbo = step()
+    for i in range(a.steps):
+        elbo = step(keep=a.dump_outputs is not None and i == a.steps - 1)
     fence()
     dt_s = time.perf_counter() - t0
     clocks = clock.stop() if clock else None
-    prof = ops.profile_read()
-    ops.profile_enable(False)
+    if a.full:
+        prof = ops.profile_read()
+        ops.profile_enable(False)
     tmax = torch.tensor([dt_s], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     if grouped:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     t = float(tmax)
+    dumped = None
+    if a.dump_outputs is not None and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, path.pop("out"), elbo)
     elbo = float(elbo)
 
     train_ms = small_m = None
-    if world == 1 and not grouped and not a.no_extra_legs:
+    if a.full and world == 1 and not grouped and not a.no_extra_legs:
         train_ms = train_leg(ops, spec, g, c, extra, a.chunk)
         if cfg_id == 3 and (a.N, a.M, a.L) == (None, None, None):
             small_m = small_m_record(ops, dev)
 
     if rank == 0:
-        Mp = (M + 127) // 128 * 128
-        ms1, n1 = prof["stage1"]
-        ms2, n2 = prof["stage2"]
-        # dominant kernel: Wt = Linv * Kzx, one launch per N-chunk -- fp32: gemmw_kernel (128 x 256 tiles, csrc/gemmw.hip),
-        # fp64: gemm128_kernel<T,NN,store+colstats>.  algorithmic flops = L * M^2 * N per evaluation (SURVEY §8d TRSM count).
-        flops1 = Lper * float(M) * M * N * a.steps
-        # the kernel that ran, from the predicate the library itself dispatches on (gpz_svgp_forward_path)
-        bits = path.get("bits", 0)
-        panel = bool(bits & 4)      # fp32, M <= 512: ONE launch runs both products panel by panel (csrc/gemmp.hip): 2 x the flops
-        ach1 = (2.0 if panel else 1.0) * flops1 / (ms1 * 1e-3) / 1e12 if ms1 > 0 else 0.0
-        mp = measured_peaks()
-        traffic, traffic_src = pmc_traffic(cfg_id, N, M, Lper, a.chunk)
-        kname = ("panel_kernel<Mp/64 row blocks> (Wt = Linv*Kzx and colsum((LuE^T Wt)^2) on one 64-column panel in LDS, csrc/gemmp.hip)" if panel
-                 else "gemmw_gen_kernel<512,128,generated Kzx,lower,store+colstats> (Wt = Linv*k(Z,X), csrc/gemmw.hip)" if bits & 2
-                 else "gemmw_kernel<128,256,mem,lower,store+colstats> (Wt = Linv*Kzx, csrc/gemmw.hip)" if bits & 1
-                 else "gemm128_kernel<%s,NN,store+colstats> (Wt = Linv*Kzx, csrc/gemm.hip)" % ("float" if dname == "f32" else "double"))
-        roof = {"bound": "mfma",
-                "kernel": kname,
-                "achieved": ach1, "peak": PEAK[dname], "unit": "TFLOP/s", "frac": ach1 / PEAK[dname],
-                "traffic": traffic, "traffic_source": traffic_src, "launches": n1,
-                "avg_launch_ms": ms1 / max(n1, 1)}
-        if clocks:     # the same fraction against the peak at the clock this box actually ran the timed region at
-            roof["peak_at_sampled_clock"] = PEAK[dname] * clocks["sclk_MHz_mean"] / ClockSampler.NOMINAL_MHZ
-            roof["frac_at_sampled_clock"] = ach1 / roof["peak_at_sampled_clock"]
-        mpk = mp.get("mfma_%s_TFLOPs" % dname)
-        if mpk:
-            roof["measured_peak"], roof["frac_of_measured_peak"] = mpk, ach1 / mpk
-        kms, kn = prof["kfill"]
-        esz = 4 if dname == "f32" else 8
-        kbytes = (Lper * float(Mp) * N * esz) * a.steps
-        kgbs = kbytes / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
-        tr_tf = (trailing_flops(Mp // 128) * Lper * a.steps / (prof["potrf_trailing"][0] * 1e-3) / 1e12
-                 if prof["potrf_trailing"][0] > 0 else 0.0)
-        sub = {
-            "kuf_fill": ({"bound": "hbm", "achieved_GBps": kgbs, "peak_GBps": HBM_PEAK, "frac": kgbs / HBM_PEAK,
-                          "ms_per_eval": kms / a.steps} if kn > 0 else
-                         {"bound": "hbm", "achieved_GBps": None, "peak_GBps": HBM_PEAK, "frac": None, "ms_per_eval": 0.0,
-                          "note": "no fill launch: panel_kernel computes its covariance panel itself and Kzx is never written"}),
-            # (panel kernel: the second product runs inside the launch counted as stage 1 -- its rate is that launch's, over both)
-            "stage2_LuT_Wt": ({"bound": "mfma", "achieved_TFLOPs": ach1, "peak_TFLOPs": PEAK[dname], "ms_per_eval": 0.0,
-                               "note": "inside panel_kernel with the first product: achieved_TFLOPs is the launch's rate over both"}
-                              if panel else
-                              {"bound": "mfma", "achieved_TFLOPs": flops1 / (ms2 * 1e-3) / 1e12 if ms2 > 0 else 0.0,
-                               "peak_TFLOPs": PEAK[dname], "ms_per_eval": ms2 / a.steps}),
-            "stage1_ms_per_eval": ms1 / a.steps,
-            "potrf_ms_per_eval": prof["potrf_all"][0] / a.steps,
-            "potrf_trailing": {"bound": "mfma", "dtype": "f64", "achieved_TFLOPs": tr_tf, "peak_TFLOPs": PEAK["f64"],
-                               "frac": tr_tf / PEAK["f64"],
-                               "ms_per_eval": prof["potrf_trailing"][0] / a.steps,
-                               "note": "K=256 SYRK launches only (90 % of the M^3/3 factorisation flops at M=2048)"},
-            "trtri_ms_per_eval": prof["trtri"][0] / a.steps,
-            "finalize_ms_per_eval": prof["finalize"][0] / a.steps,
-        }
-        potrf_flops = Lper * float(Mp) ** 3 / 3.0
-        coop = bool(_lib.load().gpz_factor_path(M, 1))
-        if coop:
-            # one launch does the Cholesky AND the triangular inverse (csrc/coop.hip): the two profile slots bracket the
-            # same interval, and there is no separate trailing-update launch to time
-            fms = prof["potrf_all"][0] / a.steps
-            ftf = 2.0 * potrf_flops / (fms * 1e-3) / 1e12 if fms > 0 else 0.0
-            sub["factor_path"] = "one launch: coop_factor_kernel (Cholesky + triangular inverse, tile dataflow)"
-            sub["factor"] = {"bound": "mfma", "dtype": "f64", "ms_per_eval": fms,
-                             "algorithmic_flops": 2.0 * potrf_flops, "achieved_TFLOPs": ftf, "peak_TFLOPs": PEAK["f64"],
-                             "frac": ftf / PEAK["f64"],
-                             "note": "L*M^3/3 (potrf) + L*M^3/3 (trtri) over the launch; potrf_ms_per_eval and "
-                                     "trtri_ms_per_eval both report this interval"}
-            del sub["potrf_trailing"]
-        else:
-            sub["factor_path"] = "launch per step (GPZ_FACTOR_PATH=launches or an order beyond the task list)"
-            if prof["potrf_all"][0] > 0:
-                sub["potrf_whole_TFLOPs"] = potrf_flops * a.steps / (prof["potrf_all"][0] * 1e-3) / 1e12
-        if mp:   # fractions of the rates measured on the box (tools/peaks.sh), next to the spec / datasheet ones
-            sub["measured_peaks"] = {k: v for k, v in mp.items() if k != "how"}
-            if mp.get("hbm_write_GBps") and kn > 0:
-                sub["kuf_fill"]["frac_of_measured_write_rate"] = kgbs / mp["hbm_write_GBps"]
-            if mp.get("mfma_f64_TFLOPs") and "potrf_trailing" in sub:
-                sub["potrf_trailing"]["frac_of_measured_peak"] = tr_tf / mp["mfma_f64_TFLOPs"]
+        if a.full:
+            Mp = (M + 127) // 128 * 128
+            ms1, n1 = prof["stage1"]
+            ms2, n2 = prof["stage2"]
+            # dominant kernel: Wt = Linv * Kzx, one launch per N-chunk -- fp32: gemmw_kernel (128 x 256 tiles, csrc/gemmw.hip),
+            # fp64: gemm128_kernel<T,NN,store+colstats>.  algorithmic flops = L * M^2 * N per evaluation (SURVEY §8d TRSM count).
+            flops1 = Lper * float(M) * M * N * a.steps
+            # the kernel that ran, from the predicate the library itself dispatches on (gpz_svgp_forward_path)
+            bits = path.get("bits", 0)
+            panel = bool(bits & 4)      # fp32, M <= 512: ONE launch runs both products panel by panel (csrc/gemmp.hip): 2 x the flops
+            ach1 = (2.0 if panel else 1.0) * flops1 / (ms1 * 1e-3) / 1e12 if ms1 > 0 else 0.0
+            mp = measured_peaks()
+            traffic, traffic_src = pmc_traffic(cfg_id, N, M, Lper, a.chunk)
+            kname = ("panel_kernel<Mp/64 row blocks> (Wt = Linv*Kzx and colsum((LuE^T Wt)^2) on one 64-column panel in LDS, csrc/gemmp.hip)" if panel
+                     else "gemmw_gen_kernel<512,128,generated Kzx,lower,store+colstats> (Wt = Linv*k(Z,X), csrc/gemmw.hip)" if bits & 2
+                     else "gemmw_kernel<128,256,mem,lower,store+colstats> (Wt = Linv*Kzx, csrc/gemmw.hip)" if bits & 1
+                     else "gemm128_kernel<%s,NN,store+colstats> (Wt = Linv*Kzx, csrc/gemm.hip)" % ("float" if dname == "f32" else "double"))
+            roof = {"bound": "mfma",
+                    "kernel": kname,
+                    "achieved": ach1, "peak": PEAK[dname], "unit": "TFLOP/s", "frac": ach1 / PEAK[dname],
+                    "traffic": traffic, "traffic_source": traffic_src, "launches": n1,
+                    "avg_launch_ms": ms1 / max(n1, 1)}
+            if clocks:     # the same fraction against the peak at the clock this box actually ran the timed region at
+                roof["peak_at_sampled_clock"] = PEAK[dname] * clocks["sclk_MHz_mean"] / ClockSampler.NOMINAL_MHZ
+                roof["frac_at_sampled_clock"] = ach1 / roof["peak_at_sampled_clock"]
+            mpk = mp.get("mfma_%s_TFLOPs" % dname)
+            if mpk:
+                roof["measured_peak"], roof["frac_of_measured_peak"] = mpk, ach1 / mpk
+            kms, kn = prof["kfill"]
+            esz = 4 if dname == "f32" else 8
+            kbytes = (Lper * float(Mp) * N * esz) * a.steps
+            kgbs = kbytes / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
+            tr_tf = (trailing_flops(Mp // 128) * Lper * a.steps / (prof["potrf_trailing"][0] * 1e-3) / 1e12
+                     if prof["potrf_trailing"][0] > 0 else 0.0)
+            sub = {
+                "kuf_fill": ({"bound": "hbm", "achieved_GBps": kgbs, "peak_GBps": HBM_PEAK, "frac": kgbs / HBM_PEAK,
+                              "ms_per_eval": kms / a.steps} if kn > 0 else
+                             {"bound": "hbm", "achieved_GBps": None, "peak_GBps": HBM_PEAK, "frac": None, "ms_per_eval": 0.0,
+                              "note": "no fill launch: panel_kernel computes its covariance panel itself and Kzx is never written"}),
+                # (panel kernel: the second product runs inside the launch counted as stage 1 -- its rate is that launch's, over both)
+                "stage2_LuT_Wt": ({"bound": "mfma", "achieved_TFLOPs": ach1, "peak_TFLOPs": PEAK[dname], "ms_per_eval": 0.0,
+                                   "note": "inside panel_kernel with the first product: achieved_TFLOPs is the launch's rate over both"}
+                                  if panel else
+                                  {"bound": "mfma", "achieved_TFLOPs": flops1 / (ms2 * 1e-3) / 1e12 if ms2 > 0 else 0.0,
+                                   "peak_TFLOPs": PEAK[dname], "ms_per_eval": ms2 / a.steps}),
+                "stage1_ms_per_eval": ms1 / a.steps,
+                "potrf_ms_per_eval": prof["potrf_all"][0] / a.steps,
+                "potrf_trailing": {"bound": "mfma", "dtype": "f64", "achieved_TFLOPs": tr_tf, "peak_TFLOPs": PEAK["f64"],
+                                   "frac": tr_tf / PEAK["f64"],
+                                   "ms_per_eval": prof["potrf_trailing"][0] / a.steps,
+                                   "note": "K=256 SYRK launches only (90 % of the M^3/3 factorisation flops at M=2048)"},
+                "trtri_ms_per_eval": prof["trtri"][0] / a.steps,
+                "finalize_ms_per_eval": prof["finalize"][0] / a.steps,
+            }
+            potrf_flops = Lper * float(Mp) ** 3 / 3.0
+            coop = bool(_lib.load().gpz_factor_path(M, 1))
+            if coop:
+                # one launch does the Cholesky AND the triangular inverse (csrc/coop.hip): the two profile slots bracket the
+                # same interval, and there is no separate trailing-update launch to time
+                fms = prof["potrf_all"][0] / a.steps
+                ftf = 2.0 * potrf_flops / (fms * 1e-3) / 1e12 if fms > 0 else 0.0
+                sub["factor_path"] = "one launch: coop_factor_kernel (Cholesky + triangular inverse, tile dataflow)"
+                sub["factor"] = {"bound": "mfma", "dtype": "f64", "ms_per_eval": fms,
+                                 "algorithmic_flops": 2.0 * potrf_flops, "achieved_TFLOPs": ftf, "peak_TFLOPs": PEAK["f64"],
+                                 "frac": ftf / PEAK["f64"],
+                                 "note": "L*M^3/3 (potrf) + L*M^3/3 (trtri) over the launch; potrf_ms_per_eval and "
+                                         "trtri_ms_per_eval both report this interval"}
+                del sub["potrf_trailing"]
+            else:
+                sub["factor_path"] = "launch per step (GPZ_FACTOR_PATH=launches or an order beyond the task list)"
+                if prof["potrf_all"][0] > 0:
+                    sub["potrf_whole_TFLOPs"] = potrf_flops * a.steps / (prof["potrf_all"][0] * 1e-3) / 1e12
+            if mp:   # fractions of the rates measured on the box (tools/peaks.sh), next to the spec / datasheet ones
+                sub["measured_peaks"] = {k: v for k, v in mp.items() if k != "how"}
+                if mp.get("hbm_write_GBps") and kn > 0:
+                    sub["kuf_fill"]["frac_of_measured_write_rate"] = kgbs / mp["hbm_write_GBps"]
+                if mp.get("mfma_f64_TFLOPs") and "potrf_trailing" in sub:
+                    sub["potrf_trailing"]["frac_of_measured_peak"] = tr_tf / mp["mfma_f64_TFLOPs"]
         # one step = one ELBO evaluation of the WHOLE model (all ranks together): strong scaling counts evaluations of the
         # Ltot-latent model, weak scaling evaluations of the per-GPU block (Lper latents) summed over ranks
         strong = world > 1 and scaling == "strong"
@@ -571,14 +619,18 @@ def main():
                        "whitened": bool(c["whitened"]), "chunk": a.chunk, "factor_dtype": "f64"},
             # the same throughput in the one-GPU line's unit (L=32-latent evaluations per second)
             "value_per_32_latents": value * unit_L / 32.0,
-            "elbo": elbo, "roofline": roof, "kernels": sub, "clocks": clocks,
+            "elbo": elbo,
         }
+        if a.full:
+            res.update(roofline=roof, kernels=sub, clocks=clocks)
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         if train_ms is not None:
             res["forward_backward_ms"] = train_ms
             res["forward_backward_roofline"] = train_roofline(train_ms, Lper, M, N, dname)
         if small_m is not None:
             res["small_m"] = small_m
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             cb = cpu_baseline(cfg_id, c, a.cpu_sample)
             # parity on the driver-run line: the HIP path on the very slice the CPU port just evaluated
             # (outside the timed region), same dtype, all latents and inducing points
@@ -597,7 +649,7 @@ def main():
                 cb["sample_elbo_reference_fp64"] = ref
                 cb["sample_rel_diff_vs_reference"] = abs(cb["sample_elbo_hip"] - ref) / abs(ref)
             res["cpu_baseline"] = cb
-        elif not a.no_cpu_baseline:
+        elif a.full and not a.no_cpu_baseline:
             res["cpu_baseline"] = None
         print(json.dumps(res), flush=True)
     if grouped:

@@ -98,3 +98,46 @@ def test_clock_sampler_reads_the_active_sclk_level(tmp_path):
     none.path, none.samples, none._stop, none._thread = None, [], threading.Event(), None
     none.start()
     assert none.stop() is None
+
+
+def test_plain_run_is_lean_by_default(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` times the steps and nothing else: the secondary figures wait for --full,
+    the outputs are written only when --dump-outputs names a directory."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_step_result_within_budget(tmp_path, monkeypatch):
+    """Every floating-point array of the forward result and the step's ELBO, in the dtype computed; over the byte budget
+    the (L, N) arrays keep one fixed, seeded set of spots, the same from run to run."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    out = {"mean": torch.randn(4, 1000, generator=g), "scale": torch.rand(4, 1000, generator=g),
+           "kl": torch.rand(4, dtype=torch.float64, generator=g), "loglik": torch.rand(4, dtype=torch.float64, generator=g),
+           "elbo": torch.tensor(-3.5, dtype=torch.float64), "info": torch.zeros(4, dtype=torch.int32), "path": 1}
+    shapes = bench.dump_outputs(str(tmp_path / "all"), out, out["elbo"])
+    assert shapes == {"mean": [4, 1000], "scale": [4, 1000], "kl": [4], "loglik": [4], "elbo": []}
+    for k in shapes:
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == out[k].numpy().dtype and np.array_equal(a, out[k].numpy())
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(k + ".npy" for k in shapes)
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 4 * 4 * 300 + 2 * 4 * 8 + 8)     # room for 300 of the 1000 spots
+    for d in ("s1", "s2"):
+        shapes = bench.dump_outputs(str(tmp_path / d), out, out["elbo"])
+        assert shapes["mean"] == [4, 300] and shapes["scale"] == [4, 300] and shapes["kl"] == [4]
+        payload = sum(np.load(tmp_path / d / (k + ".npy")).nbytes for k in shapes)
+        assert payload <= bench.DUMP_BYTES
+    m1, m2 = np.load(tmp_path / "s1" / "mean.npy"), np.load(tmp_path / "s2" / "mean.npy")
+    assert np.array_equal(m1, m2)
+    full = out["mean"].numpy()
+    idx = [next(j for j in range(1000) if np.array_equal(full[:, j], col)) for col in m1.T]
+    assert idx == sorted(set(idx))                                       # 300 distinct spots of the original, in order
+    assert np.array_equal(np.load(tmp_path / "s1" / "elbo.npy"), np.float64(-3.5))

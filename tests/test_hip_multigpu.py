@@ -195,7 +195,7 @@ def test_bench_under_the_drivers_launcher_with_rccl_at_one_rank():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--N", "20000", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -212,3 +212,38 @@ def test_bench_under_the_drivers_launcher_with_rccl_at_one_rank():
     o = ops.svgp_forward(spec, g["X"], g["Z"], g["mu"], g["Lu_raw"], g["jitter"], g["whitened"], y=g["y"],
                          noise_sd=g["noise_sd"], want_Lu=False, want_moments=False, **extra)
     assert res["elbo"] == pytest.approx(float(o["elbo"]), rel=1e-12)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline figure only; --dump-outputs writes what the last timed step
+    returned (q(F) mean and scale, per-latent KL and expected log-likelihood, the ELBO), which a direct call of the same
+    forward pass on the same seeded inputs reproduces."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--N", "20000", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["unit"] == "ELBO evals/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert res["value"] == pytest.approx(1e3 / res["ms_per_step"], rel=1e-9)
+    for k in ("roofline", "kernels", "clocks", "forward_backward_ms", "small_m", "cpu_baseline"):
+        assert k not in res
+    from gpzoo_amd import ops
+    from gpzoo_amd.configs import spec_for_config
+    from gpzoo_amd.synthetic import make_config
+    g = _to_dev(make_config(3, N=20000))
+    spec, extra = spec_for_config(g, torch.device("cuda", 0))
+    o = ops.svgp_forward(spec, g["X"], g["Z"], g["mu"], g["Lu_raw"], g["jitter"], g["whitened"], y=g["y"],
+                         noise_sd=g["noise_sd"], want_Lu=False, **extra)
+    assert sorted(os.listdir(d)) == ["elbo.npy", "kl.npy", "loglik.npy", "mean.npy", "scale.npy"]
+    for k in ("mean", "scale", "kl", "loglik", "elbo"):
+        got, want = np.load(d / (k + ".npy")), o[k].cpu().numpy()
+        assert got.dtype == want.dtype and got.shape == want.shape, k
+        np.testing.assert_allclose(got, want, rtol=1e-6, atol=0, err_msg=k)
+    assert float(np.load(d / "elbo.npy")) == pytest.approx(res["elbo"], rel=1e-15)

@@ -1,6 +1,6 @@
 set -e
 export TMPDIR=/tmp
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 out=gpurun_out/prof_extra
 mkdir -p $out
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL --output-format csv -d $out/pmc_lds -- $B > $out/pmc_lds.log 2>&1

@@ -4,7 +4,7 @@
 set -e
 tag=${1:-r01}
 export TMPDIR=/tmp
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 out=gpurun_out/prof_$tag
 mkdir -p $out
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $B > $out/trace.log 2>&1

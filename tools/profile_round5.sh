@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 out=gpurun_out/prof_$tag
 pub=profiles/$tag
 mkdir -p $out $pub
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- $B > $out/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- $B > $out/pmc_write.log 2>&1
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $out/pmc_l2 -- $B > $out/pmc_l2.log 2>&1
@@ -23,8 +23,8 @@ echo "pmc passes done"
 python3 tools/publish_profile5.py traffic $out $pub
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $B > $out/trace.log 2>&1
 echo "trace done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_train -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > $out/trace_train.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_cfg2 -- python3 bench.py --config 2 --steps 10 --warmup 2 --no-cpu-baseline > $out/trace_cfg2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_train -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $out/trace_train.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_cfg2 -- python3 bench.py --full --config 2 --steps 10 --warmup 2 --no-cpu-baseline > $out/trace_cfg2.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_minibatch -- python3 tools/minibatch_step.py > $out/trace_minibatch.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_poisson -- python3 tools/poisson_step.py 3 > $out/trace_poisson.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_poisson20 -- python3 tools/poisson_step.py 20 > $out/trace_poisson20.log 2>&1
@@ -32,7 +32,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_vnngp -- pyth
 echo "traces done"
 # PMC passes over the default bench line WITH its training legs (forward + backward at config 3 and configs[1]): how busy the
 # matrix pipes are under the backward pass's kernels
-T="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline"
+T="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $out/pmc_sq_train -- $T > $out/pmc_sq_train.log 2>&1
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $out/pmc_l2_train -- $T > $out/pmc_l2_train.log 2>&1
 python3 tools/pmc_summary.py $out/pmc_sq_train $out/pmc_l2_train --json $pub/pmc_train.json > /dev/null

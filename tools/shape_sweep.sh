@@ -3,7 +3,7 @@
 # tile schedule is unbalanced.   bash tools/shape_sweep.sh > gpurun_out/shape_sweep.txt
 for shape in "7000 3000 20" "7000 2048 32" "100000 384 16" "20000 1000 10" "40000 1000 10" "100000 1024 16" "30000 4096 8" "12288 2048 32" "13000 2048 32" "5000 512 64" "200000 256 32" "3000 3000 4" "50000 1500 12"; do
   set -- $shape
-  python3 bench.py --N $1 --M $2 --L $3 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --N $1 --M $2 --L $3 --steps 5 --warmup 2 --full --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 r=json.loads(sys.stdin.read()); k=r['kernels']
 pk = r['roofline']['kernel'].startswith('panel_kernel')
