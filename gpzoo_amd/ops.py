@@ -715,17 +715,71 @@ def knn(X, Z, K: int) -> torch.Tensor:
 def morton_order(X: torch.Tensor) -> torch.Tensor:
     """(N,) int64 permutation that sorts the rows of X (N,d), d <= 4, along a Z-order (Morton) curve, 16 bits per
     coordinate, ties in index order: the ``point_order`` of ``vnngp_backward`` -- points that share their nearest
-    inducing points become neighbours in the pass's per-point records."""
+    inducing points become neighbours in the pass's per-point records -- and the search order of ``spatial_knn``.
+    The bits of all coordinates are interleaved in one broadcast per block of rows (a handful of launches, not one per
+    bit and coordinate)."""
     Xd = X.detach().double()
     lo = Xd.min(dim=0).values
     span = (Xd.max(dim=0).values - lo).clamp_min(1e-300)
-    q = ((Xd - lo) / span * 65535.0).round().to(torch.int64)
     d = X.shape[1]
-    key = torch.zeros(X.shape[0], dtype=torch.int64, device=X.device)
-    for bit in range(16):
-        for k in range(d):
-            key |= ((q[:, k] >> bit) & 1) << (bit * d + k)
+    bit = torch.arange(16, device=X.device)
+    shift = bit.unsqueeze(0) * d + torch.arange(d, device=X.device).unsqueeze(1)        # (d,16): bit b of coordinate k
+    key = torch.empty(X.shape[0], dtype=torch.int64, device=X.device)
+    for r0 in range(0, X.shape[0], 1 << 20):
+        q = ((Xd[r0:r0 + (1 << 20)] - lo) / span * 65535.0).round().to(torch.int64)
+        key[r0:r0 + (1 << 20)] = (((q.unsqueeze(-1) >> bit) & 1) << shift).sum(dim=(1, 2))   # distinct bits: sum == or
     return torch.argsort(key, stable=True)
+
+
+@_on_device
+def spatial_knn(X, k: int = 6) -> torch.Tensor:
+    """(N,k) int64 self-kNN graph of the rows of X (N,d), d <= 4, fp32 or fp64 (gpz_spatial_knn): row i holds the k
+    points nearest to point i, itself excluded, ascending by (fp64 squared distance, index) -- the directed graph of
+    squidpy's ``spatial_neighbors(coord_type="generic", n_neighs=k)`` wherever no exact tie falls on the k-th distance.
+    Exact; the points are searched in ``morton_order(X)``."""
+    _need_cuda(X)
+    lib = _lib.load()
+    X = X.detach().contiguous()
+    if X.dim() != 2:
+        raise ValueError(f"spatial_knn: X must be (N, d), got shape {tuple(X.shape)}")
+    N, d = X.shape
+    nb = lib.gpz_spatial_knn_workspace_bytes(N, d, int(k))
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    order = morton_order(X)
+    idx = torch.empty((N, int(k)), dtype=torch.int64, device=X.device)
+    ws = _workspace(X.device, nb)
+    rc = lib.gpz_spatial_knn(_ptr(X), N, d, int(k), _dt(X), _ptr(order), _ptr(idx), _ptr(ws), ws.numel(), _stream(X.device))
+    _lib.check(rc, "gpz_spatial_knn")
+    return idx
+
+
+@_on_device
+def morans_i(values, nbr) -> torch.Tensor:
+    """(L,) fp64 Moran's I of every column of values (N,L), fp32 or fp64, over the neighbour table nbr (N,K) int64
+    with row-normalised weights (gpz_morans_i; squidpy's ``spatial_autocorr(mode="moran")``).  A constant column gives
+    NaN.  Sums in a fixed order: repeated calls agree bit for bit.  A table entry outside [0, N) or naming its own row
+    raises ValueError (checked on the device; one synchronisation)."""
+    _need_cuda(values)
+    lib = _lib.load()
+    V = values.detach().contiguous()
+    if V.dim() != 2 or nbr.dim() != 2 or nbr.shape[0] != V.shape[0]:
+        raise ValueError(f"morans_i: values (N, L) and nbr (N, K) expected, got {tuple(V.shape)} and {tuple(nbr.shape)}")
+    nbr = nbr.to(device=V.device, dtype=torch.int64).contiguous()
+    N, L = V.shape
+    K = nbr.shape[1]
+    nb = lib.gpz_morans_i_workspace_bytes(N, L, K)
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    out = torch.empty(L, dtype=torch.float64, device=V.device)
+    info = torch.empty(1, dtype=torch.int32, device=V.device)
+    ws = _workspace(V.device, nb)
+    rc = lib.gpz_morans_i(_ptr(V), N, L, _dt(V), _ptr(nbr), K, _ptr(out), _ptr(info), _ptr(ws), ws.numel(),
+                          _stream(V.device))
+    _lib.check(rc, "gpz_morans_i")
+    if int(info.item()) != 0:
+        raise ValueError("morans_i: the neighbour table has an entry outside [0, N) or naming its own row")
+    return out
 
 
 @_on_device

@@ -316,12 +316,63 @@ def train_closure_batched(model, optimizer, X, groupsX, y, device=None, steps=20
     return losses
 
 
+def dims_autocorr(factors, coords, sort=True, *, n_neighs=6):
+    """Moran's I of every column of ``factors`` (N,L) over the directed ``n_neighs``-nearest-neighbour graph of
+    ``coords`` (N,d), d <= 4 -- the reference's dims_autocorr (utilities.py:131-156), which builds that graph with
+    squidpy's ``spatial_neighbors`` (generic coordinates, 6 neighbours, self excluded) and scores it with
+    ``spatial_autocorr(mode="moran")`` (weights 1/n_neighs per row).  Both run here as HIP kernels
+    (``ops.spatial_knn``, ``ops.morans_i``) on the GPU of the tensor arguments, or on the current GPU for numpy / host
+    inputs.  Neighbours are ranked by (fp64 squared distance, index): sklearn's graph wherever no exact distance tie
+    falls on the n_neighs-th place (there its KD-tree's visit order decides).  A constant column gives NaN.
+
+    Returns numpy arrays ``(idx, I)``: idx (L,) int64, I (L,) float64.  ``sort=True``: decreasing I, NaN last, equal
+    values in column order (``factors[:, idx]`` orders the factors by spatial autocorrelation).  ``sort=False``: the
+    reference's ``df.sort_index()`` over AnnData's default names "0" ... "L-1", which is a STRING sort -- for L >= 11 the
+    order is 0, 1, 10, 11, ..., 19, 2, 20, ...; idx and I stay aligned either way.  The reference's
+    ``print('here_andata')`` is not reproduced."""
+    import numpy as np
+    from . import ops
+
+    def as_tensor(a):
+        return a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+    F, X = as_tensor(factors), as_tensor(coords)
+    if F.dim() != 2 or X.dim() != 2:
+        raise ValueError(f"dims_autocorr: factors (N, L) and coords (N, d) expected, got {tuple(F.shape)} and {tuple(X.shape)}")
+    N, L = F.shape
+    if X.shape[0] != N:
+        raise ValueError(f"dims_autocorr: {N} rows of factors but {X.shape[0]} of coords")
+    if not 1 <= X.shape[1] <= 4:
+        raise ValueError(f"dims_autocorr: coordinates of dimension {X.shape[1]} unsupported (1..4)")
+    k = int(n_neighs)
+    if not 1 <= k <= 32:
+        raise ValueError(f"dims_autocorr: n_neighs={k} unsupported (1..32)")
+    if N <= k:
+        raise ValueError(f"dims_autocorr: {N} observations, more than n_neighs={k} needed")
+    dev = next((t.device for t in (F, X) if t.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if X.dtype not in (torch.float32, torch.float64):
+        X = X.double()
+    if F.dtype not in (torch.float32, torch.float64):
+        F = F.double()
+    X, F = X.to(dev), F.to(dev)
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError("dims_autocorr: coords hold a non-finite value")
+    I = ops.morans_i(F, ops.spatial_knn(X, k)).cpu().numpy()
+    if sort:
+        order = np.argsort(-I, kind="stable")                 # NaN (-NaN) sorts last; ties keep column order
+    else:
+        order = np.array(sorted(range(L), key=str), dtype=np.int64)
+    return order.astype(np.int64), I[order]
+
+
 # Host-side data preparation of the reference's utilities module (AnnData conversion, scanpy size factors,
 # sklearn NMF initialisation, plotting, ...) is outside the accelerated path and not rebuilt here.  The
 # names resolve so that ``from gpzoo.utilities import train_hybrid, anndata_to_train_val`` -- the notebooks'
 # import lines -- keep working; calling one says where it lives.
 _NOT_REBUILT = ("build_group_distances", "init_softplus", "smooth_spatial_factors", "rescale_spatial_coords",
-                "anndata_to_train_val", "scanpy_sizefactors", "dims_autocorr", "lnormal_approx_dirichlet",
+                "anndata_to_train_val", "scanpy_sizefactors", "lnormal_approx_dirichlet",
                 "regularized_nmf", "shrink_factors", "shrink_loadings", "plot_factors")
 
 

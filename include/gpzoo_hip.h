@@ -17,6 +17,9 @@
  *  - non-PD input to a factorisation: LAPACK-style info[b] = k > 0 written to
  *    device memory (order of the first non-positive leading minor); the Python
  *    wrapper turns it into torch.linalg.LinAlgError like gp.py:213/270/360.
+ *
+ * Additions under version 212 (the version number is unchanged; nothing existing moved): gpz_spatial_knn,
+ * gpz_morans_i and their *_workspace_bytes queries -- the spatial statistics of dims_autocorr (utilities.py:131-156).
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -311,6 +314,31 @@ int gpz_wsvgp_precomputed_backward(const void* W, const void* sigma, const void*
                                    int64_t L, int64_t N, int64_t M, int32_t dtype, const void* g_mean,
                                    const void* g_scale, const void* scale, void* grad_mu, void* grad_Lu_raw,
                                    double* grad_sigma, void* ws, size_t ws_bytes, void* stream);
+
+/* Self-kNN graph of N points (X (N,d) of `dtype`, row-major): idx (N,K) int64, row i = the K points nearest to point i,
+ * self excluded, ascending by (d^2, original index), where d^2 is sklearn's: the coordinates converted to fp64, each
+ * (x_k - y_k)^2 rounded, the terms added in coordinate order.  Other points at distance 0 are ordinary neighbours.
+ * Exact -- what squidpy's spatial_neighbors(coord_type="generic", n_neighs=K) builds through
+ * NearestNeighbors.kneighbors() (dims_autocorr, utilities.py:149), except where an exact tie at the K-th distance is
+ * broken by its KD-tree's visit order there.  1 <= d <= 4, 1 <= K <= 32, K < N < 2^31.
+ * `order` (N,) int64 or NULL: the order in which the points are searched (a space-filling curve makes each group of 64
+ * queries spatially compact, so most candidate tiles are skipped on their bounding boxes).  The graph does not depend on
+ * it; an order that is not a permutation of [0, N) is detected on the device and the identity is used instead.  A
+ * non-finite coordinate ranks its pairs as +inf (behind every finite one): every slot is still a valid index. */
+size_t gpz_spatial_knn_workspace_bytes(int64_t N, int32_t d, int32_t K);
+int gpz_spatial_knn(const void* X, int64_t N, int32_t d, int32_t K, int32_t dtype, const int64_t* order, int64_t* idx,
+                    void* ws, size_t ws_bytes, void* stream);
+
+/* Moran's I of every column of values (N,L) of `dtype`, row-major, over a K-neighbour graph nbr (N,K) int64 with
+ * row-normalised weights 1/K -- squidpy's spatial_autocorr(mode="moran", transformation=True):
+ *   z = v - mean(v),  I = sum_i z_i (1/K sum_{j in nbr(i)} z_j) / sum_i z_i^2   (N / S0 = 1),
+ * I (L,) fp64; a constant column gives 0 / 0 = NaN (the mean is formed around the column's first value, so it is
+ * exact for a constant column).  Every sum is taken in a fixed order: repeated calls agree bit for bit.  Each entry of
+ * nbr is checked on the device: one outside [0, N) or equal to its row is not read, and info[0] (device int32) is set
+ * to 1.  1 <= K < N < 2^31, 1 <= L <= 2^20. */
+size_t gpz_morans_i_workspace_bytes(int64_t N, int64_t L, int32_t K);
+int gpz_morans_i(const void* values, int64_t N, int64_t L, int32_t dtype, const int64_t* nbr, int32_t K, double* I,
+                 int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
 /* Multi-GPU: latent GPs shard across ranks with no data-path collective; the only exchange is
  * the sum of each rank's partial ELBO -- one ncclAllReduce(sum, fp64) over RCCL/xGMI.  The reference has no
