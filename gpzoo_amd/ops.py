@@ -782,6 +782,78 @@ def morans_i(values, nbr) -> torch.Tensor:
     return out
 
 
+def _nmf_args(X, W, H, who: str):
+    _need_cuda(X, W, H)
+    if X.dim() != 2 or W.dim() != 2 or H.dim() != 2 or W.shape[0] != X.shape[0] or H.shape[1] != X.shape[1] or W.shape[1] != H.shape[0]:
+        raise ValueError(f"{who}: X (N, D), W (N, L) and H (L, D) expected, got {tuple(X.shape)}, {tuple(W.shape)} and {tuple(H.shape)}")
+    if not (X.dtype == W.dtype == H.dtype):
+        raise TypeError(f"{who}: X, W and H must share one dtype, got {X.dtype}, {W.dtype} and {H.dtype}")
+    lib = _lib.load()
+    (N, D), L = X.shape, W.shape[1]
+    nb = lib.gpz_nmf_kl_workspace_bytes(N, D, L, _dt(X))
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return lib, N, D, L, nb
+
+
+def _nmf_divergence(lib, X, W, H, N, D, L, nb, out):
+    ws = _workspace(X.device, nb)
+    rc = lib.gpz_nmf_kl_divergence(_ptr(X), _ptr(W), _ptr(H), N, D, L, _dt(X), _ptr(out), _ptr(ws), ws.numel(),
+                                   _stream(X.device))
+    _lib.check(rc, "gpz_nmf_kl_divergence")
+    return float(out.item())
+
+
+@_on_device
+def nmf_kl_divergence(X, W, H) -> float:
+    """sklearn's ``_beta_divergence(X, W, H, 1, square_root=True)`` for dense X (N,D) >= 0, W (N,L), H (L,D) on the GPU,
+    fp32 or fp64 (gpz_nmf_kl_divergence): W H is formed tile by tile and never stored, the sums run in fp64 in a fixed
+    order.  One synchronisation (the scalar comes back to the host)."""
+    X, W, H = X.detach().contiguous(), W.detach().contiguous(), H.detach().contiguous()
+    lib, N, D, L, nb = _nmf_args(X, W, H, "nmf_kl_divergence")
+    out = torch.empty(1, dtype=torch.float64, device=X.device)
+    return _nmf_divergence(lib, X, W, H, N, D, L, nb, out)
+
+
+@_on_device
+def nmf_kl_mu(X, W0, H0, max_iter: int = 200, tol: float = 1e-4):
+    """KL-divergence NMF by multiplicative updates from (W0, H0): sklearn's ``_fit_multiplicative_update`` with
+    ``beta_loss='kullback-leibler'`` and no regularisation, on the GPU (gpz_nmf_kl_update: the N x D product and
+    quotient are never stored).  X (N,D) >= 0 and finite, W0 (N,L), H0 (L,D), one dtype (fp32 or fp64), L <= 64.
+    Returns ``(W, H, n_iter)``; W0 and H0 are copied, not modified.  The control flow is sklearn's: the divergence
+    before the loop, then after every 10th iteration (one scalar read back each), stopping when
+    ``(previous_error - error) / error_at_init < tol``; ``tol = 0`` runs exactly ``max_iter`` iterations with no
+    read-back.  Sums in a fixed order: the same input gives the same bits."""
+    X = X.detach().contiguous()
+    W, H = W0.detach().clone().contiguous(), H0.detach().clone().contiguous()
+    lib, N, D, L, nb = _nmf_args(X, W, H, "nmf_kl_mu")
+    max_iter = int(max_iter)
+
+    def update(k):
+        ws = _workspace(X.device, nb)
+        rc = lib.gpz_nmf_kl_update(_ptr(X), _ptr(W), _ptr(H), N, D, L, _dt(X), k, _ptr(ws), ws.numel(), _stream(X.device))
+        _lib.check(rc, "gpz_nmf_kl_update")
+
+    if max_iter < 1:
+        return W, H, 0
+    if not tol > 0:
+        update(max_iter)
+        return W, H, max_iter
+    out = torch.empty(1, dtype=torch.float64, device=X.device)
+    error_at_init = previous = _nmf_divergence(lib, X, W, H, N, D, L, nb, out)
+    n_iter = 0
+    while n_iter < max_iter:
+        k = min(10, max_iter - n_iter)
+        update(k)
+        n_iter += k
+        if n_iter % 10 == 0:
+            error = _nmf_divergence(lib, X, W, H, N, D, L, nb, out)
+            if (previous - error) / error_at_init < tol:
+                break
+            previous = error
+    return W, H, n_iter
+
+
 @_on_device
 def vnngp_forward(spec: KernelSpec, X, Z, mu, Lu_raw, jitter: float, K: int, clamp_min: float = 5e-2,
                   check_info: bool = True, idx=None, keep_state: bool = False) -> dict:

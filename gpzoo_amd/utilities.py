@@ -367,13 +367,124 @@ def dims_autocorr(factors, coords, sort=True, *, n_neighs=6):
     return order.astype(np.int64), I[order]
 
 
+def lnormal_approx_dirichlet(L):
+    """(mu, sigma) of the L independent lognormals that match the marginal means and variances of a flat symmetric
+    Dirichlet (alpha = L) of dimension L: sigma^2 = log(2 L / (L + 1)), mu = -log(L) - sigma^2 / 2 (both 0 at L = 1);
+    reference utilities.py:237-249."""
+    import numpy as np
+    sigma2 = np.log(2 * L) - np.log(L + 1)
+    mu = -np.log(L) - sigma2 / 2.0
+    return mu, np.sqrt(sigma2)
+
+
+def shrink_factors(F, shrinkage=0.2):
+    """Rows of F (N,L) pulled towards their own mean, F (1 - a) + a rowsum(F) / L: row sums are kept.  A shrinkage
+    outside (0, 1) returns F itself (reference utilities.py:301-306)."""
+    a = shrinkage
+    if 0 < a < 1:
+        F = F * (1 - a) + a * F.sum(axis=1, keepdims=True) / float(F.shape[1])
+    return F
+
+
+def shrink_loadings(W, shrinkage=0.2):
+    """Columns of W (D,L) pulled towards their own mean, W (1 - a) + a colsum(W) / D: column sums are kept.  A
+    shrinkage outside (0, 1) returns W itself (reference utilities.py:308-313)."""
+    a = shrinkage
+    if 0 < a < 1:
+        W = W * (1 - a) + a * W.sum(axis=0) / float(W.shape[0])
+    return W
+
+
+_NMF_KWARGS = ("solver", "beta_loss", "init", "max_iter", "tol", "random_state", "verbose", "shuffle", "alpha_W", "alpha_H",
+               "l1_ratio")
+
+
+def _nmf_options(kwargs):
+    """The sklearn NMF keywords regularized_nmf runs, checked before anything touches a GPU."""
+    for k in kwargs:
+        if k not in _NMF_KWARGS:
+            raise NotImplementedError(f"regularized_nmf: keyword {k!r} is not supported (supported: {', '.join(_NMF_KWARGS)})")
+    solver = kwargs.get("solver", "cd")
+    if solver != "mu":
+        raise NotImplementedError(f"regularized_nmf: solver={solver!r} is not supported: pass solver='mu' (the multiplicative-"
+                                  "update solver is the one rebuilt here; sklearn's default 'cd' is not)")
+    beta_loss = kwargs.get("beta_loss", "frobenius")
+    if not (beta_loss == "kullback-leibler" or (not isinstance(beta_loss, str) and beta_loss == 1)):
+        raise NotImplementedError(f"regularized_nmf: beta_loss={beta_loss!r} is not supported: pass "
+                                  "beta_loss='kullback-leibler' (or 1); sklearn's default 'frobenius' is not rebuilt")
+    if kwargs.get("alpha_W", 0.0) != 0.0:
+        raise NotImplementedError(f"regularized_nmf: alpha_W={kwargs['alpha_W']!r} is not supported (only 0.0: no regularisation)")
+    alpha_H = kwargs.get("alpha_H", "same")
+    if not (alpha_H == "same" or (not isinstance(alpha_H, str) and alpha_H == 0.0)):
+        raise NotImplementedError(f"regularized_nmf: alpha_H={alpha_H!r} is not supported (only 'same' or 0.0: no regularisation)")
+    init = kwargs.get("init", None)
+    if init not in (None, "random", "nndsvd", "nndsvda", "nndsvdar"):
+        raise NotImplementedError(f"regularized_nmf: init={init!r} is not supported (None, 'random', 'nndsvd', 'nndsvda', "
+                                  "'nndsvdar'; 'custom' starts go through factors= and loadings=)")
+    return init, int(kwargs.get("max_iter", 200)), float(kwargs.get("tol", 1e-4)), kwargs.get("random_state", None)
+
+
+def regularized_nmf(Y, L, sz=1, pseudocount=1e-2, factors=None, loadings=None, shrinkage=0.2, **kwargs):
+    """The NSF notebooks' starting values (reference utilities.py:253-299): a KL-divergence NMF of the nonnegative
+    (obs x feat) matrix Y with L components, loadings and factors shrunk towards a symmetric Dirichlet, the factors put
+    on the log scale (``log(pseudocount + eF) - log(sz)``) and recentred to the lognormal prior mean
+    ``lnormal_approx_dirichlet(max(L, 1.1))[0]``, the shift folded into the loadings.  Returns numpy ``(F (N,L), W (D,L))``.
+
+    ``factors`` and ``loadings`` both given: no NMF, only the post-processing, on the host (no GPU needed).  Unlike the
+    reference, which scales a float ``loadings`` argument in place when ``shrinkage`` is outside (0, 1), the caller's
+    arrays are never modified.
+
+    Otherwise the factorisation runs on the GPU -- Y's own if it is a CUDA tensor, else the current one: float32 stays
+    float32, everything else is computed in float64 (as sklearn does); ``nmf.initialize_nmf`` gives sklearn's starting
+    values and ``ops.nmf_kl_mu`` (gpz_nmf_kl_update) its multiplicative updates with its stopping rule.  The keywords are
+    sklearn's ``NMF``: ``solver='mu'`` and ``beta_loss='kullback-leibler'`` (or 1) are required -- sklearn's defaults,
+    coordinate descent on the Frobenius loss, are not rebuilt and raise NotImplementedError rather than return other
+    factors; ``init``, ``max_iter`` (200), ``tol`` (1e-4) and ``random_state`` act as in sklearn; ``verbose`` and
+    ``shuffle`` are accepted and ignored; ``alpha_W=0.0``, ``alpha_H`` in ('same', 0.0) and ``l1_ratio`` are accepted at
+    these no-regularisation values only.  ValueError: Y not 2-D, negative or non-finite entries (checked on the device,
+    one synchronisation), L outside 1..64, an NNDSVD init with L > min(N, D).  The output dtypes are the reference's:
+    for float32 Y, F is float64 (``np.log(sz)`` is a float64 scalar) and W float32."""
+    import numpy as np
+    L_int = int(L)
+    if factors is None or loadings is None:
+        init, max_iter, tol, random_state = _nmf_options(kwargs)
+        from . import nmf, ops
+        Yt = Y.detach() if isinstance(Y, torch.Tensor) else torch.as_tensor(np.asarray(Y))
+        if Yt.dim() != 2:
+            raise ValueError(f"regularized_nmf: Y must be (obs, feat), got shape {tuple(Yt.shape)}")
+        if not 1 <= L_int <= 64:
+            raise ValueError(f"regularized_nmf: L={L_int} unsupported (1..64)")
+        if init not in (None, "random") and L_int > min(Yt.shape):
+            raise ValueError(f"regularized_nmf: init={init!r} needs L <= min(N, D) = {min(Yt.shape)}, got L={L_int}")
+        n_sz = np.shape(sz)
+        if len(n_sz) and n_sz[0] not in (1, Yt.shape[0]):
+            raise ValueError(f"regularized_nmf: {n_sz[0]} size factors for {Yt.shape[0]} observations")
+        dev = Yt.device if Yt.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        Yt = Yt.to(device=dev, dtype=torch.float32 if Yt.dtype == torch.float32 else torch.float64).contiguous()
+        if not bool((torch.isfinite(Yt) & (Yt >= 0)).all()):
+            raise ValueError("regularized_nmf: Y holds a negative or non-finite value")
+        W0, H0 = nmf.initialize_nmf(Yt, L_int, init=init, random_state=random_state)
+        Wd, Hd, _ = ops.nmf_kl_mu(Yt, W0, H0, max_iter=max_iter, tol=tol)
+        eF, W = Wd.cpu().numpy(), Hd.cpu().numpy().T
+    else:
+        eF, W = np.asarray(factors), np.asarray(loadings)
+    W = shrink_loadings(W, shrinkage=shrinkage)
+    wsum = W.sum(axis=0)
+    eF = shrink_factors(eF * wsum, shrinkage=shrinkage)
+    F = np.log(pseudocount + eF) - np.log(sz)
+    shift = F.mean(axis=0) - lnormal_approx_dirichlet(max(L, 1.1))[0] * np.ones(L_int)
+    F = F - shift
+    scale = np.exp(shift - np.log(wsum))
+    W = (W * scale).astype(W.dtype, copy=False) if np.issubdtype(W.dtype, np.floating) else W * scale
+    return F, W
+
+
 # Host-side data preparation of the reference's utilities module (AnnData conversion, scanpy size factors,
-# sklearn NMF initialisation, plotting, ...) is outside the accelerated path and not rebuilt here.  The
-# names resolve so that ``from gpzoo.utilities import train_hybrid, anndata_to_train_val`` -- the notebooks'
-# import lines -- keep working; calling one says where it lives.
+# plotting, ...) is outside the accelerated path and not rebuilt here.  The names resolve so that
+# ``from gpzoo.utilities import train_hybrid, anndata_to_train_val`` -- the notebooks' import lines -- keep
+# working; calling one says where it lives.
 _NOT_REBUILT = ("build_group_distances", "init_softplus", "smooth_spatial_factors", "rescale_spatial_coords",
-                "anndata_to_train_val", "scanpy_sizefactors", "lnormal_approx_dirichlet",
-                "regularized_nmf", "shrink_factors", "shrink_loadings", "plot_factors")
+                "anndata_to_train_val", "scanpy_sizefactors", "plot_factors")
 
 
 def __getattr__(name):

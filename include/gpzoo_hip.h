@@ -19,7 +19,9 @@
  *    wrapper turns it into torch.linalg.LinAlgError like gp.py:213/270/360.
  *
  * Additions under version 212 (the version number is unchanged; nothing existing moved): gpz_spatial_knn,
- * gpz_morans_i and their *_workspace_bytes queries -- the spatial statistics of dims_autocorr (utilities.py:131-156).
+ * gpz_morans_i and their *_workspace_bytes queries -- the spatial statistics of dims_autocorr (utilities.py:131-156);
+ * gpz_nmf_kl_update, gpz_nmf_kl_divergence and gpz_nmf_kl_workspace_bytes -- the KL multiplicative-update NMF behind
+ * regularized_nmf (utilities.py:253-299, sklearn's NMF(solver='mu', beta_loss='kullback-leibler')).
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -339,6 +341,26 @@ int gpz_spatial_knn(const void* X, int64_t N, int32_t d, int32_t K, int32_t dtyp
 size_t gpz_morans_i_workspace_bytes(int64_t N, int64_t L, int32_t K);
 int gpz_morans_i(const void* values, int64_t N, int64_t L, int32_t dtype, const int64_t* nbr, int32_t K, double* I,
                  int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
+/* KL-divergence NMF by multiplicative updates: X (N,D) >= 0, dense row-major, ~ W (N,L) . H (L,D), all of `dtype`.
+ * One iteration is sklearn's _multiplicative_update_w followed by _multiplicative_update_h for beta_loss = 1, no
+ * regularisation (EPS = the float32 epsilon in both precisions):
+ *   P = W H, P[P < EPS] = EPS, Q = X / P;  W *= (Q H^T) / rowsum(H)             (a zero rowsum reads as EPS)
+ *   P = W H with the new W, clamped, Q = X / P;  H *= (W^T Q) / colsum(W)[:, None]  (a zero colsum reads as 1)
+ *   H[H < the float64 epsilon] = 0.
+ * gpz_nmf_kl_update runs `iters` >= 1 iterations on W and H in place.  P and Q are never stored: per iteration X is read
+ * twice and nothing of size N x D is written; the sum over N of the H update goes through per-slab partial sums in the
+ * workspace.  No atomics, every sum in a fixed order: repeated calls on the same input agree bit for bit, and one call of
+ * 2 k iterations equals two calls of k.
+ * gpz_nmf_kl_divergence writes sklearn's _beta_divergence(X, W, H, 1, square_root=True) to out (device fp64):
+ *   sqrt(2 max(0, sum_{X > EPS} X log(X / max(W H, EPS)) + colsum(W) . rowsum(H) - sum_{X > EPS} X)), summed in fp64.
+ * X must be finite and non-negative (not checked here).  1 <= L <= 64, N, D >= 1, N, D < 2^31, N D < 2^40; anything
+ * else is an argument error on the host, before any launch (the workspace query then returns 0). */
+size_t gpz_nmf_kl_workspace_bytes(int64_t N, int64_t D, int64_t L, int32_t dtype);
+int gpz_nmf_kl_update(const void* X, void* W, void* H, int64_t N, int64_t D, int64_t L, int32_t dtype, int64_t iters,
+                      void* ws, size_t ws_bytes, void* stream);
+int gpz_nmf_kl_divergence(const void* X, const void* W, const void* H, int64_t N, int64_t D, int64_t L, int32_t dtype,
+                          double* out, void* ws, size_t ws_bytes, void* stream);
 
 /* Multi-GPU: latent GPs shard across ranks with no data-path collective; the only exchange is
  * the sum of each rank's partial ELBO -- one ncclAllReduce(sum, fp64) over RCCL/xGMI.  The reference has no
