@@ -19,8 +19,9 @@ def kernel_for_config(c: dict) -> nn.Module:
         k = kernels.NSF_RBF(L=L)
         k.sigma = nn.Parameter(c["sigma"].reshape(L, 1, 1).clone())
         k.lengthscale = nn.Parameter(c["lengthscale"].reshape(L, 1, 1).clone())
-    elif kind == "matern32":
-        k = kernels.batched_Matern32()
+    elif kind in ("matern12", "matern32", "matern52"):
+        k = {"matern12": kernels.batched_Matern12, "matern32": kernels.batched_Matern32,
+             "matern52": kernels.batched_Matern52}[kind]()
         k.sigma = nn.Parameter(c["sigma"].clone())
         k.lengthscale = nn.Parameter(c["lengthscale"].clone())
     elif kind == "mggp_nsf_rbf":

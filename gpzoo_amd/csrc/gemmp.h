@@ -10,7 +10,7 @@ struct PanelArgs {
   const float* Kzx;                           // (L, Mp, ncp), zero beyond M rows / the real columns -- or null with Z set:
   const float* Z; const float* X;             // generated operand (panel_generates): (M, d) inducing points, (nreal, d) spots
   const float* sigma; const float* ell;       //   (L,) kernel parameters
-  int64_t M, nreal; int kind, d;              //   real rows / columns; GPZ_KERNEL_RBF / GPZ_KERNEL_MATERN32; d in {1, 2}
+  int64_t M, nreal; int kind, d;              //   real rows / columns; GPZ_KERNEL_RBF / GPZ_KERNEL_MATERN{32,12,52}; d in {1, 2}
   float* Wt;                                  // out (L, Mp, ncp), or null: Wt never leaves the chip
   const float* muE;                           // (L, Mp), zero padded
   float* ps1; float* pm1; float* ps2;         // out [L][Mp/128][ncp], per 128-row block: colsum(Wt^2), muE^T Wt, colsum((LuT Wt)^2)

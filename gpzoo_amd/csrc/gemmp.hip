@@ -80,9 +80,16 @@ template <int NB> __device__ __forceinline__ int row_block_of(int w) {
   else return w;
 }
 
-// GEN: 0 the Kzx panel is read from memory (the stand-alone fill wrote it); 1 + 2 * KIND + (D - 1): the fetching waves
-// compute it themselves (cov.h: the fill's own arithmetic, same bits) -- fp32 RBF (KIND 0) / Matern-3/2 (KIND 1) on 1-D / 2-D
-// inputs -- and Kzx never exists.
+// GEN: 0 the Kzx panel is read from memory (the stand-alone fill wrote it); 1 + 2 * slot + (D - 1): the fetching waves
+// compute it themselves (cov.h: the fill's own arithmetic, same bits) -- fp32 RBF (slot 0) / Matern-3/2 (1) / Matern-1/2 (2) /
+// Matern-5/2 (3) on 1-D / 2-D inputs -- and Kzx never exists.
+constexpr int P_GEN_KINDS[4] = {GPZ_KERNEL_RBF, GPZ_KERNEL_MATERN32, GPZ_KERNEL_MATERN12, GPZ_KERNEL_MATERN52};
+constexpr int panel_gen_kind(int gen) { return P_GEN_KINDS[(gen - 1) >> 1]; }
+constexpr int panel_gen_of(int kind, int d) {     // 0: this kind has no generator
+  for (int i = 0; i < 4; ++i)
+    if (P_GEN_KINDS[i] == kind) return 1 + 2 * i + (d - 1);
+  return 0;
+}
 template <int NB, bool STORE, int GEN>
 __global__ __launch_bounds__(64 * NB) void panel_kernel(const PanelParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -149,7 +156,7 @@ __global__ __launch_bounds__(64 * NB) void panel_kernel(const PanelParams p) {
       // Computed: a fetching wave takes sixteen groups of four consecutive k (inducing points: wave-uniform)
       // for all 64 columns (one spot per lane, in registers) -- a lane's four values are one 16-byte LDS write.  Padded rows
       // and columns are exactly zero, as the stand-alone fill writes them.
-      constexpr int KIND = (GEN - 1) >> 1, D = ((GEN - 1) & 1) + 1;
+      constexpr int KIND = panel_gen_kind(GEN), D = ((GEN - 1) & 1) + 1;
       const CovConst cc = cov_const<KIND>(p.sigma[l], p.ell[l]);
       const int64_t n = col0 + lane;
       const bool real = n < p.nreal;
@@ -174,7 +181,7 @@ __global__ __launch_bounds__(64 * NB) void panel_kernel(const PanelParams p) {
 #pragma unroll
           for (int kk = 0; kk < D; ++kk) z[kk] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, zl[kk]), 4 * i + e));
           const float keep = colf * __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rowf), 4 * i + e));
-          pv[i][e] = keep * cov_value<KIND>(cov_radial<KIND>(cov_d2<D>(z, xc)), cc.amp, cc.c0, cc.c1);
+          pv[i][e] = keep * cov_value<KIND>(cov_radial<KIND>(cov_d2<D>(z, xc)), cc.amp, cc.c0, cc.c1, cc.c2);
         }
       }
     }
@@ -425,7 +432,7 @@ __global__ __launch_bounds__(64 * NB) void panel_kernel(const PanelParams p) {
 static unsigned long long* g_panel_stamps = nullptr;
 
 bool panel_generates(int kind, int d) {
-  return (kind == GPZ_KERNEL_RBF || kind == GPZ_KERNEL_MATERN32) && (d == 1 || d == 2);
+  return (d == 1 || d == 2) && panel_gen_of(kind, d) != 0;
 }
 
 bool panel_supported(int64_t Mp, int64_t ncp) {
@@ -481,7 +488,7 @@ int panel_launch(const PanelArgs& a, hipStream_t s) {
   if (a.Z) {       // generated operand
     GPZ_REQUIRE(panel_generates(a.kind, a.d) && a.X && a.sigma && a.ell && a.M >= 1 && a.M <= a.Mp && a.nreal >= 1 && a.nreal <= a.ncp,
                 "panel_launch: bad generator arguments (kind=%d d=%d)", a.kind, a.d);
-    gen = 1 + 2 * (a.kind == GPZ_KERNEL_MATERN32 ? 1 : 0) + (a.d - 1);
+    gen = panel_gen_of(a.kind, a.d);
     p.Z = a.Z; p.X = a.X; p.sigma = a.sigma; p.ell = a.ell; p.M = (int)a.M; p.nreal = (int)a.nreal;
   } else {
     GPZ_REQUIRE(a.Kzx, "panel_launch: neither a Kzx buffer nor generator arguments");
@@ -493,6 +500,10 @@ int panel_launch(const PanelArgs& a, hipStream_t s) {
       case 2: return launch_t<NBV, 2>(p, store, s);          \
       case 3: return launch_t<NBV, 3>(p, store, s);          \
       case 4: return launch_t<NBV, 4>(p, store, s);          \
+      case 5: return launch_t<NBV, 5>(p, store, s);          \
+      case 6: return launch_t<NBV, 6>(p, store, s);          \
+      case 7: return launch_t<NBV, 7>(p, store, s);          \
+      case 8: return launch_t<NBV, 8>(p, store, s);          \
       default: return launch_t<NBV, 0>(p, store, s);         \
     }
   switch (a.Mp / 32) {

@@ -10,7 +10,7 @@ struct Fused1Args {
   const float* Linv; int64_t Mp;              // (L, Mp, Mp) fp32 copy of chol(Kzz)^{-1}, identity padded
   const float* Z; int64_t M;                  // (M, d) inducing inputs
   const float* X; int64_t nreal;              // this chunk's spots (nreal, d)
-  int d, kind, L;                             // d in {1, 2}; kind GPZ_KERNEL_RBF / GPZ_KERNEL_MATERN32
+  int d, kind, L;                             // d in {1, 2}; kind GPZ_KERNEL_RBF / GPZ_KERNEL_MATERN{32,12,52}
   const float* sigma; const float* ell;       // (L,)
   float* Wt; int64_t ncp;                     // out (L, Mp, ncp): zero beyond M rows / nreal columns
   const float* muE;                           // (L, Mp), zero padded

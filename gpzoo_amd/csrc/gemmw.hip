@@ -225,8 +225,8 @@ __global__ __launch_bounds__(64 * (TM / 128) * (TN / 32)) __attribute__((amdgpu_
   // ahead.  Thread (wave w, lane l) computes rows w and w + 8 of the 16-deep step at columns l, l + 64, ...: its z is a
   // wave-uniform LDS broadcast, its x sits in registers for the whole tile.
   constexpr int NXC = TN / 64;                  // columns per lane
-  float xc[NXC][D], ampn[NXC], c0n[NXC];
-  CovConst cc = {0.f, 0.f, 0.f};
+  float xc[NXC][D], ampn[NXC], c0n[NXC], c2n[NXC];
+  CovConst cc = {0.f, 0.f, 0.f, 0.f};
   if constexpr (BSRC == WB_GEN) {
     cc = cov_const<KIND>(p.sigma[b0], p.ell[b0]);
 #pragma unroll
@@ -236,7 +236,8 @@ __global__ __launch_bounds__(64 * (TM / 128) * (TN / 32)) __attribute__((amdgpu_
 #pragma unroll
       for (int k = 0; k < D; ++k) xc[h][k] = real ? p.X[n * D + k] : 0.f;
       ampn[h] = real ? cc.amp : 0.f;            // padded columns: exactly zero, as the stand-alone fill writes them
-      c0n[h] = (KIND == 1 && !real) ? 0.f : cc.c0;   // (Matern: c0 carries the amplitude too)
+      c0n[h] = (KIND != 0 && !real) ? 0.f : cc.c0;   // (Matern: c0 carries the amplitude too,
+      c2n[h] = real ? cc.c2 : 0.f;                   //  and so does the quadratic coefficient of Matern-5/2)
     }
   }
   auto z_load = [&](int blk) __attribute__((always_inline)) {
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(64 * (TM / 128) * (TN / 32)) __attribute__((amdgpu_
 #pragma unroll
       for (int h = 0; h < NXC; ++h) {
         const float v = (GPZ_W_ABL & 1) ? z[0] + xc[h][0]
-                                        : cov_value<KIND>(cov_radial<KIND>(cov_d2<D>(z, xc[h])), ampn[h], c0n[h], cc.c1);
+                                        : cov_value<KIND>(cov_radial<KIND>(cov_d2<D>(z, xc[h])), ampn[h], c0n[h], cc.c1, c2n[h]);
         sB(buf)[addrB(kk, h * 64 + lane)] = v;
       }
     }
@@ -849,7 +850,8 @@ static int launch_wide(K kernel, size_t lds, const WParams& p, int64_t nblocks, 
 }
 
 bool fused1_supported(int dtype, int kind, int d) {
-  return dtype == GPZ_F32 && (kind == GPZ_KERNEL_RBF || kind == GPZ_KERNEL_MATERN32) && (d == 1 || d == 2);
+  return dtype == GPZ_F32 && (d == 1 || d == 2) &&
+         (kind == GPZ_KERNEL_RBF || kind == GPZ_KERNEL_MATERN32 || kind == GPZ_KERNEL_MATERN12 || kind == GPZ_KERNEL_MATERN52);
 }
 
 int fused1_launch(const Fused1Args& a, hipStream_t s) {
@@ -878,6 +880,8 @@ int fused1_launch(const Fused1Args& a, hipStream_t s) {
 #define GPZ_W1(KIND, D) return launch_wide(gemmw_kernel<TM, TN, WB_GEN, WA_LOWER, WE_STORE_STATS, KIND, D>, \
                                            WLds<TM, TN, WB_GEN, D>::bytes, p, nblocks, s, 1024)
   if (a.kind == GPZ_KERNEL_MATERN32) { if (a.d == 2) GPZ_W1(1, 2); GPZ_W1(1, 1); }
+  if (a.kind == GPZ_KERNEL_MATERN12) { if (a.d == 2) GPZ_W1(4, 2); GPZ_W1(4, 1); }
+  if (a.kind == GPZ_KERNEL_MATERN52) { if (a.d == 2) GPZ_W1(5, 2); GPZ_W1(5, 1); }
   if (a.d == 2) GPZ_W1(0, 2);
   GPZ_W1(0, 1);
 #undef GPZ_W1

@@ -1,7 +1,7 @@
 // kfill.hip -- pairwise-distance + covariance fill for L latents at once.
 //
 // Replaces kernel.forward(A, B) of gpzoo/kernels.py (RBF :118-130, NSF_RBF
-// :146-155, batched_RBF :42-58, batched_Matern32 :14-30, MGGP_* :75-104,
+// :146-155, batched_RBF :42-58, batched_Matern32 :14-30 (and the Matern-1/2 / -5/2 forms of it), MGGP_* :75-104,
 // :176-228) and the in-place diagonal jitter of utilities.py:407-418.
 //
 // HBM-write bound: one squared distance per (i,j) pair is shared by all L
@@ -64,15 +64,17 @@ __device__ __forceinline__ int checked_group(const int64_t* g, int64_t i, int G,
   return (int)v;
 }
 
-// KIND: 0 RBF, 1 Matern-3/2, 2 MGGP RBF, 3 plain distance.  VECST: aligned 16-byte stores allowed.
+// KIND: 0 RBF, 1 Matern-3/2, 2 MGGP RBF, 3 plain distance, 4 Matern-1/2, 5 Matern-5/2.  VECST: aligned 16-byte stores allowed.
 template <typename Tin, typename To, int KIND, bool VECST>
 __global__ __launch_bounds__(KF_TX* KF_TY) void kfill_kernel(KfillArgs a) {
   constexpr int VEC = VecOf<To>::N;
   // fp32 RBF / Matern values come from cov.h, the definition the fused stage-1 product shares (bitwise equal)
-  constexpr bool F32COV = std::is_same<To, float>::value && (KIND == 0 || KIND == 1);
+  constexpr bool F32COV = std::is_same<To, float>::value && (KIND == 0 || KIND == 1 || KIND == 4 || KIND == 5);
+  constexpr bool RADIAL = KIND == 1 || KIND == 3 || KIND == 4 || KIND == 5;     // works on r, not r^2
   __shared__ To s_amp[KF_MAXL];     // sigma^2
-  __shared__ To s_coef[KF_MAXL];    // RBF: -0.5/ell^2 ; Matern: sqrt(3)/ell   (F32COV: cov_const's c0)
+  __shared__ To s_coef[KF_MAXL];    // RBF: -0.5/ell^2 ; Matern: sqrt(2 nu)/ell   (F32COV: cov_const's c0)
   __shared__ To s_c1[F32COV ? KF_MAXL : 1];
+  __shared__ To s_c2[F32COV && KIND == 5 ? KF_MAXL : 1];
   __shared__ To s_tab[KIND == 2 ? 2 * KF_MAXTAB : 2];  // MGGP: [l][ga][gb] -> {exp coef, amplitude}
 
   const int tid = threadIdx.y * KF_TX + threadIdx.x;
@@ -83,9 +85,11 @@ __global__ __launch_bounds__(KF_TX* KF_TY) void kfill_kernel(KfillArgs a) {
     if constexpr (F32COV) {
       const CovConst cc = cov_const<KIND>((float)s, (float)e);
       s_amp[l] = cc.amp; s_coef[l] = cc.c0; s_c1[l] = cc.c1;
+      if constexpr (KIND == 5) s_c2[l] = cc.c2;
     } else {
       s_amp[l] = s * s;
-      s_coef[l] = (KIND == 1) ? (To)1.7320508075688772935 / e : (To)-0.5 / (e * e);
+      s_coef[l] = (KIND == 1) ? (To)1.7320508075688772935 / e : (KIND == 4) ? (To)1 / e
+                  : (KIND == 5) ? (To)2.2360679774997896964 / e : (To)-0.5 / (e * e);
     }
   }
   if (KIND == 2) {
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(KF_TX* KF_TY) void kfill_kernel(KfillArgs a) {
       To acc = 0;
       for (int k = 0; k < d; ++k) { const To df = ax[k] - bx[v][k]; acc = fma(df, df, acc); }
       if constexpr (F32COV) d2[v] = cov_radial<KIND>(acc);
-      else d2[v] = (KIND == 1 || KIND == 3) ? fast_sqrt(acc) : acc;
+      else d2[v] = RADIAL ? fast_sqrt(acc) : acc;
     }
     To* Krow = static_cast<To*>(a.K) + i * a.ldk + j0;
     for (int l = 0; l < L; ++l) {
@@ -149,7 +153,7 @@ __global__ __launch_bounds__(KF_TX* KF_TY) void kfill_kernel(KfillArgs a) {
         const int64_t j = j0 + v;
         To val;
         if constexpr (F32COV) {
-          val = cov_value<KIND>(d2[v], amp, cf, s_c1[l]);
+          val = cov_value<KIND>(d2[v], amp, cf, s_c1[l], KIND == 5 ? s_c2[l] : 0.f);
         } else if (KIND == 0) {
           val = amp * fast_exp(cf * d2[v]);
         } else if (KIND == 1) {
@@ -157,6 +161,11 @@ __global__ __launch_bounds__(KF_TX* KF_TY) void kfill_kernel(KfillArgs a) {
           val = amp * ((To)1 + t) * fast_exp(-t);
         } else if (KIND == 3) {
           val = d2[v];
+        } else if (KIND == 4) {
+          val = amp * fast_exp(-(cf * d2[v]));
+        } else if (KIND == 5) {
+          const To t = cf * d2[v];
+          val = amp * ((To)1 + t + t * t / (To)3) * fast_exp(-t);
         } else {
           const int t = 2 * ((l * G + gai) * G + gb[v]);
           val = s_tab[t + 1] * fast_exp(s_tab[t] * d2[v]);
@@ -210,6 +219,8 @@ static int launch_kfill(const gpz_kernel_desc* k, KfillArgs a, hipStream_t s) {
       case GPZ_KERNEL_RBF: GPZ_KF(0); break;
       case GPZ_KERNEL_MATERN32: GPZ_KF(1); break;
       case GPZ_KERNEL_DISTANCE: GPZ_KF(3); break;
+      case GPZ_KERNEL_MATERN12: GPZ_KF(4); break;
+      case GPZ_KERNEL_MATERN52: GPZ_KF(5); break;
       default: GPZ_KF(2); break;
     }
 #undef GPZ_KF
@@ -224,7 +235,7 @@ int kfill_padded(const gpz_kernel_desc* k, const void* A, int64_t nA, int64_t pA
                  double jitter, int pad_identity, int out_dtype, hipStream_t s, int32_t* bad_group) {
   GPZ_REQUIRE(k && A && B && K, "gpz_kfill: null pointer");
   GPZ_REQUIRE(d >= 1 && d <= 4, "gpz_kfill: input dimension %d unsupported (1..4)", d);
-  GPZ_REQUIRE(k->kind >= 0 && k->kind <= 3, "gpz_kfill: unknown kernel kind %d", k->kind);
+  GPZ_REQUIRE(k->kind >= 0 && k->kind <= GPZ_KERNEL_MATERN52, "gpz_kfill: unknown kernel kind %d", k->kind);
   GPZ_REQUIRE(k->n_latent >= 1, "gpz_kfill: n_latent must be >= 1");
   GPZ_REQUIRE(k->dtype == GPZ_F32 || k->dtype == GPZ_F64, "gpz_kfill: bad dtype");
   GPZ_REQUIRE(!(k->dtype == GPZ_F64 && out_dtype == GPZ_F32), "gpz_kfill: fp64 inputs need fp64 output");

@@ -10,7 +10,9 @@
 // over N-chunks accumulate without atomics (bitwise reproducible).
 // The Matern-3/2 derivative w.r.t. z is written in its r -> 0 limit-safe form
 // dk/dz = -sigma^2 (3 / l^2) exp(-sqrt3 r / l) (z - x); the reference's autograd returns NaN there
-// (sqrt at 0), the true derivative is 0.
+// (sqrt at 0), the true derivative is 0.  Matern-5/2 likewise:
+// dk/dz = -sigma^2 (5 / (3 l^2)) (1 + v) exp(-v) (z - x), v = sqrt5 r / l.  Matern-1/2 has a kink at r = 0:
+// dk/dz = -(k / l) (z - x) / r elsewhere, and 0 at coincident points (the unit vector is formed under a d2 > 0 guard).
 #include "common.h"
 
 namespace gpz {
@@ -30,6 +32,8 @@ __device__ __forceinline__ float kg_exp(float x) { return __builtin_amdgcn_exp2f
 __device__ __forceinline__ double kg_exp(double x) { return exp(x); }
 __device__ __forceinline__ float kg_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double kg_sqrt(double x) { return sqrt(x); }
+__device__ __forceinline__ float kg_rsqrt(float x) { return rsqrtf(x); }
+__device__ __forceinline__ double kg_rsqrt(double x) { return 1.0 / sqrt(x); }
 __device__ __forceinline__ float kg_pow(float x, float y) { return __builtin_amdgcn_exp2f(y * __builtin_amdgcn_logf(x)); }
 __device__ __forceinline__ double kg_pow(double x, double y) { return pow(x, y); }
 
@@ -86,6 +90,16 @@ __global__ __launch_bounds__(256) void kgrad_kernel(KgradArgs a) {
         psig += g[u] * (T)2 * sig * ((T)1 + v) * e;
         pell += g[u] * s2 * v * v * e / ell;
         cz = -s2 * (T)3 * il2 * e;
+      } else if (KIND == 4) {
+        const T rr = kg_sqrt(d2), kv = s2 * kg_exp(-rr / ell);
+        psig += g[u] * (T)2 * kv / sig;
+        pell += g[u] * kv * rr * il2;
+        cz = d2 > (T)0 ? -(kv / ell) * kg_rsqrt(d2) : (T)0;      // diff / r, 0 at the kink
+      } else if (KIND == 5) {
+        const T v = (T)2.2360679774997896964 * kg_sqrt(d2) / ell, e = kg_exp(-v), q3 = v * v / (T)3;
+        psig += g[u] * (T)2 * sig * ((T)1 + v + q3) * e;
+        pell += g[u] * s2 * q3 * ((T)1 + v) * e / ell;
+        cz = -s2 * (T)5 / (T)3 * il2 * ((T)1 + v) * e;
       } else {
         const T r2 = static_cast<const T*>(a.gr2)[gz * a.G + gx[u]];
         const T den = aeff * r2 + (T)1;
@@ -115,11 +129,15 @@ __global__ __launch_bounds__(256) void kgrad_kernel(KgradArgs a) {
 }
 
 int kgrad_launch(int dtype, int kind, const KgradArgs& a, int L, hipStream_t s) {
-  GPZ_REQUIRE(kind >= 0 && kind <= 2, "kgrad: unknown kernel kind %d", kind);
+  GPZ_REQUIRE((kind >= 0 && kind <= 2) || kind == GPZ_KERNEL_MATERN12 || kind == GPZ_KERNEL_MATERN52,
+              "kgrad: unknown kernel kind %d", kind);
   dim3 grid((unsigned)((a.M + 3) / 4), (unsigned)L), block(256);
 #define GPZ_KG(T, K) hipLaunchKernelGGL((kgrad_kernel<T, K>), grid, block, 0, s, a)
-  if (dtype == GPZ_F32) { if (kind == 0) GPZ_KG(float, 0); else if (kind == 1) GPZ_KG(float, 1); else GPZ_KG(float, 2); }
-  else { if (kind == 0) GPZ_KG(double, 0); else if (kind == 1) GPZ_KG(double, 1); else GPZ_KG(double, 2); }
+#define GPZ_KG_KINDS(T) \
+  switch (kind) { case 0: GPZ_KG(T, 0); break; case 1: GPZ_KG(T, 1); break; case 4: GPZ_KG(T, 4); break; \
+                  case 5: GPZ_KG(T, 5); break; default: GPZ_KG(T, 2); break; }
+  if (dtype == GPZ_F32) GPZ_KG_KINDS(float) else GPZ_KG_KINDS(double)
+#undef GPZ_KG_KINDS
 #undef GPZ_KG
   GPZ_LAUNCH_OK();
   return 0;
@@ -173,7 +191,8 @@ extern "C" int gpz_kgrad(const gpz_kernel_desc* k, const void* A, int64_t nA, co
   GPZ_REQUIRE(k && A && B && Kbar && ws, "gpz_kgrad: null pointer");
   GPZ_REQUIRE(nA >= 1 && nB >= 1 && ldk >= nB && d >= 1 && d <= 4, "gpz_kgrad: bad extents nA=%lld nB=%lld ldk=%lld d=%d",
               (long long)nA, (long long)nB, (long long)ldk, d);
-  GPZ_REQUIRE(k->kind >= 0 && k->kind <= 2, "gpz_kgrad: kernel kind %d has no parameters to differentiate", k->kind);
+  GPZ_REQUIRE((k->kind >= 0 && k->kind <= 2) || k->kind == GPZ_KERNEL_MATERN12 || k->kind == GPZ_KERNEL_MATERN52,
+              "gpz_kgrad: kernel kind %d has no parameters to differentiate", k->kind);
   GPZ_REQUIRE(k->n_latent >= 1 && (k->dtype == GPZ_F32 || k->dtype == GPZ_F64), "gpz_kgrad: bad kernel description");
   if (k->kind == GPZ_KERNEL_MGGP_RBF)
     GPZ_REQUIRE(gA && gB && k->group_a && k->group_r2 && k->n_groups >= 1, "gpz_kgrad: MGGP kernel needs groups, group_a, group_r2");

@@ -91,10 +91,10 @@ class _HipKernel(nn.Module):
         mine = getattr(type(self), "covariance", None)
         if mine is None:
             return
-        shipped = any(mine is getattr(c, "covariance", None) for c in (batched_RBF, batched_Matern32, batched_MGGP_RBF))
+        shipped = any(mine is getattr(c, "covariance", None) for c in (batched_RBF, batched_Matern32, batched_Matern12, batched_Matern52, batched_MGGP_RBF))
         if not shipped or "covariance" in self.__dict__:
             raise NotImplementedError(
-                f"{type(self).__name__}.covariance is user-defined: gpzoo_amd evaluates the closed-form RBF / Matern-3/2 / "
+                f"{type(self).__name__}.covariance is user-defined: gpzoo_amd evaluates the closed-form RBF / Matern-1/2, -3/2, -5/2 / "
                 "multi-group RBF covariances in HIP and has no generic (vmap) path; use the reference package for custom kernels")
 
     def _spec(self, n_latent: int | None = None) -> KernelSpec:
@@ -165,6 +165,43 @@ class batched_Matern32(_HipKernel):
     def covariance(self, x1, x2):
         v = (3 ** 0.5) * torch.sqrt(((x1 - x2) ** 2).sum()) / self.lengthscale
         return (self.sigma ** 2) * (1 + v) * torch.exp(-v)
+
+    def forward(self, X, Z, diag=False):
+        return super().forward(X, Z, diag=diag)
+
+
+class batched_Matern12(_HipKernel):
+    """sigma^2 exp(-r / l), the exponential (Ornstein-Uhlenbeck) kernel: the closed form of a reference
+    ``batched_Matern32`` subclass that overrides ``covariance`` (kernels.py:14-20).  The derivative with respect to a
+    point does not exist at r = 0 (a kink); the backward returns 0 there."""
+    _kind = _lib.KERNEL_MATERN12
+
+    def __init__(self, sigma=1.0, lengthscale=2.0):
+        super().__init__()
+        self.sigma = nn.Parameter(torch.tensor(sigma))
+        self.lengthscale = nn.Parameter(torch.tensor(lengthscale))
+
+    def covariance(self, x1, x2):
+        v = torch.sqrt(((x1 - x2) ** 2).sum()) / self.lengthscale
+        return (self.sigma ** 2) * torch.exp(-v)
+
+    def forward(self, X, Z, diag=False):
+        return super().forward(X, Z, diag=diag)
+
+
+class batched_Matern52(_HipKernel):
+    """sigma^2 (1 + v + v^2 / 3) exp(-v), v = sqrt5 r / l: like ``batched_Matern12`` the closed form of a
+    ``covariance`` override of the reference's vmap kernel (kernels.py:14-20)."""
+    _kind = _lib.KERNEL_MATERN52
+
+    def __init__(self, sigma=1.0, lengthscale=2.0):
+        super().__init__()
+        self.sigma = nn.Parameter(torch.tensor(sigma))
+        self.lengthscale = nn.Parameter(torch.tensor(lengthscale))
+
+    def covariance(self, x1, x2):
+        v = (5 ** 0.5) * torch.sqrt(((x1 - x2) ** 2).sum()) / self.lengthscale
+        return (self.sigma ** 2) * (1 + v + v * v / 3) * torch.exp(-v)
 
     def forward(self, X, Z, diag=False):
         return super().forward(X, Z, diag=diag)
@@ -287,4 +324,4 @@ def kernel_spec(kernel: nn.Module, X: torch.Tensor, n_latent: int | None = None)
     if isinstance(kernel, _HipKernel):
         return kernel._spec(n_latent)
     raise TypeError(f"{type(kernel).__name__} has no HIP implementation: gpzoo_amd supports the closed-form "
-                    "kernels of gpzoo.kernels (RBF, Matern-3/2 and multi-group RBF families)")
+                    "kernels of gpzoo.kernels (RBF, Matern-1/2, -3/2, -5/2 and multi-group RBF families)")

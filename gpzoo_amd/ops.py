@@ -498,7 +498,7 @@ def svgp_forward(spec: KernelSpec, X, Z, mu, Lu_raw, jitter: float, whitened: bo
     ``retain_wt`` > 0: keep Wt of every chunk for ``svgp_backward(wt_cache=out["wt_cache"])`` when it fits
     in that fraction of the free device memory (288 GB HBM: 52 GB at N=200k, M=2048, L=32, fp32).
     ``materialize_kzx``: True = write every Kzx chunk to HBM and run the triangular product on it (the reference's
-    structure), False = the product that generates its covariance operand itself (fp32 RBF / Matern-3/2, d <= 2), None =
+    structure), False = the product that generates its covariance operand itself (fp32 RBF / Matern-1/2, -3/2, -5/2, d <= 2), None =
     the library's choice; ``narrow_tiles``: the 128 x 128-tile kernel of the other precisions for the two big fp32
     products; ``panel_products`` (fp32, M <= 512): both products in one launch on 64-column panels held in LDS.  Same Wt
     bits on every path."""

@@ -34,13 +34,19 @@ def _softplus(v: float) -> float:
 
 
 def make_config(cfg: int, *, N: int | None = None, M: int | None = None, L: int | None = None,
-                latents: range | None = None, dtype: torch.dtype | None = None) -> dict:
+                latents: range | None = None, dtype: torch.dtype | None = None, kind: str | None = None) -> dict:
     """Draw configuration ``cfg`` (1..5), optionally scaled down via N/M/L.
 
     ``latents`` restricts the per-latent arrays (sigma, lengthscale, mu, Lu_raw,
     y, group_diff) to a contiguous latent range -- the block a rank owns.
+    ``kind`` swaps the Matern smoothness of configurations 3 and 4 ("matern12", "matern32", "matern52"): the same
+    draws under another kernel; the numbered configurations themselves keep theirs.
     """
     c = dict(CONFIGS[cfg])
+    if kind is not None and kind != c["kind"]:
+        if c["kind"] != "matern32" or kind not in ("matern12", "matern52"):
+            raise ValueError(f"make_config: kind={kind!r} is not available for configuration {cfg} ({c['kind']})")
+        c["kind"] = kind
     N = c["N"] if N is None else N
     M = c["M"] if M is None else M
     L = c["L"] if L is None else L

@@ -21,7 +21,9 @@
  * Additions under version 212 (the version number is unchanged; nothing existing moved): gpz_spatial_knn,
  * gpz_morans_i and their *_workspace_bytes queries -- the spatial statistics of dims_autocorr (utilities.py:131-156);
  * gpz_nmf_kl_update, gpz_nmf_kl_divergence and gpz_nmf_kl_workspace_bytes -- the KL multiplicative-update NMF behind
- * regularized_nmf (utilities.py:253-299, sklearn's NMF(solver='mu', beta_loss='kullback-leibler')).
+ * regularized_nmf (utilities.py:253-299, sklearn's NMF(solver='mu', beta_loss='kullback-leibler'));
+ * GPZ_KERNEL_MATERN12 and GPZ_KERNEL_MATERN52 -- two more values of gpz_kernel_desc.kind, accepted wherever
+ * GPZ_KERNEL_MATERN32 is (gpz_kfill, gpz_kgrad, gpz_svgp_forward / _backward and the Poisson entries; not gpz_vnngp).
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -42,7 +44,10 @@ enum {
   GPZ_KERNEL_RBF = 0,      /* RBF, NSF_RBF, batched_RBF      kernels.py:34-59,106-155  */
   GPZ_KERNEL_MATERN32 = 1, /* batched_Matern32               kernels.py:6-30           */
   GPZ_KERNEL_MGGP_RBF = 2, /* MGGP_RBF, MGGP_NSF_RBF, batched_MGGP_RBF  kernels.py:62-104,158-228 */
-  GPZ_KERNEL_DISTANCE = 3  /* plain Euclidean distance (return_distance=True, kernels.py:118,125-126) */
+  GPZ_KERNEL_DISTANCE = 3, /* plain Euclidean distance (return_distance=True, kernels.py:118,125-126) */
+  GPZ_KERNEL_MATERN12 = 4, /* batched_Matern12: sigma^2 exp(-r / l), the closed form of a batched_Matern32 subclass
+                              whose covariance() is the exponential (Ornstein-Uhlenbeck) kernel  kernels.py:6-30 */
+  GPZ_KERNEL_MATERN52 = 5  /* batched_Matern52: sigma^2 (1 + v + v^2 / 3) exp(-v), v = sqrt(5) r / l  (same) */
 };
 
 /* Hyper-parameters of one covariance family for L independent latents.
@@ -88,8 +93,8 @@ int gpz_kfill(const gpz_kernel_desc* k, const void* A, int64_t nA, const void* B
  * 75-104, 114-130, 139-155, 176-228; e.g. the inline ExactGP of exact_mggp.ipynb).  Outputs fp64:
  * grad_theta (L,4) = d/dsigma, d/dlengthscale, d/dgroup_a (effective multiplier), 0;  grad_A (nA,4), first d
  * columns used, summed over latents (NULL: skipped).  For dLoss/dB call it again with A and B (and the groups)
- * swapped and Kbar transposed.  Matern-3/2: dK/dA at coincident points is 0 (its limit; the reference's
- * autograd yields NaN there).  GPZ_KERNEL_DISTANCE is not differentiable here. */
+ * swapped and Kbar transposed.  Matern-3/2 and -5/2: dK/dA at coincident points is 0 (its limit; the reference's
+ * autograd yields NaN there); Matern-1/2 has a kink there and 0 is returned as well.  GPZ_KERNEL_DISTANCE is not differentiable here. */
 size_t gpz_kgrad_workspace_bytes(int64_t nA, int32_t n_latent);
 int gpz_kgrad(const gpz_kernel_desc* k, const void* A, int64_t nA, const void* B, int64_t nB, int32_t d,
               const int64_t* gA, const int64_t* gB, const void* Kbar, int64_t ldk, int64_t stride_k,
