@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""The NSF notebooks' initialisation chain, every step of it on this package (no sklearn, anndata or squidpy):
+
+    rescale_spatial_coords -> regularized_nmf -> inducing points -> smooth_spatial_factors -> gp.mu, model.W -> train
+
+on synthetic counts, against the same model started from mu = 0 and random loadings.
+
+    PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30]
+"""
+import argparse
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from gpzoo.gp import SVGP
+from gpzoo.kernels import NSF_RBF
+from gpzoo.likelihoods import NSF2
+from gpzoo.utilities import (init_softplus, regularized_nmf, rescale_spatial_coords, scanpy_sizefactors,
+                             smooth_spatial_factors, train)
+
+
+def synthetic_counts(N, D, L, rng):
+    X = (rng.random((N, 2)) * np.array([[6400.0, 3100.0]]) + 500.0).astype(np.float32)          # pixel coordinates
+    centres = X[rng.choice(N, L, replace=False)]
+    F = np.exp(-((X[None] - centres[:, None]) ** 2).sum(-1) / (2 * 700.0 ** 2))                  # (L,N)
+    W = rng.random((D, L)) ** 3 * 4.0
+    return X, rng.poisson(W @ F + 0.05).T.astype(np.float32)                                     # Y (N,D)
+
+
+def model_for(X, Y, Z, L, dev, mu=None, W=None):
+    kernel = NSF_RBF(sigma=1.0, lengthscale=0.4, L=L)
+    gp = SVGP(kernel, dim=2, M=len(Z), jitter=1e-2)
+    gp.Z = nn.Parameter(torch.as_tensor(Z), requires_grad=False)
+    gp.mu = nn.Parameter(torch.zeros(L, len(Z)) if mu is None else torch.as_tensor(mu, dtype=torch.float32))
+    gp.Lu = nn.Parameter(1e-2 * torch.eye(len(Z)).repeat(L, 1, 1))
+    kernel.sigma.requires_grad_(False); kernel.lengthscale.requires_grad_(False)                 # as in the notebooks
+    model = NSF2(gp, torch.as_tensor(Y.T), L=L)
+    if W is not None:
+        model.W = nn.Parameter(torch.as_tensor(init_softplus(W), dtype=torch.float32))           # softplus(model.W) = W
+    return model.to(dev)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--spots", type=int, default=20000)
+    ap.add_argument("--genes", type=int, default=500)
+    ap.add_argument("--factors", type=int, default=6)
+    ap.add_argument("--inducing", type=int, default=500)
+    ap.add_argument("--steps", type=int, default=30)
+    a = ap.parse_args()
+    dev = torch.device("cuda")
+    rng = np.random.default_rng(0)
+    X, Y = synthetic_counts(a.spots, a.genes, a.factors, rng)
+    L, M = a.factors, a.inducing
+
+    X = rescale_spatial_coords(X)                                                                # roughly (-2, 2)
+    sz = scanpy_sizefactors(Y)
+    F, W = regularized_nmf(torch.as_tensor(Y, device=dev), L, sz=sz, solver="mu", init="nndsvdar",
+                           beta_loss="kullback-leibler", max_iter=200, random_state=0)
+    Z = X[rng.choice(a.spots, M, replace=False)]
+    U, beta0, beta = smooth_spatial_factors(F, Z, X)
+    print(f"N={a.spots} D={a.genes} L={L} M={M}: F {F.shape} {F.dtype}, U {U.shape} {U.dtype}, trend {beta.shape}")
+
+    Xd, Yd = torch.as_tensor(X, device=dev), torch.as_tensor(Y.T, device=dev)
+    for name, model in (("NMF + smooth_spatial_factors", model_for(X, Y, Z, L, dev, mu=U.T, W=W)),
+                        ("mu = 0, random loadings", model_for(X, Y, Z, L, dev))):
+        with torch.no_grad():
+            model.V.copy_(torch.as_tensor(init_softplus(sz[:, 0].astype(np.float64))))
+        opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=1e-2)
+        losses = train(model, opt, Xd, Yd, dev, steps=a.steps, E=3)
+        print(f"  {name:30s} loss {losses[0]:.4g} -> {losses[-1]:.4g}")
+
+
+if __name__ == "__main__":
+    main()

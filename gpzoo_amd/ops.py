@@ -782,6 +782,42 @@ def morans_i(values, nbr) -> torch.Tensor:
     return out
 
 
+@_on_device
+def knn_mean(X, F, Z, K: int, return_index: bool = False):
+    """(M,L) fp64 mean of F (N,L) over the K rows of X (N,d) nearest to each row of Z (M,d), d <= 4, L <= 256
+    (gpz_knn_mean): sklearn's ``KNeighborsRegressor(n_neighbors=K).fit(X, F).predict(Z)``.  X and Z fp32 or fp64 (both
+    are taken as fp64 when they differ), F fp32 or fp64.  The K smallest (fp64 squared distance, index) keys are selected exactly,
+    ties to the lower index; sums in a fixed order: repeated calls agree bit for bit.  ``return_index``: also the
+    (M,K) int64 table of the selected rows, each query's in ascending index order."""
+    _need_cuda(X, F, Z)
+    lib = _lib.load()
+    if X.dim() != 2 or F.dim() != 2 or Z.dim() != 2:
+        raise ValueError(f"knn_mean: X (N, d), F (N, L) and Z (M, d) expected, got {tuple(X.shape)}, {tuple(F.shape)} and "
+                         f"{tuple(Z.shape)}")
+    if F.shape[0] != X.shape[0]:
+        raise ValueError(f"knn_mean: {X.shape[0]} rows of X but {F.shape[0]} of F")
+    if Z.shape[1] != X.shape[1]:
+        raise ValueError(f"knn_mean: X has {X.shape[1]} coordinates per point, Z {Z.shape[1]}")
+    N, d = X.shape
+    M, L, K = Z.shape[0], F.shape[1], int(K)
+    if not 1 <= K <= N:
+        raise ValueError(f"knn_mean: K={K} outside 1..N={N}")
+    ct = X.dtype if X.dtype == Z.dtype else torch.float64       # (either cast is exact)
+    X = X.detach().to(ct).contiguous()
+    Z = Z.detach().to(ct).contiguous()
+    F = F.detach().contiguous()
+    nb = lib.gpz_knn_mean_workspace_bytes(N, M, d, K, L)
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    U = torch.empty((M, L), dtype=torch.float64, device=X.device)
+    idx = torch.empty((M, K), dtype=torch.int64, device=X.device) if return_index else None
+    ws = _workspace(X.device, nb)
+    rc = lib.gpz_knn_mean(_ptr(X), N, _ptr(Z), M, d, _dt(X), _ptr(F), L, _dt(F), K, _ptr(U), _ptr(idx), _ptr(ws),
+                          ws.numel(), _stream(X.device))
+    _lib.check(rc, "gpz_knn_mean")
+    return (U, idx) if return_index else U
+
+
 def _nmf_args(X, W, H, who: str):
     _need_cuda(X, W, H)
     if X.dim() != 2 or W.dim() != 2 or H.dim() != 2 or W.shape[0] != X.shape[0] or H.shape[1] != X.shape[1] or W.shape[1] != H.shape[0]:

@@ -479,12 +479,119 @@ def regularized_nmf(Y, L, sz=1, pseudocount=1e-2, factors=None, loadings=None, s
     return F, W
 
 
-# Host-side data preparation of the reference's utilities module (AnnData conversion, scanpy size factors,
-# plotting, ...) is outside the accelerated path and not rebuilt here.  The names resolve so that
+def init_softplus(mat, minval=1e-5):
+    """A copy of the numpy array ``mat`` with every entry x < 20 replaced by ``log(exp(x) - 1 + minval)``, the inverse
+    of softplus floored by ``minval``: raw parameters whose softplus is ``mat`` (reference utilities.py:38-43).  Entries
+    >= 20 are their own inverse to rounding and stay."""
+    import numpy as np
+    out = np.array(mat, copy=True)
+    small = out < 20
+    out[small] = np.log(np.exp(out[small]) - 1 + minval)
+    return out
+
+
+def scanpy_sizefactors(Y):
+    """(N,1) size factors of the count matrix Y (obs x feat): the row totals over their median (reference
+    utilities.py:232-234)."""
+    import numpy as np
+    totals = Y.sum(axis=1, keepdims=True)
+    return totals / np.median(totals)
+
+
+def rescale_spatial_coords(X, box_side=4):
+    """The coordinates X (N,d) shifted to a zero minimum, scaled by ``box_side`` over the geometric mean of the
+    extents -- the aspect ratio is kept and the bounding box gets the volume ``box_side ** d`` -- and centred at their
+    mean; ``box_side=4`` puts them roughly in (-2, 2) (reference utilities.py:177-190).  The arithmetic is the
+    reference's, in X's own floating dtype.  Unlike the reference, which shifts and scales the caller's array in place
+    before it returns the centred copy, the caller's array is never modified; the returned values are the same."""
+    import numpy as np
+    X = np.array(X, copy=True)
+    if not np.issubdtype(X.dtype, np.floating):
+        X = X.astype(np.float64)
+    X -= X.min(axis=0)
+    X *= box_side / np.exp(np.mean(np.log(X.max(axis=0))))
+    return X - X.mean(axis=0)
+
+
+def smooth_spatial_factors(F, Z, X=None):
+    """Starting values of an NSF model at its inducing points from factors at the spots (reference utilities.py:50-68;
+    ``regularized_nmf`` gives F (N,L) on the log scale, ``gp.mu`` is U.T).  Returns numpy ``(U (M,L), beta0 (L,),
+    beta (L,d))``:
+
+    ``U``: for each row of Z (M,d) the uniform mean of F over the ``K = max(2, ceil(N / M))`` spots of X (N,d) nearest to
+    it -- sklearn's ``KNeighborsRegressor(n_neighbors=K).fit(X, F).predict(Z)`` -- as one HIP selection
+    (``ops.knn_mean``, gpz_knn_mean) on the GPU of the tensor arguments, or on the current GPU for numpy / host inputs.
+    The K smallest (fp64 squared distance, index) keys are taken: sklearn's set wherever no exact distance tie falls on
+    the K-th place (there its tree's visit order decides, here the lower index) -- the one place the result can differ
+    from the reference.  ``beta0``, ``beta``: intercept and coefficients of the least-squares trend of F on X, sklearn's
+    ``LinearRegression().fit(X, F)``: the centred normal equations are formed in fp64 on the device and their
+    minimum-norm solution (``numpy.linalg.lstsq``) is taken on the host, which is sklearn's answer for rank-deficient
+    (e.g. collinear) coordinates too.
+
+    ``X=None``: ``beta0 = F.mean(0)``, U is that mean tiled M times and beta is None -- on the host, no GPU needed.
+
+    F, Z, X: numpy arrays or torch tensors, host or CUDA.  Everything is computed in fp64 and rounded at the end:
+    float32 F gives float32 outputs (as the reference does), anything else float64.  ValueError, before anything touches
+    a GPU: F not (N,L), Z or X not 2-D, row counts of F and X that differ, coordinate dimensions that differ or lie
+    outside 1..4, L > 256, N < K; after one device check: a non-finite coordinate or factor."""
+    import math
+    import numpy as np
+
+    def as_tensor(a):
+        return a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+    Ft, Zt = as_tensor(F), as_tensor(Z)
+    if Ft.dim() != 2:
+        raise ValueError(f"smooth_spatial_factors: F must be (N, L), got shape {tuple(Ft.shape)}")
+    if Zt.dim() != 2:
+        raise ValueError(f"smooth_spatial_factors: Z must be (M, d), got shape {tuple(Zt.shape)}")
+    N, L = Ft.shape
+    M = Zt.shape[0]
+    out = np.float32 if Ft.dtype == torch.float32 else np.float64
+    if X is None:
+        beta0 = Ft.cpu().numpy().astype(np.float64).mean(axis=0)
+        return np.tile(beta0, [M, 1]).astype(out), beta0.astype(out), None
+    Xt = as_tensor(X)
+    if Xt.dim() != 2:
+        raise ValueError(f"smooth_spatial_factors: X must be (N, d), got shape {tuple(Xt.shape)}")
+    if Xt.shape[0] != N:
+        raise ValueError(f"smooth_spatial_factors: {N} rows of F but {Xt.shape[0]} of X")
+    d = Xt.shape[1]
+    if Zt.shape[1] != d:
+        raise ValueError(f"smooth_spatial_factors: X has {d} coordinates per point, Z {Zt.shape[1]}")
+    if not 1 <= d <= 4:
+        raise ValueError(f"smooth_spatial_factors: coordinates of dimension {d} unsupported (1..4)")
+    if not 1 <= L <= 256:
+        raise ValueError(f"smooth_spatial_factors: L={L} unsupported (1..256)")
+    if M < 1:
+        raise ValueError("smooth_spatial_factors: Z holds no inducing point")
+    K = max(2, math.ceil(N / M))
+    if N < K:
+        raise ValueError(f"smooth_spatial_factors: {N} observations, at least n_neighbors={K} needed")
+    from . import ops
+    dev = next((t.device for t in (Ft, Zt, Xt) if t.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ct = torch.float32 if Xt.dtype == Zt.dtype == torch.float32 else torch.float64
+    Xt, Zt = Xt.to(device=dev, dtype=ct), Zt.to(device=dev, dtype=ct)
+    Ft = Ft.to(device=dev, dtype=torch.float32 if Ft.dtype == torch.float32 else torch.float64)
+    if not bool(torch.isfinite(Xt).all() & torch.isfinite(Zt).all() & torch.isfinite(Ft).all()):
+        raise ValueError("smooth_spatial_factors: F, Z or X holds a non-finite value")
+    U = ops.knn_mean(Xt, Ft, Zt, K).cpu().numpy()
+    Xd, Fd = Xt.double(), Ft.double()
+    mx, mf = Xd.mean(dim=0), Fd.mean(dim=0)
+    Xc, Fc = Xd - mx, Fd - mf
+    G, C = (Xc.t() @ Xc).cpu().numpy(), (Xc.t() @ Fc).cpu().numpy()
+    beta = np.linalg.lstsq(G, C, rcond=None)[0].T
+    beta0 = mf.cpu().numpy() - beta @ mx.cpu().numpy()
+    return U.astype(out), beta0.astype(out), beta.astype(out)
+
+
+# Host-side data preparation of the reference's utilities module (AnnData conversion, plotting, ...) is outside the
+# accelerated path and not rebuilt here.  The names resolve so that
 # ``from gpzoo.utilities import train_hybrid, anndata_to_train_val`` -- the notebooks' import lines -- keep
 # working; calling one says where it lives.
-_NOT_REBUILT = ("build_group_distances", "init_softplus", "smooth_spatial_factors", "rescale_spatial_coords",
-                "anndata_to_train_val", "scanpy_sizefactors", "plot_factors")
+_NOT_REBUILT = ("build_group_distances", "anndata_to_train_val", "plot_factors")
 
 
 def __getattr__(name):

@@ -23,7 +23,9 @@
  * gpz_nmf_kl_update, gpz_nmf_kl_divergence and gpz_nmf_kl_workspace_bytes -- the KL multiplicative-update NMF behind
  * regularized_nmf (utilities.py:253-299, sklearn's NMF(solver='mu', beta_loss='kullback-leibler'));
  * GPZ_KERNEL_MATERN12 and GPZ_KERNEL_MATERN52 -- two more values of gpz_kernel_desc.kind, accepted wherever
- * GPZ_KERNEL_MATERN32 is (gpz_kfill, gpz_kgrad, gpz_svgp_forward / _backward and the Poisson entries; not gpz_vnngp).
+ * GPZ_KERNEL_MATERN32 is (gpz_kfill, gpz_kgrad, gpz_svgp_forward / _backward and the Poisson entries; not gpz_vnngp);
+ * gpz_knn_mean and gpz_knn_mean_workspace_bytes -- the exact K-nearest mean of the factors at the inducing points behind
+ * smooth_spatial_factors (utilities.py:50-68, sklearn's KNeighborsRegressor.predict).
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -366,6 +368,22 @@ int gpz_nmf_kl_update(const void* X, void* W, void* H, int64_t N, int64_t D, int
                       void* ws, size_t ws_bytes, void* stream);
 int gpz_nmf_kl_divergence(const void* X, const void* W, const void* H, int64_t N, int64_t D, int64_t L, int32_t dtype,
                           double* out, void* ws, size_t ws_bytes, void* stream);
+
+/* Exact K-nearest mean: for each of M query points Z (M,d) the mean of F (N,L) over the K points of X (N,d) nearest to it
+ * -- sklearn's KNeighborsRegressor(n_neighbors=K).fit(X, F).predict(Z) with uniform weights (smooth_spatial_factors,
+ * utilities.py:66-67).  X and Z share `dtype`, F has `f_dtype` (fp32 or fp64 each), all row-major.  d^2 is sklearn's: the
+ * coordinates converted to fp64, each (x_k - z_k)^2 rounded, the terms added in coordinate order; a NaN d^2 ranks as +inf.
+ * The K smallest keys (d^2, index) are selected -- exact ties go to the lower index, which is sklearn's set wherever no
+ * exact tie falls on the K-th place -- by a radix select on the bit pattern of d^2, recomputed in every pass: nothing of
+ * size M x N is stored and nothing is sorted.
+ *   U (M,L) fp64: U[m] = (sum of F[n] over the selected n) / K, fp64 accumulators, the spots dealt to threads and the
+ *   partial sums combined in a fixed order, no floating-point atomics: repeated calls agree bit for bit.
+ *   idx (M,K) int64 or NULL: the selected points of each query in ASCENDING INDEX order (not by distance).
+ * 1 <= d <= 4, 1 <= K <= N < 2^31, 1 <= M < 2^31, 1 <= L <= 256; anything else is an argument error on the host, before
+ * any launch (the workspace query then returns 0).  The workspace holds the fp64 coordinates: (N + M) d doubles. */
+size_t gpz_knn_mean_workspace_bytes(int64_t N, int64_t M, int32_t d, int64_t K, int64_t L);
+int gpz_knn_mean(const void* X, int64_t N, const void* Z, int64_t M, int32_t d, int32_t dtype, const void* F, int64_t L,
+                 int32_t f_dtype, int64_t K, double* U, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
 
 /* Multi-GPU: latent GPs shard across ranks with no data-path collective; the only exchange is
  * the sum of each rank's partial ELBO -- one ncclAllReduce(sum, fp64) over RCCL/xGMI.  The reference has no
