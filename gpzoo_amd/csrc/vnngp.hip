@@ -123,6 +123,57 @@ __global__ __launch_bounds__(256) void knn_kernel(const T* __restrict__ X, int64
 // The sorted list above holds KM >= K entries; only a list of exactly K entries reproduces
 // "the K smallest" (a longer list is a superset and its first K entries are the same).
 
+// ---- k(x, z_idx) of the point kernels, fp64, by kernel kind (a compile-time parameter: no branch per neighbour) ----
+// KIND is the ABI's kernel kind: 0 RBF, 1 Matern-3/2, 4 Matern-1/2, 5 Matern-5/2 (kernels.py:14-20, 42-47 and the two
+// closed forms of cov.h).  VnnCov holds a latent's constants: s2 = sigma^2, a = -1 / (2 l^2) (RBF) or sqrt(2 nu) / l.
+struct VnnCov { double sg, el, s2, a; };
+
+template <int KIND>
+__device__ __forceinline__ VnnCov vnn_cov_const(double sg, double el) {
+  VnnCov c;
+  c.sg = sg; c.el = el; c.s2 = sg * sg;
+  c.a = KIND == GPZ_KERNEL_RBF ? -0.5 / (el * el)
+      : KIND == GPZ_KERNEL_MATERN32 ? 1.7320508075688772935 / el
+      : KIND == GPZ_KERNEL_MATERN52 ? 2.2360679774997896964 / el : 1.0 / el;
+  return c;
+}
+
+template <int KIND>
+__device__ __forceinline__ double vnn_cov(const VnnCov& c, double d2) {
+  if (KIND == GPZ_KERNEL_RBF) return c.s2 * exp(c.a * d2);
+  const double v = c.a * sqrt(d2);
+  if (KIND == GPZ_KERNEL_MATERN32) return c.s2 * (1.0 + v) * exp(-v);
+  if (KIND == GPZ_KERNEL_MATERN52) return c.s2 * (1.0 + v + v * v * (1.0 / 3.0)) * exp(-v);
+  return c.s2 * exp(-v);
+}
+
+// Backward of one neighbour: gkp = dLoss/dk_p.  Adds gkp dk/dsigma = gkp 2 k / sigma and gkp dk/dl to the point's totals
+// and returns the factor cz of dk/dz = cz (x - z), which the point kernel leaves in the record for the gather.  The
+// Matern forms are written so that r -> 0 is safe (as kgrad.hip's): nu = 3/2, 5/2 have cz finite there, the kink of
+// nu = 1/2 gives 0.
+template <int KIND>
+__device__ __forceinline__ double vnn_cov_bwd(const VnnCov& c, double il2, double gkp, double kx, double d2, double& dsig,
+                                              double& dell) {
+  const double gk = gkp * kx;
+  dsig += gk * 2.0 / c.sg;
+  if (KIND == GPZ_KERNEL_RBF) {
+    dell += gk * d2 * il2 / c.el;                      // dk/dl = k d^2 / l^3
+    return kx * il2;                                   // dk/dz = k (x - z) / l^2
+  }
+  const double r = sqrt(d2);
+  if (KIND == GPZ_KERNEL_MATERN12) {
+    dell += gk * r * il2;                              // k r / l^2
+    return d2 > 0.0 ? kx / (c.el * r) : 0.0;           // k / (l r)
+  }
+  const double v = c.a * r, se = c.s2 * exp(-v);
+  if (KIND == GPZ_KERNEL_MATERN32) {
+    dell += gkp * se * v * v / c.el;                   // sigma^2 v^2 e^-v / l
+    return 3.0 * se * il2;                             // 3 sigma^2 e^-v / l^2
+  }
+  dell += gkp * se * v * v * (1.0 + v) / (3.0 * c.el); // sigma^2 v^2 (1 + v) e^-v / (3 l)
+  return 5.0 * se * (1.0 + v) * il2 * (1.0 / 3.0);     // 5 sigma^2 (1 + v) e^-v / (3 l^2)
+}
+
 template <typename T>
 struct VnnArgs {
   const T* X; const T* Z; const T* sigma; const T* ell; const T* mu;
@@ -137,20 +188,20 @@ struct VnnArgs {
 
 // Per-point forward state left in the thread's scratch columns: A = Cholesky factor of the jittered
 // K x K block (lower), kx = k(x, z_idx), w = A^{-1} kx, sw = S_block w.  Returns mean and the unclamped cov.
-template <typename T>
+template <typename T, int KIND>
 __device__ __forceinline__ void vnn_point_solve(const VnnArgs<T>& a, int64_t total, int l, int64_t n,
                                                 const int64_t* id, double* A, double* kx, double* w, double* sw,
                                                 double& mean, double& cov) {
   const int K = a.K;
   const double* Kl = a.Kzz + (int64_t)l * a.Mp * a.Mp;
   const double* Sl = a.S + (int64_t)l * a.Mp * a.Mp;
-  const double sg = (double)a.sigma[l], el = (double)a.ell[l];
-  const double s2 = sg * sg, c = -0.5 / (el * el);
+  const VnnCov cc = vnn_cov_const<KIND>((double)a.sigma[l], (double)a.ell[l]);
+  const double s2 = cc.s2;
   for (int p = 0; p < K; ++p) {
     const int64_t ip = id[p];
     double d2 = 0;
     for (int k = 0; k < a.d; ++k) { const double df = (double)a.X[n * a.d + k] - (double)a.Z[ip * a.d + k]; d2 += df * df; }
-    kx[p * total] = s2 * exp(c * d2);
+    kx[p * total] = vnn_cov<KIND>(cc, d2);
     for (int q = 0; q <= p; ++q) A[(int64_t)(p * K + q) * total] = Kl[ip * a.Mp + id[q]] + (p == q ? a.jitter : 0.0);
   }
   // in-place Cholesky of the K x K block (lower), then two triangular solves
@@ -189,7 +240,7 @@ __device__ __forceinline__ void vnn_point_solve(const VnnArgs<T>& a, int64_t tot
   cov = s2 + wsw - wk;
 }
 
-template <typename T>
+template <typename T, int KIND>
 __global__ __launch_bounds__(256) void vnngp_point_kernel(VnnArgs<T> a) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)a.L * a.N;
@@ -201,7 +252,7 @@ __global__ __launch_bounds__(256) void vnngp_point_kernel(VnnArgs<T> a) {
   double* kx = a.scratch + (int64_t)K * K * total + t;     // kx[p] at kx[p * total]
   double* w = kx + (int64_t)K * total;
   double mean, cov;
-  vnn_point_solve<T>(a, total, l, n, a.idx + n * K, A, kx, w, nullptr, mean, cov);
+  vnn_point_solve<T, KIND>(a, total, l, n, a.idx + n * K, A, kx, w, nullptr, mean, cov);
   if (!(cov > a.clamp_min)) cov = a.clamp_min;
   a.mean[t] = (T)mean;
   a.scale[t] = (T)sqrt(cov);
@@ -215,8 +266,10 @@ struct VnnBwdArgs {
   double* gS;                   // (L,Mp,Mp)  T with dLoss/dS = T + T^T
   double* gK;                   // (L,Mp,Mp)  T with T + T^T = 2 sym(dLoss/d(Kzz + jitter I)) from the K x K blocks, or null
   double* kacc;                 // (L,Mp,8)   dz0..3, dsigma, dlengthscale (kgrad.hip layout), or null
-  T* rec;                       // [L*N][3K + 2], in the problem's precision: per point w[K], v[K], kx[K], gm, gcov CONTIGUOUS -- what vnngp_gather_kernel
-                                // reads per entry (from the [column][point] scratch every value is a 64-byte sector of its own)
+  T* rec;                       // [L*N][3K + 2], in the problem's precision: per point w[K], v[K], cz[K], gm, gcov CONTIGUOUS -- what vnngp_gather_kernel
+                                // reads per entry (from the [column][point] scratch every value is a 64-byte sector of its own).
+                                // cz[p] is the factor of dk(x, z_p)/dz_p = cz[p] (x - z_p): the gather needs neither the
+                                // lengthscale nor the kernel kind (zeros when no kernel / Z gradient is asked for)
   const int32_t* inv;           // (N*K) entries n * 32 + p grouped by the inducing point they name, ascending inside a group
   const int32_t* start;         // (M + 1) group boundaries in inv
   const int32_t* dup;           // one word: non-zero when some point names an inducing point twice (caller-supplied tables
@@ -230,7 +283,7 @@ struct VnnBwdArgs {
   const T* Xp;                  // (N,d) points in that order
 };
 
-template <typename T>
+template <typename T, int KIND>
 __global__ __launch_bounds__(256) void vnngp_point_bwd_kernel(VnnBwdArgs<T> b) {
   const VnnArgs<T>& a = b.f;
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -248,7 +301,7 @@ __global__ __launch_bounds__(256) void vnngp_point_bwd_kernel(VnnBwdArgs<T> b) {
   double* sw = w + (int64_t)K * total;
   double* v = sw + (int64_t)K * total;
   double mean, cov;
-  vnn_point_solve<T>(a, total, l, n, id, A, kx, w, sw, mean, cov);
+  vnn_point_solve<T, KIND>(a, total, l, n, id, A, kx, w, sw, mean, cov);
   const double gm = (double)b.g_mean[tn];
   // scale = sqrt(clamp(cov, min)): no gradient through a clamped variance (gp.py:117)
   const double gcov = (cov > a.clamp_min) ? 0.5 * (double)b.g_scale[tn] / sqrt(cov) : 0.0;
@@ -268,25 +321,26 @@ __global__ __launch_bounds__(256) void vnngp_point_bwd_kernel(VnnBwdArgs<T> b) {
   // What the scatter needs per point stays in its scratch columns (w, v, kx are there already): the sums over the
   // points that name an inducing point are formed by vnngp_gather_kernel in a FIXED order (no atomics: the backward is
   // bitwise reproducible; rounds 1-3 added these contributions with fp64 atomics in arrival order).
-  const double sg = (double)a.sigma[l], el = (double)a.ell[l], il2 = 1.0 / (el * el);
-  double dsig = gcov * 2.0 * sg, dell = 0.0;
-  if (b.kacc)
-    for (int p = 0; p < K; ++p) {
+  const VnnCov cc = vnn_cov_const<KIND>((double)a.sigma[l], (double)a.ell[l]);
+  const double il2 = 1.0 / (cc.el * cc.el);
+  double dsig = gcov * 2.0 * cc.sg, dell = 0.0;
+  T* rec = b.rec + t * (3 * K + 2);
+  for (int p = 0; p < K; ++p) {
+    double cz = 0.0;                                   // dk_p/dz = cz (x - z): the record's third vector
+    if (b.kacc) {
       const int64_t ip = id[p];
-      const double gk = (v[p * total] - gcov * w[p * total]) * kx[p * total];   // dLoss/dk_p * k_p
       double d2 = 0.0;
       for (int k = 0; k < a.d; ++k) {
         const double df = (double)a.X[n * a.d + k] - (double)a.Z[ip * a.d + k];
         d2 += df * df;
       }
-      dsig += gk * 2.0 / sg;
-      dell += gk * d2 * il2 / el;
+      cz = vnn_cov_bwd<KIND>(cc, il2, v[p * total] - gcov * w[p * total], kx[p * total], d2, dsig, dell);
     }
+    rec[p] = (T)w[p * total]; rec[K + p] = (T)v[p * total]; rec[2 * K + p] = (T)cz;
+  }
+  rec[3 * K] = (T)gm; rec[3 * K + 1] = (T)gcov;
   double* ex = v + (int64_t)K * total;
   ex[0] = gm; ex[total] = gcov; ex[2 * total] = dsig; ex[3 * total] = dell;
-  T* rec = b.rec + t * (3 * K + 2);
-  for (int p = 0; p < K; ++p) { rec[p] = (T)w[p * total]; rec[K + p] = (T)v[p * total]; rec[2 * K + p] = (T)kx[p * total]; }
-  rec[3 * K] = (T)gm; rec[3 * K + 1] = (T)gcov;
 }
 
 // ---- the same two kernels with the K x K system in REGISTERS (K <= 16) ----
@@ -298,15 +352,15 @@ __global__ __launch_bounds__(256) void vnngp_point_bwd_kernel(VnnBwdArgs<T> b) {
 // kernels read afterwards (same scratch columns as above; the factor's columns stay unwritten).
 template <int KT> __device__ __forceinline__ constexpr int vtri(int p, int q) { return p * (p + 1) / 2 + q; }
 
-template <typename T, int KT>
+template <typename T, int KT, int KIND>
 __device__ __forceinline__ void vnn_point_solve_reg(const VnnArgs<T>& a, int l, int64_t n, const int64_t* idp,
                                                     double (&A)[KT * (KT + 1) / 2], double (&kx)[KT], double (&w)[KT],
                                                     double (&sw)[KT], int64_t (&id)[KT], double& mean, double& cov) {
   const int K = a.K;
   const double* Kl = a.Kzz + (int64_t)l * a.Mp * a.Mp;
   const double* Sl = a.S + (int64_t)l * a.Mp * a.Mp;
-  const double sg = (double)a.sigma[l], el = (double)a.ell[l];
-  const double s2 = sg * sg, c = -0.5 / (el * el);
+  const VnnCov cc = vnn_cov_const<KIND>((double)a.sigma[l], (double)a.ell[l]);
+  const double s2 = cc.s2;
 #pragma unroll
   for (int p = 0; p < KT; ++p) id[p] = p < K ? idp[p] : 0;
 #pragma unroll
@@ -314,7 +368,7 @@ __device__ __forceinline__ void vnn_point_solve_reg(const VnnArgs<T>& a, int l, 
     if (p < K) {
       double d2 = 0;
       for (int k = 0; k < a.d; ++k) { const double df = (double)a.X[n * a.d + k] - (double)a.Z[id[p] * a.d + k]; d2 += df * df; }
-      kx[p] = s2 * exp(c * d2);
+      kx[p] = vnn_cov<KIND>(cc, d2);
     } else {
       kx[p] = 0.0;
     }
@@ -370,7 +424,7 @@ __device__ __forceinline__ void vnn_point_solve_reg(const VnnArgs<T>& a, int l, 
   cov = s2 + wsw - wk;
 }
 
-template <typename T, int KT>
+template <typename T, int KT, int KIND>
 __global__ __launch_bounds__(256) void vnngp_point_reg_kernel(VnnArgs<T> a) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)a.L * a.N;
@@ -379,13 +433,13 @@ __global__ __launch_bounds__(256) void vnngp_point_reg_kernel(VnnArgs<T> a) {
   const int64_t n = t - (int64_t)l * a.N;
   double A[KT * (KT + 1) / 2], kx[KT], w[KT], sw[KT], mean, cov;
   int64_t id[KT];
-  vnn_point_solve_reg<T, KT>(a, l, n, a.idx + n * a.K, A, kx, w, sw, id, mean, cov);
+  vnn_point_solve_reg<T, KT, KIND>(a, l, n, a.idx + n * a.K, A, kx, w, sw, id, mean, cov);
   if (!(cov > a.clamp_min)) cov = a.clamp_min;
   a.mean[t] = (T)mean;
   a.scale[t] = (T)sqrt(cov);
 }
 
-template <typename T, int KT>
+template <typename T, int KT, int KIND>
 __global__ __launch_bounds__(256) void vnngp_point_bwd_reg_kernel(VnnBwdArgs<T> b) {
   const VnnArgs<T>& a = b.f;
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -398,7 +452,7 @@ __global__ __launch_bounds__(256) void vnngp_point_bwd_reg_kernel(VnnBwdArgs<T> 
   const int K = a.K;
   double A[KT * (KT + 1) / 2], kx[KT], w[KT], sw[KT], v[KT], mean, cov;
   int64_t id[KT];
-  vnn_point_solve_reg<T, KT>(a, l, n, a.idx + n * K, A, kx, w, sw, id, mean, cov);
+  vnn_point_solve_reg<T, KT, KIND>(a, l, n, a.idx + n * K, A, kx, w, sw, id, mean, cov);
   const double gm = (double)b.g_mean[tn];
   const double gcov = (cov > a.clamp_min) ? 0.5 * (double)b.g_scale[tn] / sqrt(cov) : 0.0;
 #pragma unroll
@@ -418,24 +472,26 @@ __global__ __launch_bounds__(256) void vnngp_point_bwd_reg_kernel(VnnBwdArgs<T> 
     for (int k = i + 1; k < KT; ++k) r -= A[vtri<KT>(k, i)] * v[k];
     v[i] = r / A[vtri<KT>(i, i)];
   }
-  const double sg = (double)a.sigma[l], el = (double)a.ell[l], il2 = 1.0 / (el * el);
-  double dsig = gcov * 2.0 * sg, dell = 0.0;
-  // the per-point record vnngp_gather_kernel reads, and the two per-latent totals' terms in their scratch columns
+  const VnnCov cc = vnn_cov_const<KIND>((double)a.sigma[l], (double)a.ell[l]);
+  const double il2 = 1.0 / (cc.el * cc.el);
+  double dsig = gcov * 2.0 * cc.sg, dell = 0.0;
+  // the per-point record vnngp_gather_kernel reads (w, v and cz with dk_p/dz = cz (x - z)), and the two per-latent totals'
+  // terms in their scratch columns
   T* rec = b.rec + t * (3 * K + 2);
 #pragma unroll
   for (int p = 0; p < KT; ++p)
     if (p < K) {
-      rec[p] = (T)w[p]; rec[K + p] = (T)v[p]; rec[2 * K + p] = (T)kx[p];
+      rec[p] = (T)w[p]; rec[K + p] = (T)v[p];
+      double cz = 0.0;
       if (b.kacc) {
-        const double gk = (v[p] - gcov * w[p]) * kx[p];
         double d2 = 0.0;
         for (int k = 0; k < a.d; ++k) {
           const double df = (double)a.X[n * a.d + k] - (double)a.Z[id[p] * a.d + k];
           d2 += df * df;
         }
-        dsig += gk * 2.0 / sg;
-        dell += gk * d2 * il2 / el;
+        cz = vnn_cov_bwd<KIND>(cc, il2, v[p] - gcov * w[p], kx[p], d2, dsig, dell);
       }
+      rec[2 * K + p] = (T)cz;
     }
   rec[3 * K] = (T)gm; rec[3 * K + 1] = (T)gcov;
   double* ex = a.scratch + (int64_t)(K * K + 4 * K) * total + t;
@@ -572,8 +628,7 @@ __global__ __launch_bounds__(64) void vnngp_gather_kernel(VnnBwdArgs<T> b) {
   if (!(GPZ_VN_ABL & 4))
     for (int64_t j = lane; j < (KG ? 2 : 1) * a.Mp; j += 64) vnn_rows[j] = 0.0;
   __syncthreads();
-  const int R = 3 * K + 2;                    // record: w[K], v[K], kx[K], gm, gcov
-  const double el = (double)a.ell[l], il2 = 1.0 / (el * el);
+  const int R = 3 * K + 2;                    // record: w[K], v[K], cz[K], gm, gcov
   double gmu = 0.0, dz = 0.0;                 // lane 0: gmu; lanes k < d: dz_k
   const int32_t e0 = b.start[ip], e1 = b.start[ip + 1];
   // With pairwise distinct neighbours the lanes q <= p of an entry add into distinct columns of the two rows.  A table that
@@ -584,7 +639,7 @@ __global__ __launch_bounds__(64) void vnngp_gather_kernel(VnnBwdArgs<T> b) {
   // all issued before the first use, the updates are applied in entry order -- the sums are the same sums in the same
   // order.  One entry per trip was bound by exactly that latency: 400 entries x 2 us per wave, 2.8 ms per backward at
   // N = 40 000, M = 1000, L = 10, K = 10.
-  // A point's record (3K + 2 values: w, v, kx, gm, gcov) arrives as ONE load per entry, a value per lane, and the values an
+  // A point's record (3K + 2 values: w, v, cz, gm, gcov) arrives as ONE load per entry, a value per lane, and the values an
   // update needs are broadcast from the lanes that hold them (w[q] is already in lane q).  Loaded value by value -- seven
   // mostly wave-uniform loads per entry -- the kernel was bound by the rate at which a CU issues vector memory
   // instructions, not by where the records lie: laying them out along a Morton curve changed nothing until this did.
@@ -652,9 +707,8 @@ __global__ __launch_bounds__(64) void vnngp_gather_kernel(VnnBwdArgs<T> b) {
       }
       if (lane == 0) gmu += gm * wp;
       if (KG && lane < a.d) {
-        const double kxp = pick(r0, r1, 2 * K + p);
-        const double gk = (vp - gcov * wp) * kxp;
-        dz += gk * (q_cur.xd[u] - zl) * il2;      // dk/dz = k (x - z) / l^2
+        const double czp = pick(r0, r1, 2 * K + p);
+        dz += (vp - gcov * wp) * czp * (q_cur.xd[u] - zl);     // dk/dz = cz (x - z), cz by kernel kind from the point kernel
       }
       // (two entries of one trip can name the same column through different points: the LDS updates of entry u are
       // complete before entry u + 1 reads the row -- one wave, program order)
@@ -959,10 +1013,20 @@ static int vnngp_t(const gpz_svgp_problem* p, int K, const int64_t* idx_in, void
   if (int rc = vnn_prepare<T>(p, pl, idx_in, a, s)) return rc;
   {
     const dim3 grid((unsigned)((pl.L * pl.N + 255) / 256));
-    if (K <= 8) hipLaunchKernelGGL((vnngp_point_reg_kernel<T, 8>), grid, dim3(256), 0, s, a);
-    else if (K <= 12) hipLaunchKernelGGL((vnngp_point_reg_kernel<T, 12>), grid, dim3(256), 0, s, a);
-    else if (K <= 16) hipLaunchKernelGGL((vnngp_point_reg_kernel<T, 16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((vnngp_point_kernel<T>), grid, dim3(256), 0, s, a);
+#define GPZ_VNN_FWD(KIND)                                                                                            \
+  do {                                                                                                               \
+    if (K <= 8) hipLaunchKernelGGL((vnngp_point_reg_kernel<T, 8, KIND>), grid, dim3(256), 0, s, a);                  \
+    else if (K <= 12) hipLaunchKernelGGL((vnngp_point_reg_kernel<T, 12, KIND>), grid, dim3(256), 0, s, a);           \
+    else if (K <= 16) hipLaunchKernelGGL((vnngp_point_reg_kernel<T, 16, KIND>), grid, dim3(256), 0, s, a);           \
+    else hipLaunchKernelGGL((vnngp_point_kernel<T, KIND>), grid, dim3(256), 0, s, a);                                \
+  } while (0)
+    switch (p->k.kind) {             // vnn_check admitted exactly these
+      case GPZ_KERNEL_MATERN32: GPZ_VNN_FWD(GPZ_KERNEL_MATERN32); break;
+      case GPZ_KERNEL_MATERN12: GPZ_VNN_FWD(GPZ_KERNEL_MATERN12); break;
+      case GPZ_KERNEL_MATERN52: GPZ_VNN_FWD(GPZ_KERNEL_MATERN52); break;
+      default: GPZ_VNN_FWD(GPZ_KERNEL_RBF); break;
+    }
+#undef GPZ_VNN_FWD
   }
   GPZ_LAUNCH_OK();
   if (p->kl)
@@ -1163,11 +1227,20 @@ static int vnngp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, 
   b.gmu = pl.gmu; b.gS = pl.gS; b.gK = kgrads ? pl.gK : nullptr; b.kacc = kgrads ? pl.kacc : nullptr; b.rec = reinterpret_cast<T*>(pl.rec);
   {
     const dim3 grid((unsigned)((L * pl.N + 255) / 256));
-    const int K = b.f.K;
-    if (K <= 8) hipLaunchKernelGGL((vnngp_point_bwd_reg_kernel<T, 8>), grid, dim3(256), 0, s, b);
-    else if (K <= 12) hipLaunchKernelGGL((vnngp_point_bwd_reg_kernel<T, 12>), grid, dim3(256), 0, s, b);
-    else if (K <= 16) hipLaunchKernelGGL((vnngp_point_bwd_reg_kernel<T, 16>), grid, dim3(256), 0, s, b);
-    else hipLaunchKernelGGL((vnngp_point_bwd_kernel<T>), grid, dim3(256), 0, s, b);
+#define GPZ_VNN_BWD(KIND)                                                                                            \
+  do {                                                                                                               \
+    if (K <= 8) hipLaunchKernelGGL((vnngp_point_bwd_reg_kernel<T, 8, KIND>), grid, dim3(256), 0, s, b);              \
+    else if (K <= 12) hipLaunchKernelGGL((vnngp_point_bwd_reg_kernel<T, 12, KIND>), grid, dim3(256), 0, s, b);       \
+    else if (K <= 16) hipLaunchKernelGGL((vnngp_point_bwd_reg_kernel<T, 16, KIND>), grid, dim3(256), 0, s, b);       \
+    else hipLaunchKernelGGL((vnngp_point_bwd_kernel<T, KIND>), grid, dim3(256), 0, s, b);                            \
+  } while (0)
+    switch (p->k.kind) {
+      case GPZ_KERNEL_MATERN32: GPZ_VNN_BWD(GPZ_KERNEL_MATERN32); break;
+      case GPZ_KERNEL_MATERN12: GPZ_VNN_BWD(GPZ_KERNEL_MATERN12); break;
+      case GPZ_KERNEL_MATERN52: GPZ_VNN_BWD(GPZ_KERNEL_MATERN52); break;
+      default: GPZ_VNN_BWD(GPZ_KERNEL_RBF); break;
+    }
+#undef GPZ_VNN_BWD
   }
   GPZ_LAUNCH_OK();
   {
@@ -1282,7 +1355,7 @@ static int vnngp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, 
   ka.Kbar = pl.PS; ka.ld = Mp; ka.stride = mm; ka.Z = p->Z; ka.X = p->Z; ka.gZ = nullptr; ka.gX = nullptr;
   ka.sigma = p->k.sigma; ka.ell = p->k.lengthscale; ka.ga = nullptr; ka.gr2 = nullptr;
   ka.gpow = 0.0; ka.scalar_scale = 0.5; ka.M = M; ka.ncols = M; ka.Mp = Mp; ka.d = p->d; ka.G = 0; ka.acc = pl.kacc;
-  if (int rc = kgrad_launch(p->dtype, GPZ_KERNEL_RBF, ka, L32, s)) return rc;
+  if (int rc = kgrad_launch(p->dtype, p->k.kind, ka, L32, s)) return rc;
   const unsigned fx = (unsigned)std::max<int64_t>((M + 255) / 256, L);
   hipLaunchKernelGGL(vnn_kgrad_finish_kernel, dim3(fx, 2), dim3(256), 0, s, pl.kacc, L32, Mp, M, p->d, g->grad_Z,
                      g->grad_theta);
@@ -1306,7 +1379,11 @@ extern "C" int gpz_knn(const void* X, int64_t N, const void* Z, int64_t M, int32
 static int vnn_check(const gpz_svgp_problem* p, int K) {
   GPZ_REQUIRE(p && p->X && p->Z && p->mu && p->Lu_raw && p->info, "gpz_vnngp: null pointer");
   GPZ_REQUIRE(p->dtype == GPZ_F32 || p->dtype == GPZ_F64, "gpz_vnngp: bad dtype");
-  GPZ_REQUIRE(p->k.kind == GPZ_KERNEL_RBF, "gpz_vnngp: only the RBF family supports return_distance (kernels.py:118-126)");
+  GPZ_REQUIRE(p->k.kind != GPZ_KERNEL_MGGP_RBF,
+              "gpz_vnngp: kernel kind %d (multi-group RBF) is not supported: the reference has no multi-group VNNGP", p->k.kind);
+  GPZ_REQUIRE(p->k.kind == GPZ_KERNEL_RBF || p->k.kind == GPZ_KERNEL_MATERN32 || p->k.kind == GPZ_KERNEL_MATERN12 ||
+                  p->k.kind == GPZ_KERNEL_MATERN52,
+              "gpz_vnngp: kernel kind %d unsupported (RBF 0, Matern-3/2 1, Matern-1/2 4, Matern-5/2 5)", p->k.kind);
   GPZ_REQUIRE(p->k.n_latent >= 1 && p->N >= 1 && p->M >= 1 && p->d >= 1 && p->d <= 4, "gpz_vnngp: bad extents");
   GPZ_REQUIRE(K >= 1 && K <= KNN_MAX && K <= p->M, "gpz_vnngp: K=%d unsupported (1..min(%d, M))", K, KNN_MAX);
   return 0;

@@ -312,9 +312,15 @@ class _VNNMoments(torch.autograd.Function):
 
 
 class VNNGP(nn.Module):
-    """Nearest-neighbour variational GP; reference gp.py:7-122 (RBF-family kernels: the ones with
-    ``return_distance``).  The reference's scalar-``RBF`` path raises (gp.py:83 repeats the neighbour
-    table N times instead of L); here a scalar kernel returns ``(N,)`` moments.  Differentiable w.r.t.
+    """Nearest-neighbour variational GP; reference gp.py:7-122.  Kernels: the RBF family (``RBF``, ``NSF_RBF``,
+    ``batched_RBF``) and the Matern family (``batched_Matern12`` / ``32`` / ``52``) -- ``return_distance`` is all the
+    reference asks of a kernel here, and the neighbour table is the library's own (``ops.knn``) for every kind.  The
+    multi-group kernels are refused (the reference has no multi-group VNNGP), and so is a kernel whose ``covariance`` is
+    user-defined (``NotImplementedError``: it is not replaced by the closed form).  The reference's scalar-``RBF`` path
+    raises (gp.py:83 repeats the neighbour table N times instead of L); here a scalar-parameter kernel of either
+    family returns ``(N,)`` moments.  A datum that coincides with one of its inducing points contributes no gradient to
+    that point through k(x, z) (the r -> 0 limit; for Matern-1/2, whose derivative has a kink there, the library's
+    convention -- the reference's autograd returns NaN).  Differentiable w.r.t.
     ``mu``, ``Lu``, ``Z``, ``sigma`` and ``lengthscale``; ``kl_divergence(qU, pU)`` on the returned pair
     resolves to the KL the fused pass evaluated (see ``_kl_fused``)."""
     _clamp_min = 5e-2

@@ -452,9 +452,10 @@ def factor_key(spec: "KernelSpec", Z, jitter, dtype) -> tuple:
     return (spec.kind, spec.L, float(spec.group_pow), float(jitter), str(dtype), tuple(Z.shape), G)
 
 
-def _problem(spec: KernelSpec, X, Z, mu, Lu_raw, jitter, whitened, gX, gZ, clamp_min, keep: list):
+def _problem(spec: KernelSpec, X, Z, mu, Lu_raw, jitter, whitened, gX, gZ, clamp_min, keep: list, groups: bool = True):
     """Fill a gpz_svgp_problem from tensors (inputs only); returns (problem, (L, M, N, dtype, device, deps)) where
-    ``deps`` are the prepared tensors chol(Kzz) depends on (what FactorCache fingerprints)."""
+    ``deps`` are the prepared tensors chol(Kzz) depends on (what FactorCache fingerprints).  ``groups=False``: the entry
+    takes no group ids (gpz_vnngp, which refuses a multi-group kind itself and says so)."""
     dt = X.dtype
     if X.dim() != 2 or Z.dim() != 2 or X.shape[1] != Z.shape[1]:
         raise ValueError(f"expected X (N,d) and Z (M,d) with equal d, got {tuple(X.shape)} and {tuple(Z.shape)}")
@@ -475,7 +476,7 @@ def _problem(spec: KernelSpec, X, Z, mu, Lu_raw, jitter, whitened, gX, gZ, clamp
     p.dtype, p.whitened, p.d = _dt(X), int(whitened), dim
     p.N, p.M = N, M
     p.X, p.Z, p.mu, p.Lu_raw = X.data_ptr(), Z.data_ptr(), mu.data_ptr(), Lu_raw.data_ptr()
-    if spec.kind == _lib.KERNEL_MGGP_RBF:
+    if groups and spec.kind == _lib.KERNEL_MGGP_RBF:
         if gX is None or gZ is None:
             raise ValueError("multi-group kernels need groupsX and groupsZ")
         gX, gZ = _group_ids(gX, N, dev, "groupsX"), _group_ids(gZ, M, dev, "groupsZ")
@@ -893,12 +894,13 @@ def nmf_kl_mu(X, W0, H0, max_iter: int = 200, tol: float = 1e-4):
 @_on_device
 def vnngp_forward(spec: KernelSpec, X, Z, mu, Lu_raw, jitter: float, K: int, clamp_min: float = 5e-2,
                   check_info: bool = True, idx=None, keep_state: bool = False) -> dict:
-    """VNNGP forward (gpz_vnngp_forward): mean, scale (L,N), Lu, chol (L,M,M), idx (N,K).  ``keep_state``: also
+    """VNNGP forward (gpz_vnngp_forward; RBF and Matern-1/2, -3/2, -5/2 specs): mean, scale (L,N), Lu, chol (L,M,M), idx
+    (N,K).  ``keep_state``: also
     "state", the buffer ``vnngp_backward(state=...)`` of the same call takes the factor, S and the KL operands from."""
     _need_cuda(X, Z, mu, Lu_raw)
     lib = _lib.load()
     keep: list = []
-    p, (L, M, N, dt, dev, deps) = _problem(spec, X, Z, mu, Lu_raw, jitter, False, None, None, clamp_min, keep)
+    p, (L, M, N, dt, dev, deps) = _problem(spec, X, Z, mu, Lu_raw, jitter, False, None, None, clamp_min, keep, groups=False)
     out = {"mean": torch.empty((L, N), dtype=dt, device=dev), "scale": torch.empty((L, N), dtype=dt, device=dev),
            "Lu": torch.empty((L, M, M), dtype=dt, device=dev), "chol": torch.empty((L, M, M), dtype=dt, device=dev)}
     info = torch.empty(L, dtype=torch.int32, device=dev)
@@ -935,7 +937,7 @@ def vnngp_backward(spec: KernelSpec, X, Z, mu, Lu_raw, jitter: float, K: int, id
     _need_cuda(X, Z, mu, Lu_raw, g_mean, g_scale, idx)
     lib = _lib.load()
     keep: list = []
-    p, (L, M, N, dt, dev, deps) = _problem(spec, X, Z, mu, Lu_raw, jitter, False, None, None, clamp_min, keep)
+    p, (L, M, N, dt, dev, deps) = _problem(spec, X, Z, mu, Lu_raw, jitter, False, None, None, clamp_min, keep, groups=False)
     info = torch.empty(L, dtype=torch.int32, device=dev)
     p.info = info.data_ptr()
     g = _lib.SvgpGrads()

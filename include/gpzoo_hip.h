@@ -23,7 +23,9 @@
  * gpz_nmf_kl_update, gpz_nmf_kl_divergence and gpz_nmf_kl_workspace_bytes -- the KL multiplicative-update NMF behind
  * regularized_nmf (utilities.py:253-299, sklearn's NMF(solver='mu', beta_loss='kullback-leibler'));
  * GPZ_KERNEL_MATERN12 and GPZ_KERNEL_MATERN52 -- two more values of gpz_kernel_desc.kind, accepted wherever
- * GPZ_KERNEL_MATERN32 is (gpz_kfill, gpz_kgrad, gpz_svgp_forward / _backward and the Poisson entries; not gpz_vnngp);
+ * GPZ_KERNEL_MATERN32 is (gpz_kfill, gpz_kgrad, gpz_svgp_forward / _backward and the Poisson entries);
+ * gpz_vnngp_forward / _backward (and their workspace queries) accept GPZ_KERNEL_MATERN32, _MATERN12 and _MATERN52 next to
+ * GPZ_KERNEL_RBF -- the set of accepted kind values grew, nothing else about the entries changed;
  * gpz_knn_mean and gpz_knn_mean_workspace_bytes -- the exact K-nearest mean of the factors at the inducing points behind
  * smooth_spatial_factors (utilities.py:50-68, sklearn's KNeighborsRegressor.predict).
  */
@@ -278,8 +280,10 @@ int gpz_poisson_nsf(const float* mean, const float* scale, const float* eps, con
 int gpz_knn(const void* X, int64_t N, const void* Z, int64_t M, int32_t d, int32_t K, int32_t dtype,
             int64_t* idx, void* stream);
 
-/* VNNGP.forward (gp.py:21-122), RBF family only (the kernels with return_distance).  Uses the
- * problem's X, Z, kernel, mu, Lu_raw, jitter, var_clamp_min (the reference clamps at 5e-2) and
+/* VNNGP.forward (gp.py:21-122).  Accepted kernel kinds: GPZ_KERNEL_RBF, GPZ_KERNEL_MATERN32, GPZ_KERNEL_MATERN12 and
+ * GPZ_KERNEL_MATERN52 (the reference asks return_distance of its kernel and nothing else: its RBF family has it, a
+ * Matern kernel gets it in one line); GPZ_KERNEL_MGGP_RBF is refused (non-zero return, gpz_last_error names the kind)
+ * -- the reference has no multi-group VNNGP.  Uses the problem's X, Z, kernel, mu, Lu_raw, jitter, var_clamp_min (the reference clamps at 5e-2) and
  * writes mean, scale (L,N), optionally Lu and chol, and info.  idx: (N,K) neighbour lists from
  * gpz_knn, or NULL to compute them here. */
 size_t gpz_vnngp_workspace_bytes(const gpz_svgp_problem* p, int32_t K);
@@ -296,6 +300,8 @@ int gpz_vnngp_forward(const gpz_svgp_problem* p, int32_t K, const int64_t* idx, 
  * (utilities.py:485 over gp.py:21-122): given dLoss/dmean, dLoss/dscale (and, for the kernel
  * hyper-parameters, dLoss/dchol from KL(qU || pU)) writes grad_mu, grad_Lu_raw and, when
  * grad_theta / grad_Z are non-NULL, the gradients w.r.t. (sigma, lengthscale) per latent and Z.
+ * Kernel kinds as gpz_vnngp_forward; dk/dz of a datum that coincides with its inducing point is 0 (the r -> 0 limit for
+ * Matern-3/2 and -5/2, the convention of gpz_kgrad at the kink of Matern-1/2).
  * The neighbour table is a constant of the graph (argsort has no gradient).  `scale` of
  * gpz_svgp_grads is unused (the variance is recomputed); `g_kl` folds the gradient of the forward's
  * per-latent KL(qU || pU) (problem field `kl`) in, as in gpz_svgp_backward.  The K-sparse terms (the sums over the
