@@ -574,6 +574,13 @@ extern "C" int gpz_poisson_nsf(const float* mean, const float* scale, const floa
                                size_t ws_bytes, void* stream) {
   GPZ_REQUIRE(mean && scale && eps && W && V && y && loglik && dmean && dscale && dW && dV && ws,
               "gpz_poisson_nsf: null pointer");
+  // both passes read y and write their slabs 16 bytes at a time whenever N % 4 == 0, from the base pointers on
+  {
+    const void* arrays[] = {mean, scale, eps, W, V, y, loglik, dmean, dscale, dW, dV, ws};
+    uintptr_t low = 0;
+    for (const void* p : arrays) low |= reinterpret_cast<uintptr_t>(p);
+    GPZ_REQUIRE((low & 15) == 0, "gpz_poisson_nsf: every array argument and the workspace must be 16-byte aligned");
+  }
   GPZ_REQUIRE(N >= 1 && D >= 1, "gpz_poisson_nsf: bad extents");
   GPZ_REQUIRE(Lt >= 1 && Lt <= PMAXL, "gpz_poisson_nsf: %d factors unsupported (1..%d)", Lt, PMAXL);
   GPZ_REQUIRE(E >= 1 && E <= PMAXE, "gpz_poisson_nsf: %d samples per call unsupported (1..%d)", E, PMAXE);

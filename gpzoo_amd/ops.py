@@ -994,6 +994,9 @@ def poisson_nsf(mean, scale, eps, W_pos, V_pos, y, with_lgamma: bool = True):
     mean, scale = mean.detach().to(f32).contiguous(), scale.detach().to(f32).contiguous()
     eps, y = eps.detach().to(f32).contiguous(), y.detach().to(f32).contiguous()
     W_pos, V_pos = W_pos.detach().to(f32).contiguous(), V_pos.detach().to(f32).contiguous()
+    # the entry wants 16-byte aligned arrays (include/gpzoo_hip.h); a contiguous view keeps its storage offset
+    mean, scale, eps, W_pos, V_pos, y = (t if t.data_ptr() % 16 == 0 else t.clone()
+                                         for t in (mean, scale, eps, W_pos, V_pos, y))
     Lt, N = mean.shape
     E, D = eps.shape[0], y.shape[0]
     dev = mean.device

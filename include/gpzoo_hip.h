@@ -268,7 +268,11 @@ int gpz_svgp_backward(const gpz_svgp_problem* p, const gpz_svgp_grads* g, int64_
  * [1] = sum_dn lgamma(y+1) (0 unless with_lgamma; Poisson.log_prob = [0] - [1]); and
  * d loglik[0] / d{mean, scale, W, V}.  Lt <= 64 factors; E <= 32 samples per call (more samples: one call per group
  * of 32, as gpzoo_amd/ops.py does; y is read once per pass whatever E is).  The three dense products (rate, dW,
- * d exp F) run on MFMA. */
+ * d exp F) run on MFMA.
+ * Alignment: every array argument (the six inputs, the five outputs) and ws must be 16-byte aligned -- rows of y and of
+ * the partial-sum slabs are read and written 16 bytes at a time from the base pointers on whenever N % 4 == 0.  A
+ * misaligned pointer is an argument error on the host, before any launch (hipMalloc and torch allocations are
+ * aligned; a view at an element offset need not be: gpzoo_amd/ops.py copies such inputs). */
 size_t gpz_poisson_nsf_workspace_bytes(int64_t N, int64_t D, int32_t Lt, int32_t E);
 int gpz_poisson_nsf(const float* mean, const float* scale, const float* eps, const float* W,
                     const float* V, const float* y, int64_t N, int64_t D, int32_t Lt, int32_t E,
