@@ -13,20 +13,10 @@
 // (sqrt at 0), the true derivative is 0.  Matern-5/2 likewise:
 // dk/dz = -sigma^2 (5 / (3 l^2)) (1 + v) exp(-v) (z - x), v = sqrt5 r / l.  Matern-1/2 has a kink at r = 0:
 // dk/dz = -(k / l) (z - x) / r elsewhere, and 0 at coincident points (the unit vector is formed under a d2 > 0 guard).
-#include "common.h"
+#include "kgrad.h"
+#include "mmops.h"
 
 namespace gpz {
-
-struct KgradArgs {
-  const void* Kbar; int64_t ld, stride;
-  const void* Z; const void* X;
-  const int64_t* gZ; const int64_t* gX;
-  const void* sigma; const void* ell; const void* ga; const void* gr2;
-  double gpow, scalar_scale;
-  int64_t M, ncols, Mp;
-  int d, G;
-  double* acc;  // (L, Mp, 8): dz0..dz3, dsigma, dlengthscale, da_eff, unused
-};
 
 __device__ __forceinline__ float kg_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
 __device__ __forceinline__ double kg_exp(double x) { return exp(x); }
@@ -146,37 +136,6 @@ int kgrad_launch(int dtype, int kind, const KgradArgs& a, int L, hipStream_t s) 
 }  // namespace gpz
 
 // ---- public entry: backward of gpz_kfill ------------------------------------------------------
-namespace gpz {
-// grad_A[m][k] = sum_l acc[l][m][k];  grad_theta[l][0..2] = sum_m acc[l][m][4..6]
-__global__ __launch_bounds__(256) void kgrad_public_finish_kernel(const double* __restrict__ acc, int L, int64_t M, int d,
-                                                                  double* __restrict__ grad_A,
-                                                                  double* __restrict__ grad_theta) {
-  __shared__ double sh[4];
-  if (blockIdx.y == 0) {
-    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (m < M && grad_A)
-      for (int k = 0; k < 4; ++k) {
-        double t = 0.0;
-        if (k < d)
-          for (int l = 0; l < L; ++l) t += acc[((int64_t)l * M + m) * 8 + k];
-        grad_A[m * 4 + k] = t;
-      }
-  } else if ((int)blockIdx.x < L && grad_theta) {
-    const int l = blockIdx.x;
-    for (int q = 0; q < 3; ++q) {
-      double v = 0.0;
-      for (int64_t m = threadIdx.x; m < M; m += 256) v += acc[((int64_t)l * M + m) * 8 + 4 + q];
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-      __syncthreads();
-      if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-      __syncthreads();
-      if (threadIdx.x == 0) grad_theta[l * 4 + q] = sh[0] + sh[1] + sh[2] + sh[3];
-    }
-    if (threadIdx.x == 0) grad_theta[l * 4 + 3] = 0.0;
-  }
-}
-}  // namespace gpz
-
 extern "C" size_t gpz_kgrad_workspace_bytes(int64_t nA, int32_t n_latent) {
   if (nA < 1 || n_latent < 1) return 0;
   gpz::Carver c(nullptr);
@@ -207,8 +166,6 @@ extern "C" int gpz_kgrad(const gpz_kernel_desc* k, const void* A, int64_t nA, co
   a.sigma = k->sigma; a.ell = k->lengthscale; a.ga = k->group_a; a.gr2 = k->group_r2;
   a.gpow = k->group_pow; a.scalar_scale = 1.0; a.M = nA; a.ncols = nB; a.Mp = nA; a.d = d; a.G = k->n_groups; a.acc = acc;
   if (int rc = kgrad_launch(k->dtype, k->kind, a, L, s)) return rc;
-  const unsigned fx = (unsigned)((nA + 255) / 256 > L ? (nA + 255) / 256 : L);
-  hipLaunchKernelGGL(kgrad_public_finish_kernel, dim3(fx, 2), dim3(256), 0, s, acc, L, nA, d, grad_A, grad_theta);
-  GPZ_LAUNCH_OK();
-  return 0;
+  // grad_A[m][k] = sum_l acc[l][m][k];  grad_theta[l][0..2] = sum_m acc[l][m][4..6]
+  return kgrad_finish(acc, L, nA, nA, d, nullptr, grad_A, grad_theta, s);
 }

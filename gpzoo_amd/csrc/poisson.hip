@@ -18,6 +18,7 @@
 //   gene_mfma_kernel  pass B: the transposed tiles (spots as rows) -> dW = G expF^T partial slabs
 //   finish_kernel     sums the slabs into dmean, dscale, dV, dW and the scalar
 #include "common.h"
+#include "mmops.h"
 
 namespace gpz {
 
@@ -44,18 +45,6 @@ __global__ void expf_kernel(PoissonArgs a) {
   if (i >= per * a.E) return;
   const int64_t ln = i % per;
   a.expF[i] = __expf(a.mean[ln] + a.scale[ln] * a.eps[i]);
-}
-
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  return t;
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -258,7 +247,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
     if (q == 0 && nok[c]) a.dV_slab[((int64_t)s * nw + e * GS + gs) * a.N + n0 + 4 * r + c] = v;
   }
-  const double t = block_sum_d(ll * (double)inv_e, sh);
+  const double t = block_sum(ll * (double)inv_e, sh);
   if (threadIdx.x == 0) a.ll_slab[(int64_t)s * gridDim.x + blockIdx.x] = t;
 }
 
@@ -289,7 +278,7 @@ __global__ __launch_bounds__(256) void lgamma_sum_kernel(PoissonArgs a) {
   }
   for (int64_t i = 4 * tot4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < tot; i += (int64_t)a.nlg * 256) part += term(a.y[i]);
   lg += (double)part;
-  const double tg = block_sum_d(lg, sh);
+  const double tg = block_sum(lg, sh);
   if (threadIdx.x == 0) a.lg_slab[blockIdx.x] = tg;
 }
 
@@ -493,8 +482,8 @@ __global__ __launch_bounds__(256) void poisson_finish_kernel(PoissonArgs a, int 
     double v = 0.0, vg = 0.0;
     for (int j = threadIdx.x; j < a.S * nblk_spot; j += 256) v += a.ll_slab[j];
     for (int j = threadIdx.x; j < a.nlg; j += 256) vg += a.lg_slab[j];
-    const double t = block_sum_d(v, sh);
-    const double tg = block_sum_d(vg, sh);
+    const double t = block_sum(v, sh);
+    const double tg = block_sum(vg, sh);
     if (threadIdx.x == 0) { a.loglik[0] = t; a.loglik[1] = tg; }
   }
 }

@@ -15,29 +15,21 @@
 // colsum(Wt^2) and diag(W S W^T) = colsum(((Linv Lu)^T Wt)^2).
 // N is processed in chunks so Kzx / Wt only ever exist one chunk at a time; P is
 // never stored.  All reductions are slab-based (no atomics): bitwise reproducible.
+// The small M x M steps around the factor -- the Lu constraint and its chain rule, Linv^T v, the fp64 square product,
+// the Cholesky backward and the Kzz gradient tail -- live in mmops.hip (shared with vnngp.hip and kgrad.hip).
 #include "common.h"
 #include "gemmw.h"
 #include "gemmp.h"
 #include "factor.h"
 #include "gemm.h"
+#include "kgrad.h"
+#include "mmops.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 namespace gpz {
-
-struct KgradArgs {
-  const void* Kbar; int64_t ld, stride;
-  const void* Z; const void* X;
-  const int64_t* gZ; const int64_t* gX;
-  const void* sigma; const void* ell; const void* ga; const void* gr2;
-  double gpow, scalar_scale;
-  int64_t M, ncols, Mp;
-  int d, G;
-  double* acc;
-};
-int kgrad_launch(int dtype, int kind, const KgradArgs& a, int L, hipStream_t s);
 
 constexpr int NB = 128;
 
@@ -56,64 +48,6 @@ static ProductSchedule product_schedule(bool stats_epilogue, int nt) {
   int w = (nt + strips * tpw - 1) / (strips * tpw);     // workgroups per row tile and strip
   if (w > 16) w = 16;
   return ProductSchedule{w * tpw, tpw};
-}
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  // fixed-shape tree: lanes -> waves -> block (deterministic)
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  return t;  // valid on thread 0
-}
-
-// Constrained scale_tril of q(U) from the raw parameter (gp.py:220/278: strict lower
-// triangle kept, diagonal exponentiated), emitted in up to three forms:
-//   LuT   (L,Mp,Mp) TG  transposed (upper triangular), zero padded      [whitened: the stage-2 operand]
-//   LuD   (L,Mp,Mp) f64 as is (lower triangular), zero padded           [un-whitened: input to Linv * Lu]
-//   LuOut (L,M,M)   TIO for MultivariateNormal(scale_tril=...)
-// and per-block partial sums of ||Lu||_F^2 and of the raw diagonal (= log diag Lu).
-template <typename T>
-__global__ __launch_bounds__(256) void lu_prepare_kernel(const T* __restrict__ raw, int64_t M, int64_t Mp,
-                                                        T* __restrict__ LuT, double* __restrict__ LuD,
-                                                        T* __restrict__ LuOut, double* __restrict__ part,
-                                                        T* __restrict__ LuN = nullptr) {
-  __shared__ double tile[32][33];
-  __shared__ double sh[8];
-  const int l = blockIdx.z;
-  const int64_t i0 = (int64_t)blockIdx.y * 32, j0 = (int64_t)blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  double fro = 0.0, ld = 0.0;
-  for (int rr = ty; rr < 32; rr += 8) {
-    const int64_t i = i0 + rr, j = j0 + tx;
-    double v = 0.0;
-    if (i < M && j < M && j <= i) {
-      const double x = (double)raw[(int64_t)l * M * M + i * M + j];
-      if (i == j) { v = exp(x); ld += x; } else v = x;
-      fro += v * v;
-    }
-    tile[rr][tx] = v;
-    if (LuOut && i < M && j < M) LuOut[(int64_t)l * M * M + i * M + j] = (T)v;
-    if (LuD && i < Mp && j < Mp) LuD[(int64_t)l * Mp * Mp + i * Mp + j] = v;
-    if (LuN && i < Mp && j < Mp) LuN[(int64_t)l * Mp * Mp + i * Mp + j] = (T)v;   // padded, lower, not transposed
-  }
-  __syncthreads();
-  if (LuT)
-    for (int rr = ty; rr < 32; rr += 8) {
-      const int64_t jt = j0 + rr, it = i0 + tx;  // LuT[j][i] = Lu[i][j]
-      if (jt < Mp && it < Mp) LuT[(int64_t)l * Mp * Mp + jt * Mp + it] = (T)tile[tx][rr];
-    }
-  const double f = block_sum(fro, sh);
-  const double g = block_sum(ld, sh);
-  if (threadIdx.x == 0) {
-    const int64_t nb = (int64_t)gridDim.x * gridDim.y, b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    part[((int64_t)l * 2 + 0) * nb + b] = f;
-    part[((int64_t)l * 2 + 1) * nb + b] = g;
-  }
 }
 
 // dst (L,Mp,Mp) T = transpose(src (L,Mp,Mp) f64), plus per-block partial ||src||_F^2.
@@ -145,28 +79,6 @@ template <typename T>
 __global__ void cast_kernel(const double* __restrict__ src, T* __restrict__ dst, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     dst[i] = (T)src[i];
-}
-
-// Cholesky factor out: (L,Mp,Mp) f64 -> (L,M,M) T with zeros above the diagonal; and
-// sum of log diag per latent (one block per latent along y == 0 row).
-template <typename T>
-__global__ __launch_bounds__(256) void chol_out_kernel(const double* __restrict__ Lc, int64_t Mp, int64_t M,
-                                                      T* __restrict__ out, double* __restrict__ logdiag) {
-  __shared__ double sh[8];
-  const int l = blockIdx.y;
-  const double* src = Lc + (int64_t)l * Mp * Mp;
-  if (out) {
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < M * M; e += (int64_t)gridDim.x * 256) {
-      const int64_t i = e / M, j = e - i * M;
-      out[(int64_t)l * M * M + e] = (j <= i) ? (T)src[i * Mp + j] : (T)0;
-    }
-  }
-  if (blockIdx.x == 0) {
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < M; i += 256) s += log(src[i * (Mp + 1)]);
-    const double t = block_sum(s, sh);
-    if (threadIdx.x == 0) logdiag[l] = t;
-  }
 }
 
 // muE: whitened -> mu itself; un-whitened -> Linv * mu (fp64 GEMV, one block per 64 rows).
@@ -485,42 +397,33 @@ static int prepare_t(const gpz_svgp_problem* p, const Plan& pl, Buffers<T>& b, h
     if (int rc = factor_invert_padded(b.Kzz, Mp, L, M, b.Dinv, b.Linv, b.Tmp, b.fsync, p->info, s,
                                       sizeof(T) == 4 ? reinterpret_cast<float*>(b.LinvG) : nullptr, &wrote32, nsync > 0))
       return rc;
-    hipLaunchKernelGGL((chol_out_kernel<T>), dim3(p->chol ? 64 : 1, L32), dim3(256), 0, s, b.Kzz, Mp, M,
-                       static_cast<T*>(p->chol), b.chol_logdiag);
-    GPZ_LAUNCH_OK();
+    if (int rc = chol_out(b.Kzz, Mp, M, L32, static_cast<T*>(p->chol), b.chol_logdiag, s)) return rc;
     if (sizeof(T) == 4 && !wrote32) {
       hipLaunchKernelGGL((cast_kernel<T>), dim3(2048), dim3(256), 0, s, b.Linv, b.LinvG, L * mm);
       GPZ_LAUNCH_OK();
     }
   } else {
-    if (p->chol) {
-      hipLaunchKernelGGL((chol_out_kernel<T>), dim3(64, L32), dim3(256), 0, s, b.Kzz, Mp, M, static_cast<T*>(p->chol),
-                         b.chol_logdiag);
-      GPZ_LAUNCH_OK();
-    }
+    if (p->chol)
+      if (int rc = chol_out(b.Kzz, Mp, M, L32, static_cast<T*>(p->chol), b.chol_logdiag, s)) return rc;
   }
 
   // 2. q(U) parameters in the form the two products need
   const dim3 g32((unsigned)(Mp / 32), (unsigned)(Mp / 32), L32);
   if (qu_cached) return 0;
   if (wh) {
-    hipLaunchKernelGGL((lu_prepare_kernel<T>), g32, dim3(256), 0, s, static_cast<const T*>(p->Lu_raw), M, Mp, b.LuT,
-                       (double*)nullptr, static_cast<T*>(p->Lu), b.lu_part);
-    GPZ_LAUNCH_OK();
+    if (int rc = lu_forward(static_cast<const T*>(p->Lu_raw), M, Mp, L32, b.LuT, (double*)nullptr, static_cast<T*>(p->Lu),
+                            b.lu_part, (T*)nullptr, s))
+      return rc;
     hipLaunchKernelGGL((mu_prepare_kernel<T>), dim3((unsigned)pl.nmu, L32), dim3(256), 0, s,
                        static_cast<const T*>(p->mu), M, Mp, (const double*)nullptr, b.muE, b.mu_part);
     GPZ_LAUNCH_OK();
   } else {
-    hipLaunchKernelGGL((lu_prepare_kernel<T>), g32, dim3(256), 0, s, static_cast<const T*>(p->Lu_raw), M, Mp,
-                       (T*)nullptr, b.LuD, static_cast<T*>(p->Lu), b.lu_part);
-    GPZ_LAUNCH_OK();
-    GemmParams<double> g;  // LuW = Linv * Lu  (lower x lower -> lower)
-    g.A = b.Linv; g.lda = Mp; g.sA0 = mm;
-    g.B = b.LuD; g.ldb = Mp; g.sB0 = mm;
-    g.C = b.LuW; g.ldc = Mp; g.sC0 = mm;
-    g.nb0 = L32; g.mt = g.nt = (int)pl.nblk; g.K = (int)Mp; g.flags = GF_A_LOWER | GF_B_LOWER | GF_TILES_LOWER;
+    if (int rc = lu_forward(static_cast<const T*>(p->Lu_raw), M, Mp, L32, (T*)nullptr, b.LuD, static_cast<T*>(p->Lu),
+                            b.lu_part, (T*)nullptr, s))
+      return rc;
     GPZ_HIP_OK(hipMemsetAsync(b.LuW, 0, sizeof(double) * L * mm, s));
-    if (int rc = gemm_launch(g, EPI_STORE, s)) return rc;
+    // LuW = Linv * Lu  (lower x lower -> lower)
+    if (int rc = dgemm_mm(b.Linv, b.LuD, b.LuW, Mp, L32, GF_A_LOWER | GF_B_LOWER | GF_TILES_LOWER, 1.0, s)) return rc;
     hipLaunchKernelGGL((transpose_cast_kernel<T>), g32, dim3(256), 0, s, b.LuW, Mp, b.LuT, b.fro_part);
     GPZ_LAUNCH_OK();
     hipLaunchKernelGGL((mu_prepare_kernel<T>), dim3((unsigned)pl.nmu, L32), dim3(256), 0, s,
@@ -767,9 +670,9 @@ static int precomputed_t(const void* W, const void* sigma, const void* mu, const
   GPZ_REQUIRE(ws_bytes >= b.bytes, "gpz_wsvgp_precomputed: workspace too small");
   const int L32 = (int)L;
   const int64_t Mp = pl.Mp, mm = Mp * Mp;
-  hipLaunchKernelGGL((lu_prepare_kernel<T>), dim3((unsigned)(Mp / 32), (unsigned)(Mp / 32), L32), dim3(256), 0, s,
-                     static_cast<const T*>(Lu_raw), M, Mp, b.LuT, (double*)nullptr, static_cast<T*>(Lu), b.lu_part);
-  GPZ_LAUNCH_OK();
+  if (int rc = lu_forward(static_cast<const T*>(Lu_raw), M, Mp, L32, b.LuT, (double*)nullptr, static_cast<T*>(Lu), b.lu_part,
+                          (T*)nullptr, s))
+    return rc;
   for (int64_t ci = 0; ci < pl.nchunks; ++ci) {
     const int64_t n0 = ci * pl.nc;
     const int64_t nreal = (N - n0 < pl.nc) ? N - n0 : pl.nc;
@@ -910,21 +813,6 @@ __global__ __launch_bounds__(256) void sigma_direct_kernel(const T* __restrict__
   if (threadIdx.x == 0) acc[l] += (double)sigma[l] * t;
 }
 
-// dst = transpose(tril(src)) for (L,Mp,Mp) fp64 (src may hold garbage above the diagonal)
-__global__ __launch_bounds__(256) void tril_transpose_kernel(const double* __restrict__ src, int64_t Mp,
-                                                            double* __restrict__ dst) {
-  __shared__ double tile[32][33];
-  const int l = blockIdx.z;
-  const int64_t i0 = (int64_t)blockIdx.y * 32, j0 = (int64_t)blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int rr = ty; rr < 32; rr += 8) {
-    const int64_t i = i0 + rr, j = j0 + tx;
-    tile[rr][tx] = (j <= i) ? src[(int64_t)l * Mp * Mp + i * Mp + j] : 0.0;
-  }
-  __syncthreads();
-  for (int rr = ty; rr < 32; rr += 8) dst[(int64_t)l * Mp * Mp + (j0 + rr) * Mp + i0 + tx] = tile[tx][rr];
-}
-
 // Lbar = -tril(GL) (+ tril(upstream dLoss/dchol)) in fp64
 template <typename T, typename TG>
 __global__ void lbar_kernel(const TG* __restrict__ GL, int64_t Mp, int64_t M, const T* __restrict__ g_chol,
@@ -941,16 +829,6 @@ __global__ void lbar_kernel(const TG* __restrict__ GL, int64_t Mp, int64_t M, co
     if (g_kl && i == j && i < M) v += g_kl[l] / Lc[(int64_t)l * Mp * Mp + i * Mp + i];   // d(sum log diag L)/dL
   }
   Lbar[(int64_t)l * Mp * Mp + i * Mp + j] = v;
-}
-
-// dst = (double) tril(src)
-template <typename T>
-__global__ void tril_to_double_kernel(const T* __restrict__ src, int64_t Mp, double* __restrict__ dst) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= Mp) return;
-  const int64_t o = (int64_t)l * Mp * Mp + i * Mp + j;
-  dst[o] = (j <= i) ? (double)src[o] : 0.0;
 }
 
 // me[l][j] = (Linv mu)[j] in fp64, one wave per row (coalesced along the row), zero in the padding
@@ -978,57 +856,6 @@ __global__ __launch_bounds__(256) void rank1_update_kernel(double* __restrict__ 
   if (j >= M) return;
   const double mj = me[(int64_t)l * Mp + j];
   for (int64_t i = blockIdx.y; i < M; i += gridDim.y) R[(int64_t)l * Mp * Mp + i * Mp + j] += u[(int64_t)l * Mp + i] * mj;
-}
-
-// Phi: keep the lower triangle, halve the diagonal (Cholesky backward, Murray 2016)
-__global__ void phi_kernel(double* __restrict__ A, int64_t Mp) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= Mp) return;
-  double& v = A[(int64_t)l * Mp * Mp + i * Mp + j];
-  if (j > i) v = 0.0;
-  else if (j == i) v *= 0.5;
-}
-
-// dst = P + P^T, cast to T
-template <typename T>
-__global__ __launch_bounds__(256) void sym_cast_kernel(const double* __restrict__ P, int64_t Mp, T* __restrict__ dst) {
-  __shared__ double tile[32][33];
-  const int l = blockIdx.z;
-  const int64_t i0 = (int64_t)blockIdx.y * 32, j0 = (int64_t)blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int rr = ty; rr < 32; rr += 8) tile[rr][tx] = P[(int64_t)l * Mp * Mp + (j0 + rr) * Mp + i0 + tx];  // P[j][i]
-  __syncthreads();
-  for (int rr = ty; rr < 32; rr += 8) {
-    const int64_t i = i0 + rr, j = j0 + tx;
-    dst[(int64_t)l * Mp * Mp + i * Mp + j] = (T)(P[(int64_t)l * Mp * Mp + i * Mp + j] + tile[tx][rr]);
-  }
-}
-
-// grad_Z[m][k] = sum_l acc[l][m][k];  grad_theta[l][0..2] = sum_m acc[l][m][4..6] (+ direct sigma term)
-__global__ __launch_bounds__(256) void kgrad_finish_kernel(const double* __restrict__ acc, int L, int64_t Mp, int64_t M,
-                                                          int d, const double* __restrict__ sig_direct,
-                                                          double* __restrict__ grad_Z, double* __restrict__ grad_theta) {
-  __shared__ double sh[8];
-  if (blockIdx.y == 0) {            // Z rows
-    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (m < M && grad_Z)
-      for (int k = 0; k < 4; ++k) {
-        double t = 0.0;
-        if (k < d)
-          for (int l = 0; l < L; ++l) t += acc[((int64_t)l * Mp + m) * 8 + k];
-        grad_Z[m * 4 + k] = t;
-      }
-  } else if ((int)blockIdx.x < L && grad_theta) {   // one block per latent
-    const int l = blockIdx.x;
-    for (int q = 0; q < 3; ++q) {
-      double v = 0.0;
-      for (int64_t m = threadIdx.x; m < M; m += 256) v += acc[((int64_t)l * Mp + m) * 8 + 4 + q];
-      const double t = block_sum(v, sh);
-      if (threadIdx.x == 0) grad_theta[l * 4 + q] = t + (q == 0 ? sig_direct[l] : 0.0);
-    }
-    if (threadIdx.x == 0) grad_theta[l * 4 + 3] = 0.0;
-  }
 }
 
 // part[l][ci][m] = sum_c Wt[l][m][c] * g_mean[l][n0 + c]   (one wave per row)
@@ -1077,77 +904,12 @@ __global__ void mu_grad_kernel(const double* __restrict__ v, const double* __res
   out[(int64_t)l * M + a] = (T)t;
 }
 
-// out = Linv^T v with 32 columns x 8 row segments per block (a thread per column alone walks up to M rows serially:
-// 0.73 ms at M = 3000, L = 20)
-template <typename T>
-__global__ __launch_bounds__(256) void mu_grad_linv_kernel(const double* __restrict__ v, const double* __restrict__ Linv,
-                                                          int64_t Mp, int64_t M, T* __restrict__ out) {
-  __shared__ double sh[8][33];
-  const int l = blockIdx.y, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int64_t a = (int64_t)blockIdx.x * 32 + tx;
-  const double* Lb = Linv + (int64_t)l * Mp * Mp;
-  double t = 0.0;
-  if (a < M)
-    for (int64_t i = a + ty; i < M; i += 8) t = fma(Lb[i * Mp + a], v[(int64_t)l * Mp + i], t);
-  sh[ty][tx] = t;
-  __syncthreads();
-  if (ty == 0 && a < M) {
-    double r = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) r += sh[q][tx];
-    out[(int64_t)l * M + a] = (T)r;
-  }
-}
-
-// out[l][a] = sum_{i >= a} Linv[l][i][a] * v[l][i]  (Linv^T v) for a < M, zero in the padding; out (L, Mp)
-template <typename T>
-__global__ __launch_bounds__(256) void linvT_vec_kernel(const double* __restrict__ v, const double* __restrict__ Linv,
-                                                       int64_t Mp, int64_t M, T* __restrict__ out) {
-  __shared__ double sh[8][33];
-  const int l = blockIdx.y, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int64_t a = (int64_t)blockIdx.x * 32 + tx;
-  const double* Lb = Linv + (int64_t)l * Mp * Mp;
-  double t = 0.0;
-  if (a < M)
-    for (int64_t i = a + ty; i < M; i += 8) t = fma(Lb[i * Mp + a], v[(int64_t)l * Mp + i], t);
-  sh[ty][tx] = t;
-  __syncthreads();
-  if (ty == 0 && a < Mp) {
-    double r = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) r += sh[q][tx];
-    out[(int64_t)l * Mp + a] = (T)r;
-  }
-}
-
 // zero the strict upper triangle of (L,Mp,Mp)
 template <typename T>
 __global__ void tril_kernel(T* __restrict__ G, int64_t Mp) {
   const int l = blockIdx.z;
   const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j < Mp && j > i) G[(int64_t)l * Mp * Mp + i * Mp + j] = (T)0;
-}
-
-// chain rule of the constraint Lu = tril(raw, -1) + diag(exp(diag raw))
-template <typename T>
-__global__ void lu_grad_kernel(const T* __restrict__ G, int64_t Mp, int64_t M, const T* __restrict__ raw,
-                               T* __restrict__ out, const double* __restrict__ g_kl = nullptr, int whitened_kl = 0) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= M) return;
-  double g = (double)G[(int64_t)l * Mp * Mp + i * Mp + j];
-  const double gk = g_kl ? g_kl[l] : 0.0;
-  const double x = (double)raw[(int64_t)l * M * M + i * M + j];
-  T v = 0;
-  if (j < i) {
-    if (whitened_kl) g += gk * x;                 // whitened KL: d/dLu of |Lu|_F^2 / 2 (un-whitened: already in G)
-    v = (T)g;
-  } else if (j == i) {   // Lu_ii = exp(raw_ii); the KL's -log Lu_ii contributes -g_kl to the raw diagonal
-    const double e = exp(x);
-    if (whitened_kl) g += gk * e;
-    v = (T)(g * e - gk);
-  }
-  out[(int64_t)l * M * M + i * M + j] = v;
 }
 
 // KL(qU || pU) folded into the un-whitened gradients: dKL/dLuE = LuE (lower), dKL/dmuE = muE
@@ -1302,15 +1064,19 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
     d.nb0 = L32; d.mt = d.nt = (int)pl.nblk; d.K = (int)Mp; d.flags = flags;
     return gemm_launch(d, EPI_STORE, s);
   };
+  auto dgemm = [&](const double* A, const double* B, double* C, int flags) -> int {
+    return dgemm_mm(A, B, C, Mp, L32, flags, 1.0, s);
+  };
   if (full) {
     // Lu (lower, not transposed) in GEMM precision and Linv^T
     if (wh) {
-      hipLaunchKernelGGL((lu_prepare_kernel<T>), g32, dim3(256), 0, s, static_cast<const T*>(p->Lu_raw), M, Mp,
-                         (T*)nullptr, (double*)nullptr, (T*)nullptr, b.lu_part, w.LuN);
+      if (int rc = lu_forward(static_cast<const T*>(p->Lu_raw), M, Mp, L32, (T*)nullptr, (double*)nullptr, (T*)nullptr,
+                              b.lu_part, w.LuN, s))
+        return rc;
     } else {   // LuE = Linv Lu (lower), already formed in fp64 by the preparation step
       hipLaunchKernelGGL((cast_kernel<T>), dim3(2048), dim3(256), 0, s, b.LuW, w.LuN, L * mm);
+      GPZ_LAUNCH_OK();
     }
-    GPZ_LAUNCH_OK();
     hipLaunchKernelGGL((transpose_cast_kernel<T>), g32, dim3(256), 0, s, b.Linv, Mp, w.LinvT, (double*)w.D1);
     GPZ_LAUNCH_OK();
     // muE in fp64 (whitened: mu itself): the rank-1 terms of Kbar_x / Q and, un-whitened, of E below
@@ -1330,24 +1096,17 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
       // products run in the problem's precision (the classic form accumulates the same quantities in it).
       if (alg64) {
         // Sw - I (kept in D2 for Q) and A1 in fp64, then cast
-        GemmParams<double> d;
-        auto dg = [&](const double* A, const double* B, double* C, int flags) -> int {
-          d.A = A; d.lda = Mp; d.sA0 = mm; d.B = B; d.ldb = Mp; d.sB0 = mm; d.C = C; d.ldc = Mp; d.sC0 = mm;
-          d.nb0 = L32; d.mt = d.nt = (int)pl.nblk; d.K = (int)Mp; d.flags = flags;
-          return gemm_launch(d, EPI_STORE, s);
-        };
         const double* LuE64 = b.LuW;
         if (wh) {
           hipLaunchKernelGGL((widen_kernel<T>), dim3(2048), dim3(256), 0, s, (const T*)w.LuN, w.D3, L * mm, 0);
           GPZ_LAUNCH_OK();
           LuE64 = w.D3;
         }
-        if (int rc = dg(LuE64, LuE64, w.D2, GF_A_LOWER | GF_B_UPPER | GF_B_TRANS)) return rc;
+        if (int rc = dgemm(LuE64, LuE64, w.D2, GF_A_LOWER | GF_B_UPPER | GF_B_TRANS)) return rc;
         hipLaunchKernelGGL(minus_identity_kernel, dim3((unsigned)((Mp + 255) / 256), L32), dim3(256), 0, s, w.D2, Mp);
         GPZ_LAUNCH_OK();
-        hipLaunchKernelGGL(tril_transpose_kernel, g32, dim3(256), 0, s, b.Linv, Mp, w.D1);
-        GPZ_LAUNCH_OK();
-        if (int rc = dg(w.D1, w.D2, w.D3, GF_A_UPPER)) return rc;
+        if (int rc = tril_transpose(b.Linv, Mp, L32, w.D1, s)) return rc;
+        if (int rc = dgemm(w.D1, w.D2, w.D3, GF_A_UPPER)) return rc;
         hipLaunchKernelGGL((cast_kernel<T>), dim3(2048), dim3(256), 0, s, w.D3, w.A1, L * mm);
         GPZ_LAUNCH_OK();
       } else {
@@ -1356,8 +1115,7 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
       GPZ_LAUNCH_OK();                                                                                     // Sw - I (kept for Q)
       if (int rc = tgemm(w.LinvT, w.SwI, w.A1, GF_A_UPPER)) return rc;                                     // A1
       }
-      hipLaunchKernelGGL((linvT_vec_kernel<T>), dim3((unsigned)(Mp / 32), L32), dim3(256), 0, s, w.me, b.Linv, Mp, M, w.a3);
-      GPZ_LAUNCH_OK();
+      if (int rc = linvT_vec(w.me, b.Linv, Mp, M, L32, w.a3, Mp, nullptr, s)) return rc;    // a3 = Linv^T muE, zero padded
     }
   }
   const int64_t esz = sizeof(T);
@@ -1543,12 +1301,6 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
   hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)((Mp + 255) / 256), L32), dim3(256), 0, s, w.mu_part, pl.nchunks,
                      Mp, w.mu_sum);
   GPZ_LAUNCH_OK();
-  auto dgemm = [&](const double* A, const double* B, double* C, int flags) -> int {
-    GemmParams<double> d;
-    d.A = A; d.lda = Mp; d.sA0 = mm; d.B = B; d.ldb = Mp; d.sB0 = mm; d.C = C; d.ldc = Mp; d.sC0 = mm;
-    d.nb0 = L32; d.mt = d.nt = (int)pl.nblk; d.K = (int)Mp; d.flags = flags;
-    return gemm_launch(d, EPI_STORE, s);
-  };
   if (alg) {
     // dLoss/dLuE = tril(H LuE): H made symmetric, then one M x M product (LuT = LuE^T is the forward's stage-2 operand)
     hipLaunchKernelGGL((mirror_lower_kernel<T>), g32, dim3(256), 0, s, w.H, Mp);
@@ -1564,8 +1316,7 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
         hipLaunchKernelGGL((q_finish_kernel<double, T>), gm, dim3(256), 0, s, w.D3, (const T*)nullptr, Mp, M,
                            (const double*)w.me, (const double*)w.mu_sum);                            //    + muE v^T
         GPZ_LAUNCH_OK();
-        hipLaunchKernelGGL(tril_transpose_kernel, g32, dim3(256), 0, s, b.Linv, Mp, w.D1);
-        GPZ_LAUNCH_OK();
+        if (int rc = tril_transpose(b.Linv, Mp, L32, w.D1, s)) return rc;
         if (int rc = dgemm(w.D1, w.D3, w.D4, GF_A_UPPER | GF_TILES_LOWER)) return rc;                // D4 = GL (lower tiles)
       } else {
         if (int rc = tgemm(w.SwI, w.H, w.PS, GF_TILES_LOWER)) return rc;                             // PS = (Sw - I) H   (lower tiles)
@@ -1581,13 +1332,13 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
     hipLaunchKernelGGL((kl_add_kernel<T>), gm, dim3(256), 0, s, w.G, Mp, b.LuW, w.mu_sum, b.muE, g_kl);
     GPZ_LAUNCH_OK();
   }
-  if (wh)
+  if (wh) {
     hipLaunchKernelGGL((mu_grad_kernel<T>), dim3((unsigned)((M + 255) / 256), L32), dim3(256), 0, s, w.mu_sum,
                        (const double*)nullptr, Mp, M, static_cast<T*>(g->grad_mu), g_kl, static_cast<const T*>(p->mu));
-  else
-    hipLaunchKernelGGL((mu_grad_linv_kernel<T>), dim3((unsigned)((M + 31) / 32), L32), dim3(256), 0, s, w.mu_sum, b.Linv,
-                       Mp, M, static_cast<T*>(g->grad_mu));
-  GPZ_LAUNCH_OK();
+    GPZ_LAUNCH_OK();
+  } else {                           // grad_mu = Linv^T dLoss/dmuE
+    if (int rc = linvT_vec(w.mu_sum, b.Linv, Mp, M, L32, static_cast<T*>(g->grad_mu), M, nullptr, s)) return rc;
+  }
   T* Gfin = w.G;
   if (!wh) {
     // dLoss/dLu = tril(Linv^T tril(dLoss/dLuE))
@@ -1603,23 +1354,20 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
     if (int rc = gemm_launch(g4, EPI_STORE, s)) return rc;
     Gfin = w.G2;
   }
-  hipLaunchKernelGGL((lu_grad_kernel<T>), dim3((unsigned)((M + 255) / 256), (unsigned)M, L32), dim3(256), 0, s, Gfin, Mp,
-                     M, static_cast<const T*>(p->Lu_raw), static_cast<T*>(g->grad_Lu_raw), g_kl, (int)wh);
-  GPZ_LAUNCH_OK();
+  if (int rc = lu_grad(Gfin, Mp, M, L32, static_cast<const T*>(p->Lu_raw), static_cast<T*>(g->grad_Lu_raw), g_kl, (int)wh, s))
+    return rc;
   if (full) {
     // Cholesky backward (Murray 2016): Kbar_zz = Linv^T Phi(L^T Lbar) Linv with Lbar = -tril(GL)
     const double* E = nullptr;
     if (!wh) {
       // muE = Linv mu and LuE = Linv Lu also depend on the factor:
       // E = Linv^T (tril(dLoss/dLuE) LuE^T + dLoss/dmuE muE^T),  Lbar -= tril(E)
-      hipLaunchKernelGGL((tril_to_double_kernel<T>), gm, dim3(256), 0, s, w.G, Mp, w.D1);
-      GPZ_LAUNCH_OK();
+      if (int rc = tril_widen((const T*)w.G, Mp, Mp, L32, w.D1, s)) return rc;
       if (int rc = dgemm(w.D1, b.LuW, w.D2, GF_A_LOWER | GF_B_UPPER | GF_B_TRANS)) return rc;     // D2 = tril(G) LuE^T
       hipLaunchKernelGGL(rank1_update_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)(M < 1024 ? M : 1024), L32),
                          dim3(256), 0, s, w.D2, Mp, M, w.mu_sum, w.me);                           // (me = Linv mu, above)
       GPZ_LAUNCH_OK();
-      hipLaunchKernelGGL(tril_transpose_kernel, g32, dim3(256), 0, s, b.Linv, Mp, w.D1);         // D1 = Linv^T
-      GPZ_LAUNCH_OK();
+      if (int rc = tril_transpose(b.Linv, Mp, L32, w.D1, s)) return rc;                           // D1 = Linv^T
       if (int rc = dgemm(w.D1, w.D2, w.D3, GF_A_UPPER)) return rc;                                // D3 = E
       E = w.D3;
     }
@@ -1630,28 +1378,8 @@ static int svgp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, i
       hipLaunchKernelGGL((lbar_kernel<T, T>), gm, dim3(256), 0, s, (const T*)w.GL, Mp, M, static_cast<const T*>(g->g_chol), E, w.D2,
                          wh ? nullptr : g_kl, b.Kzz);
     GPZ_LAUNCH_OK();                                                                              // D2 = Lbar
-    hipLaunchKernelGGL(tril_transpose_kernel, g32, dim3(256), 0, s, b.Kzz, Mp, w.D1);            // D1 = L^T
-    GPZ_LAUNCH_OK();
-    if (int rc = dgemm(w.D1, w.D2, w.D3, GF_A_UPPER | GF_B_LOWER)) return rc;                     // D3 = L^T Lbar
-    hipLaunchKernelGGL(phi_kernel, gm, dim3(256), 0, s, w.D3, Mp);
-    GPZ_LAUNCH_OK();
-    GPZ_HIP_OK(hipMemsetAsync(w.D2, 0, sizeof(double) * L * mm, s));
-    if (int rc = dgemm(w.D3, b.Linv, w.D2, GF_A_LOWER | GF_B_LOWER | GF_TILES_LOWER)) return rc;   // D2 = Phi Linv
-    hipLaunchKernelGGL(tril_transpose_kernel, g32, dim3(256), 0, s, b.Linv, Mp, w.D1);           // D1 = Linv^T
-    GPZ_LAUNCH_OK();
-    if (int rc = dgemm(w.D1, w.D2, w.D3, GF_A_UPPER | GF_B_LOWER)) return rc;                     // D3 = P
-    hipLaunchKernelGGL((sym_cast_kernel<T>), g32, dim3(256), 0, s, w.D3, Mp, w.PS);               // P + P^T
-    GPZ_LAUNCH_OK();
-    KgradArgs ka;
-    ka.Kbar = w.PS; ka.ld = Mp; ka.stride = mm; ka.Z = p->Z; ka.X = p->Z; ka.gZ = p->gZ; ka.gX = p->gZ;
-    ka.sigma = p->k.sigma; ka.ell = p->k.lengthscale; ka.ga = p->k.group_a; ka.gr2 = p->k.group_r2;
-    ka.gpow = p->k.group_pow; ka.scalar_scale = 0.5; ka.M = M; ka.ncols = M; ka.Mp = Mp; ka.d = p->d;
-    ka.G = p->k.n_groups; ka.acc = w.kacc;
-    if (int rc = kgrad_launch(p->dtype, p->k.kind, ka, L32, s)) return rc;
-    const unsigned fx = (unsigned)std::max<int64_t>((M + 255) / 256, L);
-    hipLaunchKernelGGL(kgrad_finish_kernel, dim3(fx, 2), dim3(256), 0, s, w.kacc, L32, Mp, M, p->d, w.sig_direct,
-                       g->grad_Z, g->grad_theta);
-    GPZ_LAUNCH_OK();
+    if (int rc = chol_backward(b.Kzz, b.Linv, w.D2, Mp, L32, w.D1, w.D3, s)) return rc;            // D3 = P
+    if (int rc = kzz_grad(p, w.D3, nullptr, Mp, w.PS, w.kacc, w.sig_direct, g, s)) return rc;
   }
   return 0;
 }
@@ -1693,9 +1421,9 @@ static int precomputed_backward_t(const void* W, const void* sigma, const void* 
   GPZ_REQUIRE(ws_bytes >= w.bytes, "gpz_wsvgp_precomputed_backward: workspace too small");
   const int L32 = (int)L;
   const int64_t Mp = pl.Mp, mm = Mp * Mp;
-  hipLaunchKernelGGL((lu_prepare_kernel<T>), dim3((unsigned)(Mp / 32), (unsigned)(Mp / 32), L32), dim3(256), 0, s,
-                     static_cast<const T*>(Lu_raw), M, Mp, b.LuT, (double*)nullptr, (T*)nullptr, b.lu_part);
-  GPZ_LAUNCH_OK();
+  if (int rc = lu_forward(static_cast<const T*>(Lu_raw), M, Mp, L32, b.LuT, (double*)nullptr, (T*)nullptr, b.lu_part,
+                          (T*)nullptr, s))
+    return rc;
   GPZ_HIP_OK(hipMemsetAsync(w.G, 0, sizeof(T) * L * mm, s));
   GPZ_HIP_OK(hipMemsetAsync(w.sig_direct, 0, sizeof(double) * L, s));
   for (int64_t ci = 0; ci < pl.nchunks; ++ci) {
@@ -1741,9 +1469,8 @@ static int precomputed_backward_t(const void* W, const void* sigma, const void* 
   hipLaunchKernelGGL((mu_grad_kernel<T>), dim3((unsigned)((M + 255) / 256), L32), dim3(256), 0, s, w.mu_sum,
                      (const double*)nullptr, Mp, M, static_cast<T*>(grad_mu), (const double*)nullptr, static_cast<const T*>(mu));
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((lu_grad_kernel<T>), dim3((unsigned)((M + 255) / 256), (unsigned)M, L32), dim3(256), 0, s, w.G, Mp, M,
-                     static_cast<const T*>(Lu_raw), static_cast<T*>(grad_Lu_raw), (const double*)nullptr, 0);
-  GPZ_LAUNCH_OK();
+  if (int rc = lu_grad(w.G, Mp, M, L32, static_cast<const T*>(Lu_raw), static_cast<T*>(grad_Lu_raw), (const double*)nullptr, 0, s))
+    return rc;
   if (grad_sigma) {
     hipLaunchKernelGGL(copy_f64_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, s, w.sig_direct, grad_sigma, L32);
     GPZ_LAUNCH_OK();

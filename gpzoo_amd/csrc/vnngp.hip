@@ -22,13 +22,13 @@
 //                     the S and Kzz block gradients and dLoss/dZ through k_xz in that FIXED order: no
 //                     atomics on values, bitwise reproducible (a table with a repeated neighbour is summed
 //                     lane after lane, vnn_dup_kernel).  The dense tails -- dS -> dLu, Cholesky backward of
-//                     dLoss/dchol, the contraction with dKzz/d(sigma, lengthscale, Z) -- reuse the fp64
-//                     GEMM and kgrad.hip.
+//                     dLoss/dchol, the contraction with dKzz/d(sigma, lengthscale, Z) -- are the M x M helpers
+//                     of mmops.hip (shared with svgp.hip) over the fp64 GEMM and kgrad.hip.
 #include "common.h"
 #include "factor.h"
 #include "gemm.h"
-
-#include <algorithm>
+#include "kgrad.h"
+#include "mmops.h"
 
 // Timing-only diagnostics of vnngp_gather_kernel (WRONG results by construction; SRC=vnngp tools/ablate_fused.sh):
 // -DGPZ_VN_ABL=<bits>  1: no LDS row updates, 2: no record / index loads, 4: rows neither zeroed nor written out.
@@ -37,18 +37,6 @@
 #endif
 
 namespace gpz {
-
-struct KgradArgs {   // kgrad.hip
-  const void* Kbar; int64_t ld, stride;
-  const void* Z; const void* X;
-  const int64_t* gZ; const int64_t* gX;
-  const void* sigma; const void* ell; const void* ga; const void* gr2;
-  double gpow, scalar_scale;
-  int64_t M, ncols, Mp;
-  int d, G;
-  double* acc;
-};
-int kgrad_launch(int dtype, int kind, const KgradArgs& a, int L, hipStream_t s);
 
 constexpr int KNN_MAX = 32;
 
@@ -761,32 +749,6 @@ __global__ __launch_bounds__(64) void vnn_theta_sum_kernel(VnnBwdArgs<T> b, cons
   }
 }
 
-// (L,Mp,Mp) fp64 symmetric copy of the lower triangle (the fill wrote the full matrix already; this
-// is for S = Lu Lu^T whose GEMM writes every tile, nothing to do) -- kept for clarity of intent.
-
-template <typename T>
-__global__ __launch_bounds__(256) void vnn_lu_kernel(const T* __restrict__ raw, int64_t M, int64_t Mp,
-                                                    double* __restrict__ LuD, T* __restrict__ LuOut) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= Mp) return;
-  double v = 0.0;
-  if (i < M && j < M && j <= i) {
-    const double x = (double)raw[(int64_t)l * M * M + i * M + j];
-    v = (i == j) ? exp(x) : x;
-  }
-  LuD[(int64_t)l * Mp * Mp + i * Mp + j] = v;
-  if (LuOut && i < M && j < M) LuOut[(int64_t)l * M * M + i * M + j] = (T)v;
-}
-
-template <typename T>
-__global__ void vnn_chol_out_kernel(const double* __restrict__ Lc, int64_t Mp, int64_t M, T* __restrict__ out) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= M) return;
-  out[(int64_t)l * M * M + i * M + j] = (j <= i) ? (T)Lc[(int64_t)l * Mp * Mp + i * Mp + j] : (T)0;
-}
-
 struct VnnPlan {
   int64_t L, N, M, Mp; int K; size_t bytes;
   double *Kzz, *Kfac, *Dinv, *LuD, *S, *scratch; int64_t* idx;
@@ -900,7 +862,6 @@ template <typename T>
 static int vnn_prepare(const gpz_svgp_problem* p, VnnPlan& pl, const int64_t* idx_in, VnnArgs<T>& a, hipStream_t s) {
   const int64_t L = pl.L, M = pl.M, Mp = pl.Mp, N = pl.N, mm = Mp * Mp;
   const int L32 = (int)L;
-  const dim3 gm((unsigned)((Mp + 255) / 256), (unsigned)Mp, L32);
   const bool handed = p->factor_cache && (p->factor_cache_valid & 1);      // this call's forward left them in the buffer
   if (handed) {
     GPZ_HIP_OK(hipMemsetAsync(p->info, 0, sizeof(int32_t) * L, s));
@@ -910,20 +871,14 @@ static int vnn_prepare(const gpz_svgp_problem* p, VnnPlan& pl, const int64_t* id
     GPZ_HIP_OK(hipMemcpyAsync(pl.Kfac, pl.Kzz, sizeof(double) * L * mm, hipMemcpyDeviceToDevice, s));
     if (int rc = potrf_padded(pl.Kfac, Mp, Mp, mm, L, M, pl.Dinv, p->info, s, true, pl.fsync)) return rc;
   }
-  if (p->chol) {
-    hipLaunchKernelGGL((vnn_chol_out_kernel<T>), dim3((unsigned)((M + 255) / 256), (unsigned)M, L32), dim3(256), 0, s,
-                       pl.Kfac, Mp, M, static_cast<T*>(p->chol));
-    GPZ_LAUNCH_OK();
-  }
+  if (p->chol)
+    if (int rc = chol_out(pl.Kfac, Mp, M, L32, static_cast<T*>(p->chol), nullptr, s)) return rc;
   if (!handed) {
     // S = Lu Lu^T on the fp64 MFMA path
-    hipLaunchKernelGGL((vnn_lu_kernel<T>), gm, dim3(256), 0, s, static_cast<const T*>(p->Lu_raw), M, Mp, pl.LuD,
-                       static_cast<T*>(p->Lu));
-    GPZ_LAUNCH_OK();
-    GemmParams<double> g;
-    g.A = pl.LuD; g.lda = Mp; g.sA0 = mm; g.B = pl.LuD; g.ldb = Mp; g.sB0 = mm; g.C = pl.S; g.ldc = Mp; g.sC0 = mm;
-    g.nb0 = L32; g.mt = g.nt = (int)(Mp / 128); g.K = (int)Mp; g.flags = GF_A_LOWER | GF_B_UPPER | GF_B_TRANS;
-    if (int rc = gemm_launch(g, EPI_STORE, s)) return rc;
+    if (int rc = lu_forward(static_cast<const T*>(p->Lu_raw), M, Mp, L32, (T*)nullptr, pl.LuD, static_cast<T*>(p->Lu),
+                            nullptr, (T*)nullptr, s))
+      return rc;
+    if (int rc = dgemm_mm(pl.LuD, pl.LuD, pl.S, Mp, L32, GF_A_LOWER | GF_B_UPPER | GF_B_TRANS, 1.0, s)) return rc;
   }
   const int64_t* idx = idx_in;
   if (!idx) {
@@ -990,10 +945,7 @@ static int vnn_kl_prepare(const gpz_svgp_problem* p, VnnPlan& pl, double* kl, hi
   const int64_t L = pl.L, Mp = pl.Mp, mm = Mp * Mp;
   if (int rc = trtri_padded(pl.Kfac, Mp, mm, pl.Dinv, pl.Linv, Mp, L, pl.Tmp, s)) return rc;
   GPZ_HIP_OK(hipMemsetAsync(pl.LuE, 0, sizeof(double) * L * mm, s));
-  GemmParams<double> g;
-  g.A = pl.Linv; g.lda = Mp; g.sA0 = mm; g.B = pl.LuD; g.ldb = Mp; g.sB0 = mm; g.C = pl.LuE; g.ldc = Mp; g.sC0 = mm;
-  g.nb0 = (int)L; g.mt = g.nt = (int)(Mp / 128); g.K = (int)Mp; g.flags = GF_A_LOWER | GF_B_LOWER | GF_TILES_LOWER;
-  if (int rc = gemm_launch(g, EPI_STORE, s)) return rc;
+  if (int rc = dgemm_mm(pl.Linv, pl.LuD, pl.LuE, Mp, (int)L, GF_A_LOWER | GF_B_LOWER | GF_TILES_LOWER, 1.0, s)) return rc;
   double* part = pl.Tmp;     // the triangular inverse is done with its scratch (L * Mp * Mp / 2 doubles >= L * Mp)
   hipLaunchKernelGGL((vnn_kl_rows_kernel<T>), dim3((unsigned)(Mp / 4), (unsigned)L), dim3(256), 0, s, pl.Kfac, pl.Linv,
                      pl.LuE, static_cast<const T*>(p->Lu_raw), static_cast<const T*>(p->mu), pl.M, Mp, pl.muE, part);
@@ -1042,107 +994,6 @@ __global__ void vnn_mu_out_kernel(const double* __restrict__ gmu, int64_t Mp, in
   if (m < M) out[(int64_t)l * M + m] = (T)gmu[(int64_t)l * Mp + m];
 }
 
-// chain rule of Lu = tril(raw, -1) + diag(exp(diag raw)) applied to G = dLoss/dLu (fp64, padded)
-template <typename T>
-__global__ void vnn_lu_grad_kernel(const double* __restrict__ G, int64_t Mp, int64_t M, const T* __restrict__ raw,
-                                   T* __restrict__ out, const double* __restrict__ g_kl = nullptr) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= M) return;
-  const double g = G[(int64_t)l * Mp * Mp + i * Mp + j];
-  double v = 0.0;
-  if (j < i) v = g;
-  else if (j == i)   // Lu_ii = exp(raw_ii); the KL's -log Lu_ii contributes -g_kl to the raw diagonal
-    v = g * exp((double)raw[(int64_t)l * M * M + i * M + i]) - (g_kl ? g_kl[l] : 0.0);
-  out[(int64_t)l * M * M + i * M + j] = (T)v;
-}
-
-// dst (L,Mp,Mp) fp64 = tril(src (L,M,M)), zero padded
-template <typename T>
-__global__ void vnn_tril_in_kernel(const T* __restrict__ src, int64_t M, int64_t Mp, double* __restrict__ dst) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= Mp) return;
-  dst[(int64_t)l * Mp * Mp + i * Mp + j] = (i < M && j <= i) ? (double)src[(int64_t)l * M * M + i * M + j] : 0.0;
-}
-
-// dst = transpose(tril(src)), (L,Mp,Mp) fp64
-__global__ __launch_bounds__(256) void vnn_tril_transpose_kernel(const double* __restrict__ src, int64_t Mp,
-                                                                double* __restrict__ dst) {
-  __shared__ double tile[32][33];
-  const int l = blockIdx.z;
-  const int64_t i0 = (int64_t)blockIdx.y * 32, j0 = (int64_t)blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int rr = ty; rr < 32; rr += 8) {
-    const int64_t i = i0 + rr, j = j0 + tx;
-    tile[rr][tx] = (j <= i) ? src[(int64_t)l * Mp * Mp + i * Mp + j] : 0.0;
-  }
-  __syncthreads();
-  for (int rr = ty; rr < 32; rr += 8) dst[(int64_t)l * Mp * Mp + (j0 + rr) * Mp + i0 + tx] = tile[tx][rr];
-}
-
-// Phi of the Cholesky backward: keep the lower triangle, halve the diagonal
-__global__ void vnn_phi_kernel(double* __restrict__ A, int64_t Mp) {
-  const int l = blockIdx.z;
-  const int64_t i = blockIdx.y, j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= Mp) return;
-  double& v = A[(int64_t)l * Mp * Mp + i * Mp + j];
-  if (j > i) v = 0.0;
-  else if (j == i) v *= 0.5;
-}
-
-// dst = (P + P^T) [+ (Q + Q^T)] cast to T
-template <typename T>
-__global__ __launch_bounds__(256) void vnn_sym_cast_kernel(const double* __restrict__ P, const double* __restrict__ Q,
-                                                          int64_t Mp, T* __restrict__ dst) {
-  __shared__ double tile[32][33];
-  const int l = blockIdx.z;
-  const int64_t i0 = (int64_t)blockIdx.y * 32, j0 = (int64_t)blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int64_t base = (int64_t)l * Mp * Mp;
-  for (int rr = ty; rr < 32; rr += 8) {
-    const int64_t o = base + (j0 + rr) * Mp + i0 + tx;
-    tile[rr][tx] = P[o] + (Q ? Q[o] : 0.0);
-  }
-  __syncthreads();
-  for (int rr = ty; rr < 32; rr += 8) {
-    const int64_t o = base + (i0 + rr) * Mp + j0 + tx;
-    dst[o] = (T)(P[o] + (Q ? Q[o] : 0.0) + tile[tx][rr]);
-  }
-}
-
-// grad_Z[m][k] = sum_l acc[l][m][k];  grad_theta[l][q] = sum_m acc[l][m][4+q]
-__global__ __launch_bounds__(256) void vnn_kgrad_finish_kernel(const double* __restrict__ acc, int L, int64_t Mp, int64_t M,
-                                                              int d, double* __restrict__ grad_Z,
-                                                              double* __restrict__ grad_theta) {
-  __shared__ double sh[256];
-  if (blockIdx.y == 0) {
-    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (m < M && grad_Z)
-      for (int k = 0; k < 4; ++k) {
-        double t = 0.0;
-        if (k < d)
-          for (int l = 0; l < L; ++l) t += acc[((int64_t)l * Mp + m) * 8 + k];
-        grad_Z[m * 4 + k] = t;
-      }
-  } else if ((int)blockIdx.x < L && grad_theta) {
-    const int l = blockIdx.x;
-    for (int q = 0; q < 2; ++q) {
-      double v = 0.0;
-      for (int64_t m = threadIdx.x; m < M; m += 256) v += acc[((int64_t)l * Mp + m) * 8 + 4 + q];
-      __syncthreads();
-      sh[threadIdx.x] = v;
-      __syncthreads();
-      for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-      }
-      if (threadIdx.x == 0) grad_theta[l * 4 + q] = sh[0];
-    }
-    if (threadIdx.x == 0) grad_theta[l * 4 + 2] = grad_theta[l * 4 + 3] = 0.0;
-  }
-}
-
 // ---- KL(qU || pU) folded into the backward pass (g_kl = upstream dLoss/dkl_l) --------------------------------
 // G[l] += gk[l] * tril(T[l])                      (dKL/dLu = tril(Linv^T LuE); T = Linv^T LuE on the lower tiles)
 __global__ void vnn_kl_addG_kernel(double* __restrict__ G, const double* __restrict__ T, int64_t Mp,
@@ -1152,28 +1003,6 @@ __global__ void vnn_kl_addG_kernel(double* __restrict__ G, const double* __restr
   if (j > i || j >= Mp) return;
   const int64_t o = (int64_t)l * Mp * Mp + i * Mp + j;
   G[o] += g_kl[l] * T[o];
-}
-
-// gmu[l][a] += gk[l] * sum_{i >= a} Linv[l][i][a] * muE[l][i]        (dKL/dmu = Linv^T Linv mu)
-// 32 columns x 8 row segments per block (a thread per column alone left 40 blocks walking up to M rows each).
-__global__ __launch_bounds__(256) void vnn_kl_mu_kernel(double* __restrict__ gmu, const double* __restrict__ Linv,
-                                                       const double* __restrict__ muE, int64_t Mp, int64_t M,
-                                                       const double* __restrict__ g_kl) {
-  __shared__ double sh[8][33];
-  const int l = blockIdx.y, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int64_t a = (int64_t)blockIdx.x * 32 + tx;
-  const double* Li = Linv + (int64_t)l * Mp * Mp;
-  double t = 0.0;
-  if (a < M)
-    for (int64_t i = a + ty; i < M; i += 8) t = fma(Li[i * Mp + a], muE[(int64_t)l * Mp + i], t);
-  sh[ty][tx] = t;
-  __syncthreads();
-  if (ty == 0 && a < M) {
-    double v = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v += sh[q][tx];
-    gmu[(int64_t)l * Mp + a] += g_kl[l] * v;
-  }
 }
 
 // Q[l][i][j] += muE[l][i] * muE[l][j]
@@ -1285,45 +1114,35 @@ static int vnngp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, 
       GPZ_LAUNCH_OK();
     }
   }
-  const dim3 g32((unsigned)(Mp / 32), (unsigned)(Mp / 32), L32);
   const dim3 gm((unsigned)((Mp + 255) / 256), (unsigned)Mp, L32);
   auto dgemm = [&](const double* A, const double* B, double* C, int flags, double alpha) -> int {
-    GemmParams<double> d;
-    d.A = A; d.lda = Mp; d.sA0 = mm; d.B = B; d.ldb = Mp; d.sB0 = mm; d.C = C; d.ldc = Mp; d.sC0 = mm;
-    d.nb0 = L32; d.mt = d.nt = (int)(Mp / 128); d.K = (int)Mp; d.flags = flags; d.alpha = alpha;
-    return gemm_launch(d, EPI_STORE, s);
+    return dgemm_mm(A, B, C, Mp, L32, flags, alpha, s);
   };
   // S = Lu Lu^T, dS = T + T^T symmetric: dLoss/dLu = tril(2 dS Lu)
-  hipLaunchKernelGGL((vnn_sym_cast_kernel<double>), g32, dim3(256), 0, s, pl.gS, (const double*)nullptr, Mp, pl.D1);
-  GPZ_LAUNCH_OK();
+  if (int rc = sym_cast(pl.gS, nullptr, Mp, L32, pl.D1, s)) return rc;
   GPZ_HIP_OK(hipMemsetAsync(pl.G, 0, sizeof(double) * L * mm, s));
   if (int rc = dgemm(pl.D1, pl.LuD, pl.G, GF_B_LOWER | GF_TILES_LOWER, 2.0)) return rc;
   double* const LinvT = pl.S;        // the point kernels are done with S and Kzz: scratch from here on
   double* const Tm = pl.Kzz;
   if (g_kl) {
-    hipLaunchKernelGGL(vnn_tril_transpose_kernel, g32, dim3(256), 0, s, pl.Linv, Mp, LinvT);
-    GPZ_LAUNCH_OK();
+    if (int rc = tril_transpose(pl.Linv, Mp, L32, LinvT, s)) return rc;
     GPZ_HIP_OK(hipMemsetAsync(Tm, 0, sizeof(double) * L * mm, s));
     if (int rc = dgemm(LinvT, pl.LuE, Tm, GF_A_UPPER | GF_B_LOWER | GF_TILES_LOWER, 1.0)) return rc;   // Linv^T LuE
     hipLaunchKernelGGL(vnn_kl_addG_kernel, gm, dim3(256), 0, s, pl.G, Tm, Mp, g_kl);
     GPZ_LAUNCH_OK();
-    hipLaunchKernelGGL(vnn_kl_mu_kernel, dim3((unsigned)((M + 31) / 32), L32), dim3(256), 0, s, pl.gmu, pl.Linv, pl.muE,
-                       Mp, M, g_kl);
-    GPZ_LAUNCH_OK();
+    if (int rc = linvT_vec(pl.muE, pl.Linv, Mp, M, L32, pl.gmu, Mp, g_kl, s)) return rc;   // dKL/dmu = Linv^T Linv mu
   }
   hipLaunchKernelGGL((vnn_mu_out_kernel<T>), dim3((unsigned)((M + 255) / 256), L32), dim3(256), 0, s, pl.gmu, Mp, M,
                      static_cast<T*>(g->grad_mu));
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((vnn_lu_grad_kernel<T>), dim3((unsigned)((M + 255) / 256), (unsigned)M, L32), dim3(256), 0, s, pl.G,
-                     Mp, M, static_cast<const T*>(p->Lu_raw), static_cast<T*>(g->grad_Lu_raw), g_kl);
-  GPZ_LAUNCH_OK();
+  if (int rc = lu_grad((const double*)pl.G, Mp, M, L32, static_cast<const T*>(p->Lu_raw), static_cast<T*>(g->grad_Lu_raw), g_kl, 0, s))
+    return rc;
   if (!kgrads) return 0;
   const double* P = nullptr;
   if (with_chol) {
     // upstream dLoss/dchol (+ the KL's own dependence on the factor) -> Lbar
     if (g->g_chol) {
-      hipLaunchKernelGGL((vnn_tril_in_kernel<T>), gm, dim3(256), 0, s, static_cast<const T*>(g->g_chol), M, Mp, pl.D1);
-      GPZ_LAUNCH_OK();
+      if (int rc = tril_widen(static_cast<const T*>(g->g_chol), M, Mp, L32, pl.D1, s)) return rc;
     } else {
       GPZ_HIP_OK(hipMemsetAsync(pl.D1, 0, sizeof(double) * L * mm, s));
     }
@@ -1336,31 +1155,10 @@ static int vnngp_backward_t(const gpz_svgp_problem* p, const gpz_svgp_grads* g, 
       hipLaunchKernelGGL(vnn_kl_lbar_kernel, gm, dim3(256), 0, s, pl.D1, Tm, pl.Kfac, Mp, M, g_kl);
       GPZ_LAUNCH_OK();
     }
-    // Cholesky backward (Murray 2016): P = Linv^T Phi(L^T Lbar) Linv
-    hipLaunchKernelGGL(vnn_tril_transpose_kernel, g32, dim3(256), 0, s, pl.Kfac, Mp, pl.G);   // G  = L^T
-    GPZ_LAUNCH_OK();
-    if (int rc = dgemm(pl.G, pl.D1, pl.D2, GF_A_UPPER | GF_B_LOWER, 1.0)) return rc;          // D2 = L^T Lbar
-    hipLaunchKernelGGL(vnn_phi_kernel, gm, dim3(256), 0, s, pl.D2, Mp);
-    GPZ_LAUNCH_OK();
-    GPZ_HIP_OK(hipMemsetAsync(pl.D1, 0, sizeof(double) * L * mm, s));
-    if (int rc = dgemm(pl.D2, pl.Linv, pl.D1, GF_A_LOWER | GF_B_LOWER | GF_TILES_LOWER, 1.0)) return rc;   // D1 = Phi Linv
-    hipLaunchKernelGGL(vnn_tril_transpose_kernel, g32, dim3(256), 0, s, pl.Linv, Mp, pl.G);  // G  = Linv^T
-    GPZ_LAUNCH_OK();
-    if (int rc = dgemm(pl.G, pl.D1, pl.D2, GF_A_UPPER | GF_B_LOWER, 1.0)) return rc;          // D2 = P
+    if (int rc = chol_backward(pl.Kfac, pl.Linv, pl.D1, Mp, L32, pl.G, pl.D2, s)) return rc;    // D2 = P (G: scratch)
     P = pl.D2;
   }
-  hipLaunchKernelGGL((vnn_sym_cast_kernel<T>), g32, dim3(256), 0, s, pl.gK, P, Mp, static_cast<T*>(pl.PS));
-  GPZ_LAUNCH_OK();
-  KgradArgs ka;
-  ka.Kbar = pl.PS; ka.ld = Mp; ka.stride = mm; ka.Z = p->Z; ka.X = p->Z; ka.gZ = nullptr; ka.gX = nullptr;
-  ka.sigma = p->k.sigma; ka.ell = p->k.lengthscale; ka.ga = nullptr; ka.gr2 = nullptr;
-  ka.gpow = 0.0; ka.scalar_scale = 0.5; ka.M = M; ka.ncols = M; ka.Mp = Mp; ka.d = p->d; ka.G = 0; ka.acc = pl.kacc;
-  if (int rc = kgrad_launch(p->dtype, p->k.kind, ka, L32, s)) return rc;
-  const unsigned fx = (unsigned)std::max<int64_t>((M + 255) / 256, L);
-  hipLaunchKernelGGL(vnn_kgrad_finish_kernel, dim3(fx, 2), dim3(256), 0, s, pl.kacc, L32, Mp, M, p->d, g->grad_Z,
-                     g->grad_theta);
-  GPZ_LAUNCH_OK();
-  return 0;
+  return kzz_grad(p, pl.gK, P, Mp, pl.PS, pl.kacc, nullptr, g, s);
 }
 
 }  // namespace gpz
