@@ -633,11 +633,14 @@ __global__ __launch_bounds__(256) void w_rowstats_kernel(const T* __restrict__ W
 }
 
 struct PrePlan { int64_t Mp, nblk, nc, nchunks, nfb_chunk, nlu; };
+// Test seam (gpz_debug_precomputed_chunk): columns per chunk instead of the 2 GiB rule and its 1024 floor; 0: the rule.
+static int64_t g_pre_chunk_override = 0;
 static PrePlan pre_plan(int64_t L, int64_t N, int64_t M, int esz) {
   PrePlan pl;
   pl.Mp = pad_up(M); pl.nblk = pl.Mp / NB;
   int64_t chunk = (int64_t)(2.0 * (1ull << 30) / ((double)L * pl.Mp * esz));
   if (chunk < 1024) chunk = 1024;
+  if (g_pre_chunk_override > 0) chunk = g_pre_chunk_override;
   pl.nc = pad_up(chunk > N ? N : chunk);
   pl.nchunks = (N + pl.nc - 1) / pl.nc;
   pl.nfb_chunk = (pl.nc + 255) / 256;
@@ -1524,6 +1527,14 @@ extern "C" int gpz_svgp_forward(const gpz_svgp_problem* p, int64_t chunk, void* 
   hipStream_t s = static_cast<hipStream_t>(stream);
   return p->dtype == GPZ_F32 ? svgp_forward_t<float>(p, chunk, ws, ws_bytes, s)
                              : svgp_forward_t<double>(p, chunk, ws, ws_bytes, s);
+}
+
+// Tests only (not in gpzoo_hip.h): chunk width of the precomputed passes and their workspace sizes, process wide.  A multiple
+// of 128 replaces pre_plan's rule, 0 restores it, anything else is ignored; returns the previous value.
+extern "C" int64_t gpz_debug_precomputed_chunk(int64_t cols) {
+  const int64_t prev = g_pre_chunk_override;
+  if (cols >= 0 && cols % NB == 0) g_pre_chunk_override = cols;
+  return prev;
 }
 
 extern "C" size_t gpz_wsvgp_precomputed_workspace_bytes(int64_t L, int64_t N, int64_t M, int32_t dtype) {

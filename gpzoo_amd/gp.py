@@ -425,14 +425,19 @@ class WSVGP(_FusedGP):
         """q(F) from a caller-supplied W (L,N,M) (gp.py:308-322); differentiable w.r.t. mu, Lu and the kernel's
         sigma like the reference's expression (gpz_wsvgp_precomputed_backward).  W itself is a constant here."""
         trainable = (self.mu, self.Lu, self.kernel.sigma)
+        single = self.mu.dim() == 1
+        # one q(U) shared by the rows of a 3-D W: the reference's expression broadcasts to (L, N) (L = 1 too), every row is kept
+        shared = single and W.dim() == 3
+        pick = (lambda t: t[0]) if single and not shared else (lambda t: t)
         if not (torch.is_grad_enabled() and any(t.requires_grad for t in trainable)):
-            return self._distributions(ops.wsvgp_precomputed(W, self.kernel.sigma, self.mu, self.Lu))
+            out = ops.wsvgp_precomputed(W, self.kernel.sigma, self.mu, self.Lu)
+            qF = ops.checked_dist(distributions.Normal, pick(out["mean"]), pick(out["scale"]))
+            return qF, _FusedQU(self.mu, scale_tril=out["Lu"][0] if single else out["Lu"], validate_args=False), None
         if W.requires_grad:
             raise NotImplementedError("forward_precomputed treats W as a constant: detach it (gradients w.r.t. the kernel "
                                       "hyper-parameters and Z flow through forward())")
         mean, scale = _PrecomputedMoments.apply(W, self.kernel.sigma, self.mu, self.Lu)
         Lu = self.Lu.tril(-1) + torch.diag_embed(torch.diagonal(self.Lu, dim1=-2, dim2=-1).exp())
-        pick = (lambda t: t[0]) if self.mu.dim() == 1 else (lambda t: t)
         return ops.checked_dist(distributions.Normal, pick(mean), pick(scale)), _FusedQU(self.mu, scale_tril=Lu, validate_args=False), None
 
 
