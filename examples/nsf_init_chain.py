@@ -5,7 +5,8 @@
 
 on synthetic counts, against the same model started from mu = 0 and random loadings.
 
-    PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30]
+    PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30
+                                                   --inducing-from {subset,kmeans}]
 """
 import argparse
 
@@ -16,8 +17,8 @@ import torch.nn as nn
 from gpzoo.gp import SVGP
 from gpzoo.kernels import NSF_RBF
 from gpzoo.likelihoods import NSF2
-from gpzoo.utilities import (init_softplus, regularized_nmf, rescale_spatial_coords, scanpy_sizefactors,
-                             smooth_spatial_factors, train)
+from gpzoo.utilities import (init_softplus, kmeans_inducing_points, regularized_nmf, rescale_spatial_coords,
+                             scanpy_sizefactors, smooth_spatial_factors, train)
 
 
 def synthetic_counts(N, D, L, rng):
@@ -48,6 +49,8 @@ def main():
     ap.add_argument("--factors", type=int, default=6)
     ap.add_argument("--inducing", type=int, default=500)
     ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--inducing-from", "--inducing_from", choices=("subset", "kmeans"), default="subset",
+                    help="inducing points: a random subset of the spots, or their k-means centres (kmeans_inducing_points)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     rng = np.random.default_rng(0)
@@ -58,7 +61,10 @@ def main():
     sz = scanpy_sizefactors(Y)
     F, W = regularized_nmf(torch.as_tensor(Y, device=dev), L, sz=sz, solver="mu", init="nndsvdar",
                            beta_loss="kullback-leibler", max_iter=200, random_state=0)
-    Z = X[rng.choice(a.spots, M, replace=False)]
+    if a.inducing_from == "kmeans":
+        Z = kmeans_inducing_points(X, M, random_state=0)
+    else:
+        Z = X[rng.choice(a.spots, M, replace=False)]
     U, beta0, beta = smooth_spatial_factors(F, Z, X)
     print(f"N={a.spots} D={a.genes} L={L} M={M}: F {F.shape} {F.dtype}, U {U.shape} {U.dtype}, trend {beta.shape}")
 

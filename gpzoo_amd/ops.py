@@ -819,6 +819,100 @@ def knn_mean(X, F, Z, K: int, return_index: bool = False):
     return (U, idx) if return_index else U
 
 
+def _kmeans_args(who: str, X, M: int):
+    _need_cuda(X)
+    if X.dim() != 2:
+        raise ValueError(f"{who}: X must be (N, d), got shape {tuple(X.shape)}")
+    _dt(X)
+    return X.detach().contiguous(), X.shape[0], X.shape[1], int(M)
+
+
+def _kmeans_centres(who: str, C, M: int, d: int, device):
+    _need_cuda(C)
+    if C.dtype != torch.float64 or tuple(C.shape) != (M, d) or not C.is_contiguous() or C.device != device:
+        raise ValueError(f"{who}: C must be a contiguous ({M}, {d}) float64 tensor on {device}, got {tuple(C.shape)} "
+                         f"{C.dtype} on {C.device}")
+
+
+@_on_device
+def kmeans_seed(X, M: int, u):
+    """k-means++ seeding of M centres among the rows of X (N,d), d <= 4, fp32 or fp64, from the uniform draws u (M,T)
+    fp64 (gpz_kmeans_seed; sklearn's ``_kmeans_plusplus`` with the random stream passed in, T = 2 + floor(ln M) trials per
+    centre).  Returns ``(idx (M,) int64, C (M,d) fp64)``.  Sums in a fixed order: repeated calls agree bit for bit."""
+    X, N, d, M = _kmeans_args("kmeans_seed", X, M)
+    _need_cuda(u)
+    if u.dim() != 2 or u.shape[0] != M or u.dtype != torch.float64:
+        raise ValueError(f"kmeans_seed: u must be ({M}, T) float64, got {tuple(u.shape)} {u.dtype}")
+    u = u.detach().to(X.device).contiguous()
+    T = u.shape[1]
+    lib = _lib.load()
+    nb = lib.gpz_kmeans_seed_workspace_bytes(N, d, M, T)
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    idx = torch.empty(M, dtype=torch.int64, device=X.device)
+    C = torch.empty((M, d), dtype=torch.float64, device=X.device)
+    ws = _workspace(X.device, nb)
+    rc = lib.gpz_kmeans_seed(_ptr(X), N, d, _dt(X), M, T, _ptr(u), _ptr(idx), _ptr(C), _ptr(ws), ws.numel(), _stream(X.device))
+    _lib.check(rc, "gpz_kmeans_seed")
+    return idx, C
+
+
+def kmeans_state(device) -> torch.Tensor:
+    """A zeroed gpz_kmeans_state record on ``device`` for ``kmeans_lloyd``: (4,) int64 -- iterations done, stop reason
+    (0 none / 1 labels / 2 tol), the last shift (the bits of an fp64: ``state[2:3].view(torch.float64)``), points relocated."""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+@_on_device
+def kmeans_lloyd(X, C, labels, state, tol_abs: float, iters: int):
+    """Enqueue up to ``iters`` further Lloyd iterations on the centres C (M,d) fp64, IN PLACE (gpz_kmeans_lloyd).  labels
+    (N,) int32 in/out (-1 everywhere before the first iteration), state from ``kmeans_state``; every launch returns at
+    once when the record holds a stop reason, so nothing here synchronises: read ``state`` once per block of
+    iterations.  Returns None."""
+    X, N, d, M = _kmeans_args("kmeans_lloyd", X, C.shape[0] if C.dim() == 2 else 0)
+    _kmeans_centres("kmeans_lloyd", C, M, d, X.device)
+    _need_cuda(labels, state)
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (N,) or not labels.is_contiguous():
+        raise ValueError(f"kmeans_lloyd: labels must be a contiguous ({N},) int32 tensor, got {tuple(labels.shape)} {labels.dtype}")
+    if state.dtype != torch.int64 or tuple(state.shape) != (4,) or not state.is_contiguous():
+        raise ValueError("kmeans_lloyd: state must come from ops.kmeans_state")
+    lib = _lib.load()
+    nb = lib.gpz_kmeans_lloyd_workspace_bytes(N, d, M)
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ws = _workspace(X.device, nb)
+    rc = lib.gpz_kmeans_lloyd(_ptr(X), N, d, _dt(X), _ptr(C), M, float(tol_abs), int(iters), _ptr(labels), _ptr(state),
+                              _ptr(ws), ws.numel(), _stream(X.device))
+    _lib.check(rc, "gpz_kmeans_lloyd")
+
+
+@_on_device
+def kmeans_assign(X, C, labels=None, return_d2: bool = False):
+    """The nearest centre of every row of X (N,d) among C (M,d) fp64, ties to the lower index (gpz_kmeans_assign).
+    ``labels=None``: returns ``(labels (N,) int32, inertia)``; given labels (N,) int32 are kept and only their inertia is
+    computed.  inertia is a 0-d fp64 tensor on the device; ``return_d2`` adds the (N,) fp64 squared distances."""
+    X, N, d, M = _kmeans_args("kmeans_assign", X, C.shape[0] if C.dim() == 2 else 0)
+    _kmeans_centres("kmeans_assign", C, M, d, X.device)
+    keep = labels is not None
+    if keep:
+        _need_cuda(labels)
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (N,) or not labels.is_contiguous():
+            raise ValueError(f"kmeans_assign: labels must be a contiguous ({N},) int32 tensor, got {tuple(labels.shape)} {labels.dtype}")
+    else:
+        labels = torch.full((N,), -1, dtype=torch.int32, device=X.device)
+    lib = _lib.load()
+    nb = lib.gpz_kmeans_assign_workspace_bytes(N, d, M)
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    d2 = torch.empty(N, dtype=torch.float64, device=X.device) if return_d2 else None
+    inertia = torch.empty((), dtype=torch.float64, device=X.device)
+    ws = _workspace(X.device, nb)
+    rc = lib.gpz_kmeans_assign(_ptr(X), N, d, _dt(X), _ptr(C), M, int(keep), _ptr(labels), _ptr(d2), _ptr(inertia), _ptr(ws),
+                               ws.numel(), _stream(X.device))
+    _lib.check(rc, "gpz_kmeans_assign")
+    return (labels, inertia, d2) if return_d2 else (labels, inertia)
+
+
 def _nmf_args(X, W, H, who: str):
     _need_cuda(X, W, H)
     if X.dim() != 2 or W.dim() != 2 or H.dim() != 2 or W.shape[0] != X.shape[0] or H.shape[1] != X.shape[1] or W.shape[1] != H.shape[0]:

@@ -587,6 +587,120 @@ def smooth_spatial_factors(F, Z, X=None):
     return U.astype(out), beta0.astype(out), beta.astype(out)
 
 
+KMEANS_BLOCK = 16     # Lloyd iterations enqueued between two reads of the device's stop record
+
+
+def kmeans_inducing_points(X, M, *, init="k-means++", max_iter=300, tol=1e-4, random_state=None, return_info=False):
+    """The (M,d) k-means centres of the spots X (N,d) -- the usual inducing points Z of a sparse GP, and what the
+    notebooks get from ``KMeans(n_clusters=M).fit(X).cluster_centers_`` -- by k-means++ seeding and Lloyd's iterations
+    in HIP (``ops.kmeans_seed`` / ``kmeans_lloyd`` / ``kmeans_assign``) on X's GPU, or on the current GPU for numpy / host
+    inputs.  It is sklearn's ``KMeans(n_clusters=M, n_init=1, algorithm="lloyd", max_iter=max_iter, tol=tol)``; no sklearn
+    is imported.
+
+    sklearn-exact: Lloyd from a given start (``init`` an (M,d) array) -- the same labels and number of iterations, centres
+    and inertia to fp64 rounding, wherever no point lies within rounding of two centres.  The distance is fp64, each
+    (x_k - c_k)^2 rounded and added in coordinate order; ties go to the lower centre index; centres are fp64 means; the stop
+    is by repeated labels, else by shift <= tol * mean(var(X, axis=0)) (fp64, population form), else at ``max_iter``.
+    Defined here: (1) the random stream.  ``init="k-means++"`` is sklearn's greedy ``_kmeans_plusplus`` (2 + floor(ln M)
+    trials per centre) driven by ``np.random.default_rng(random_state).random((M, T))``, and ``init="random"`` takes the rows
+    ``np.random.default_rng(random_state).choice(N, M, replace=False)``: a seeded result therefore DIFFERS from sklearn's
+    for the same ``random_state`` (its choices hang on float32 GEMM-form distances and numpy's legacy generator); it is the
+    same algorithm and the same quality.  (2) the pairing of several empty clusters with the points relocated to them: the
+    farthest point goes to the lowest empty cluster (sklearn's pairing is ``argpartition``'s, which is unspecified; for one
+    empty cluster the choice is sklearn's).  A cluster left without a member stays at its old centre.  Every sum runs in a
+    fixed order without floating-point atomics: two calls on the same input agree bit for bit.
+
+    Limits: 1 <= d <= 4, 1 <= M <= N < 2**31, dense X, no sample weights, ``n_init = 1``.
+
+    X: numpy array or torch tensor (host or CUDA), float32 or float64 (anything else is taken as float64).  Returns the
+    centres in X's dtype: numpy for numpy, a tensor on X's device for a tensor.  ``return_info=True`` adds a dict:
+    ``labels`` (N,) int64, ``inertia`` (float), ``n_iter`` (int), ``converged`` ("labels", "tol" or False),
+    ``seed_indices`` ((M,) int64 of the rows the start was taken from, None for an array ``init``) -- labels and
+    seed_indices of X's kind.  ValueError, before anything touches a GPU: X not (N,d), d outside 1..4, M outside 1..N,
+    an unknown ``init`` string or an ``init`` array that is not (M,d), ``max_iter < 1``, ``tol < 0``, a non-finite ``init``,
+    a non-finite X (checked where X lives: on the host for host input, by one device reduction for a CUDA tensor, before
+    any k-means launch)."""
+    import math
+    import numpy as np
+
+    who = "kmeans_inducing_points"
+    is_tensor = isinstance(X, torch.Tensor)
+    Xt = X.detach() if is_tensor else torch.as_tensor(np.asarray(X))
+    if Xt.dim() != 2:
+        raise ValueError(f"{who}: X must be (N, d), got shape {tuple(Xt.shape)}")
+    N, d = Xt.shape
+    if not 1 <= d <= 4:
+        raise ValueError(f"{who}: coordinates of dimension {d} unsupported (1..4)")
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)):
+        raise ValueError(f"{who}: M must be an integer, got {M!r}")
+    M = int(M)
+    if not 1 <= M <= N:
+        raise ValueError(f"{who}: M={M} outside 1..N={N}")
+    if N >= 2 ** 31:
+        raise ValueError(f"{who}: N={N} unsupported (N < 2**31)")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError(f"{who}: max_iter={max_iter!r} must be an integer >= 1")
+    if not (isinstance(tol, (int, float, np.floating, np.integer)) and tol >= 0):
+        raise ValueError(f"{who}: tol={tol!r} must be a number >= 0")
+    C0 = None
+    if isinstance(init, str):
+        if init not in ("k-means++", "random"):
+            raise ValueError(f"{who}: unknown init {init!r} ('k-means++', 'random' or an (M, d) array)")
+    else:
+        C0 = init.detach() if isinstance(init, torch.Tensor) else torch.as_tensor(np.asarray(init))
+        if tuple(C0.shape) != (M, d):
+            raise ValueError(f"{who}: init must be ({M}, {d}), got shape {tuple(C0.shape)}")
+        C0 = torch.as_tensor(C0.cpu().numpy().astype(np.float64))
+        if not bool(np.isfinite(C0.numpy()).all()):
+            raise ValueError(f"{who}: init holds a non-finite value")
+    out_dtype = Xt.dtype if Xt.dtype in (torch.float32, torch.float64) else torch.float64
+
+    if Xt.is_floating_point() and not bool(torch.isfinite(Xt).all()):       # (on X's own device: the host for host input)
+        raise ValueError(f"{who}: X holds a non-finite value")
+
+    from . import ops
+    dev = Xt.device if Xt.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    Xd = Xt.to(device=dev, dtype=out_dtype).contiguous()
+
+    seed_idx = None
+    if C0 is not None:
+        C = C0.to(dev).contiguous()
+    elif init == "random":
+        seed_idx = torch.as_tensor(np.random.default_rng(random_state).choice(N, M, replace=False).astype(np.int64)).to(dev)
+        C = Xd[seed_idx].double().contiguous()
+    else:
+        T = 2 + int(math.log(M))
+        u = torch.as_tensor(np.random.default_rng(random_state).random((M, T))).to(dev)
+        seed_idx, C = ops.kmeans_seed(Xd, M, u)
+    tol_abs = float(tol) * float(Xd.double().var(dim=0, unbiased=False).mean())
+    labels = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    state = ops.kmeans_state(dev)
+    done, stop = 0, 0
+    while done < max_iter and stop == 0:
+        ops.kmeans_lloyd(Xd, C, labels, state, tol_abs, min(KMEANS_BLOCK, max_iter - done))
+        host = state.cpu()
+        done, stop = int(host[0]), int(host[1])
+    if stop == 1:
+        _, inertia = ops.kmeans_assign(Xd, C, labels)
+    else:
+        labels, inertia = ops.kmeans_assign(Xd, C)
+    centres = C.to(out_dtype)
+    if not is_tensor:
+        centres = centres.cpu().numpy()
+    elif not Xt.is_cuda:
+        centres = centres.cpu()
+    if not return_info:
+        return centres
+
+    def like_x(t):
+        t = t.to(torch.int64)
+        return t.cpu().numpy() if not is_tensor else (t if Xt.is_cuda else t.cpu())
+
+    info = dict(labels=like_x(labels), inertia=float(inertia), n_iter=done, converged={1: "labels", 2: "tol"}.get(stop, False),
+                seed_indices=None if seed_idx is None else like_x(seed_idx))
+    return centres, info
+
+
 # Host-side data preparation of the reference's utilities module (AnnData conversion, plotting, ...) is outside the
 # accelerated path and not rebuilt here.  The names resolve so that
 # ``from gpzoo.utilities import train_hybrid, anndata_to_train_val`` -- the notebooks' import lines -- keep

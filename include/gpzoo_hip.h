@@ -27,7 +27,9 @@
  * gpz_vnngp_forward / _backward (and their workspace queries) accept GPZ_KERNEL_MATERN32, _MATERN12 and _MATERN52 next to
  * GPZ_KERNEL_RBF -- the set of accepted kind values grew, nothing else about the entries changed;
  * gpz_knn_mean and gpz_knn_mean_workspace_bytes -- the exact K-nearest mean of the factors at the inducing points behind
- * smooth_spatial_factors (utilities.py:50-68, sklearn's KNeighborsRegressor.predict).
+ * smooth_spatial_factors (utilities.py:50-68, sklearn's KNeighborsRegressor.predict);
+ * gpz_kmeans_seed, gpz_kmeans_lloyd, gpz_kmeans_assign and their *_workspace_bytes queries -- k-means++ seeding and Lloyd's
+ * iterations behind kmeans_inducing_points (the notebooks' sklearn KMeans(n_clusters=M).fit(X).cluster_centers_ for Z).
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -394,6 +396,58 @@ int gpz_nmf_kl_divergence(const void* X, const void* W, const void* H, int64_t N
 size_t gpz_knn_mean_workspace_bytes(int64_t N, int64_t M, int32_t d, int64_t K, int64_t L);
 int gpz_knn_mean(const void* X, int64_t N, const void* Z, int64_t M, int32_t d, int32_t dtype, const void* F, int64_t L,
                  int32_t f_dtype, int64_t K, double* U, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
+
+/* k-means for the inducing points: Z = the centres of sklearn's KMeans(n_clusters=M, n_init=1, algorithm="lloyd") on the
+ * spots X (N,d), fp32 or fp64 by `dtype`, row-major, dense, no sample weights.  Centres C (M,d) are fp64 throughout.
+ * Shared arithmetic: d^2 is the kNN distance of gpz_knn_mean (coordinates as fp64, each (x_k - c_k)^2 rounded, added in
+ * coordinate order; a NaN d^2 ranks as +inf); a point's label is the arg-min over (d^2, centre index): ties go to the
+ * lower index.  No floating-point atomics; every sum is fp64 in an order fixed by the shapes: repeated calls agree bit for
+ * bit.  No kernel waits on another workgroup.  1 <= d <= 4, 1 <= M <= N < 2^31; anything else is an argument error on the
+ * host, before any launch (the workspace queries then return 0).  Each workspace holds the fp64 points and O(N + M) scratch
+ * (plus 12 N bytes per centre split when N is small against the chip).
+ *
+ * gpz_kmeans_lloyd runs up to `iters` (1..2^20) further iterations of sklearn's lloyd_iter + the stopping rules of
+ * _kmeans_single_lloyd, C in place.  One iteration: labels w.r.t. the current centres (labels (N,) int32 in/out: on entry
+ * the previous iteration's labels, -1 everywhere before the first); each new centre the fp64 mean of its members (lane j of
+ * one wave per cluster sums the members among the points j mod 64 in ascending index, the lanes by a fixed tree); empty
+ * clusters relocated as _relocate_empty_clusters_dense does -- skipped when max d^2 = 0, else the n_empty points with the
+ * largest d^2 to their own old centre, ties to the lower index, taken in descending order by the empty clusters in
+ * ascending index, each subtracted from the sum and count of the cluster it leaves (sklearn's set of points; its pairing
+ * for more than one empty cluster is argpartition's, which is unspecified) --; a cluster left without a member stays at
+ * its old centre; shift = sum ||c_new - c_old||^2.  Stop reason 1 when no label changed, else 2 when shift <= tol_abs
+ * (the caller's tol * mean(var(X, axis=0))).  `state` is a caller-owned DEVICE record, zeroed before the first call; every
+ * launch of an iteration returns at once when state->stop is set, so a caller enqueues a block of iterations and reads the
+ * record once per block.  After a stop other than 1 (or none) the labels are one iteration behind the centres:
+ * gpz_kmeans_assign gives the final ones.  Lloyd from a given start is sklearn-exact (labels, n_iter_) wherever no point
+ * lies within rounding of two centres.
+ *
+ * gpz_kmeans_assign: keep_labels = 0 writes labels[n] = arg-min (the final labelling step, or "which inducing point owns
+ * this spot"); keep_labels = 1 takes labels as given (one outside [0, M) has d^2 = +inf).  d2_out (N,) fp64 or NULL: d^2 of
+ * each point to its label's centre.  inertia_out (device fp64) or NULL: their sum, 256 points per block total and the block
+ * totals in block order.
+ *
+ * gpz_kmeans_seed: greedy k-means++ (sklearn's _kmeans_plusplus) with the random stream passed in: u (M,T) fp64 on the
+ * device, uniform in [0, 1), T (1..32; sklearn's 2 + floor(ln M)) trials per centre.  The first index is floor(u[0,0] N);
+ * for c = 1..M-1 candidate t is the smallest i with cumsum(closest_d2)[i] >= u[c,t] pot, clipped to N - 1 (index 0 when
+ * pot = 0), the cumulative sum in two levels (totals of blocks of 256 points, then inside the chosen block); the candidate
+ * whose sum of min(closest_d2, d^2(candidate, .)) is smallest wins, ties to the lower t.  idx_out (M,) int64 the chosen
+ * points, C_out (M,d) fp64 their coordinates.  The stream is defined here (numpy's default_rng in the Python wrapper), so a
+ * seeded result differs from sklearn's for the same random_state.  M - 1 dependent steps of four short launches. */
+typedef struct gpz_kmeans_state {
+  int64_t iterations; /* iterations done over all calls */
+  int64_t stop;       /* 0 = none, 1 = the labels repeated, 2 = shift <= tol_abs */
+  double shift;       /* of the last iteration */
+  int64_t relocated;  /* points given to empty clusters, over all iterations */
+} gpz_kmeans_state;
+size_t gpz_kmeans_seed_workspace_bytes(int64_t N, int32_t d, int64_t M, int32_t T);
+int gpz_kmeans_seed(const void* X, int64_t N, int32_t d, int32_t dtype, int64_t M, int32_t T, const double* u,
+                    int64_t* idx_out, double* C_out, void* ws, size_t ws_bytes, void* stream);
+size_t gpz_kmeans_lloyd_workspace_bytes(int64_t N, int32_t d, int64_t M);
+int gpz_kmeans_lloyd(const void* X, int64_t N, int32_t d, int32_t dtype, double* C, int64_t M, double tol_abs, int64_t iters,
+                     int32_t* labels, gpz_kmeans_state* state, void* ws, size_t ws_bytes, void* stream);
+size_t gpz_kmeans_assign_workspace_bytes(int64_t N, int32_t d, int64_t M);
+int gpz_kmeans_assign(const void* X, int64_t N, int32_t d, int32_t dtype, const double* C, int64_t M, int32_t keep_labels,
+                      int32_t* labels, double* d2_out, double* inertia_out, void* ws, size_t ws_bytes, void* stream);
 
 /* Multi-GPU: latent GPs shard across ranks with no data-path collective; the only exchange is
  * the sum of each rank's partial ELBO -- one ncclAllReduce(sum, fp64) over RCCL/xGMI.  The reference has no
