@@ -6,7 +6,7 @@
 on synthetic counts, against the same model started from mu = 0 and random loadings.
 
     PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30
-                                                   --inducing-from {subset,kmeans}]
+                                                   --inducing-from {subset,kmeans} --mu-from {smooth,projection}]
 """
 import argparse
 
@@ -17,8 +17,8 @@ import torch.nn as nn
 from gpzoo.gp import SVGP
 from gpzoo.kernels import NSF_RBF
 from gpzoo.likelihoods import NSF2
-from gpzoo.utilities import (init_softplus, kmeans_inducing_points, regularized_nmf, rescale_spatial_coords,
-                             scanpy_sizefactors, smooth_spatial_factors, train)
+from gpzoo.utilities import (init_softplus, kmeans_inducing_points, project_factors_to_inducing, regularized_nmf,
+                             rescale_spatial_coords, scanpy_sizefactors, smooth_spatial_factors, train)
 
 
 def synthetic_counts(N, D, L, rng):
@@ -51,6 +51,9 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--inducing-from", "--inducing_from", choices=("subset", "kmeans"), default="subset",
                     help="inducing points: a random subset of the spots, or their k-means centres (kmeans_inducing_points)")
+    ap.add_argument("--mu-from", "--mu_from", choices=("smooth", "projection"), default="smooth",
+                    help="gp.mu: the kNN mean of the factors at Z (smooth_spatial_factors), or their kernel least-squares "
+                         "projection onto Z (project_factors_to_inducing, the notebooks' Kzx @ Kxz composition)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     rng = np.random.default_rng(0)
@@ -67,15 +70,25 @@ def main():
         Z = X[rng.choice(a.spots, M, replace=False)]
     U, beta0, beta = smooth_spatial_factors(F, Z, X)
     print(f"N={a.spots} D={a.genes} L={L} M={M}: F {F.shape} {F.dtype}, U {U.shape} {U.dtype}, trend {beta.shape}")
+    start = "NMF + smooth_spatial_factors"
+    if a.mu_from == "projection":
+        # the model's kernel; SVGP: un-whitened.  float64 coordinates select the fp64 Gram pass: inducing points drawn from
+        # the spots with a lengthscale above their spacing make K_zx K_xz nearly singular, and fp32 entries would move it
+        # by more than the 1e-5 jitter
+        mu, info = project_factors_to_inducing(NSF_RBF(sigma=1.0, lengthscale=0.4, L=L), np.asarray(Z, dtype=np.float64),
+                                               X.astype(np.float64), np.ascontiguousarray(F.T), return_info=True)
+        U, start = mu.T, "NMF + project_factors_to_inducing"
+        print(f"  projection: residual per factor {np.array2string(info['residual'], precision=3)}, "
+              f"diag(G) in [{info['gram_diag_min']:.3g}, {info['gram_diag_max']:.3g}]")
 
     Xd, Yd = torch.as_tensor(X, device=dev), torch.as_tensor(Y.T, device=dev)
-    for name, model in (("NMF + smooth_spatial_factors", model_for(X, Y, Z, L, dev, mu=U.T, W=W)),
+    for name, model in ((start, model_for(X, Y, Z, L, dev, mu=U.T, W=W)),
                         ("mu = 0, random loadings", model_for(X, Y, Z, L, dev))):
         with torch.no_grad():
             model.V.copy_(torch.as_tensor(init_softplus(sz[:, 0].astype(np.float64))))
         opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=1e-2)
         losses = train(model, opt, Xd, Yd, dev, steps=a.steps, E=3)
-        print(f"  {name:30s} loss {losses[0]:.4g} -> {losses[-1]:.4g}")
+        print(f"  {name:34s} loss {losses[0]:.4g} -> {losses[-1]:.4g}")
 
 
 if __name__ == "__main__":

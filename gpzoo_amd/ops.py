@@ -913,6 +913,65 @@ def kmeans_assign(X, C, labels=None, return_d2: bool = False):
     return (labels, inertia, d2) if return_d2 else (labels, inertia)
 
 
+def kernel_gram_plan(N: int, M: int, n_latent: int, dtype: torch.dtype) -> dict:
+    """How ``kernel_gram`` covers a shape (gpz_kernel_gram_plan, a host-only query: no device needed): ``tile`` (rows and
+    columns of an output tile), ``col_step`` (columns of X per step of a workgroup), ``n_splits`` and ``cols_per_split`` of
+    the N-splits (the last one may be shorter), ``workspace_bytes(R)`` of the call with R right-hand sides per latent."""
+    lib = _lib.load()
+    code = GPZ_F32 if dtype == torch.float32 else GPZ_F64
+    tile, step, splits, cols = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = lib.gpz_kernel_gram_plan(int(N), int(M), int(n_latent), code, C.byref(tile), C.byref(step), C.byref(splits),
+                                  C.byref(cols))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(tile=tile.value, col_step=step.value, n_splits=splits.value, cols_per_split=cols.value,
+                workspace_bytes=lambda R=1: int(lib.gpz_kernel_gram_workspace_bytes(int(N), int(M), int(n_latent), int(R), code)))
+
+
+GRAM_MAX_R = 64     # right-hand sides per latent one gpz_kernel_gram call takes
+
+
+@_on_device
+def kernel_gram(spec: KernelSpec, Z: torch.Tensor, X: torch.Tensor, F: torch.Tensor, jitter: float = 0.0):
+    """Normal equations of the kernel least-squares fit of F on the inducing points (gpz_kernel_gram): ``(G, b)`` fp64 with
+    G (n, M, M) = K_zx K_xz + jitter I and b (n, R, M) = K_zx F^T, K_zx = k(Z, X), in one pass over X without a stored
+    K_zx.  Z (M,d), X (N,d), F (L,N).  A per-latent kernel (``spec.batched``) pairs latent l with row l of F: n = L, R = 1;
+    a scalar-parameter kernel has one Gram matrix for all rows: n = 1, R = L (more than 64 rows are served 64 at a time).
+    fp32 Z, X and parameters generate and multiply the covariance entries in fp32 (the bits ``kfill`` writes) inside an
+    N-split; the splits are added in fp64 in a fixed order: repeated calls agree bit for bit."""
+    _need_cuda(Z, X, F, spec.sigma)
+    lib = _lib.load()
+    if Z.dim() != 2 or X.dim() != 2 or F.dim() != 2 or Z.shape[1] != X.shape[1] or F.shape[1] != X.shape[0]:
+        raise ValueError(f"kernel_gram: Z (M, d), X (N, d) and F (L, N) expected, got {tuple(Z.shape)}, {tuple(X.shape)} and "
+                         f"{tuple(F.shape)}")
+    ct = torch.float32 if Z.dtype == X.dtype == spec.sigma.dtype == spec.lengthscale.dtype == torch.float32 else torch.float64
+    Z = Z.detach().to(ct).contiguous()
+    X = X.detach().to(ct).contiguous()
+    F = F.detach().to(ct).contiguous()
+    (M, d), N, L = Z.shape, X.shape[0], F.shape[0]
+    if spec.batched and spec.L != L:
+        raise ValueError(f"kernel_gram: the kernel has parameters for {spec.L} latents, F has {L} rows")
+    n, R = (L, 1) if spec.batched else (1, L)
+    keep: list = []
+    desc = _desc(spec if spec.batched else KernelSpec(spec.kind, spec.sigma.reshape(-1)[:1], spec.lengthscale.reshape(-1)[:1], False),
+                 ct, keep)
+    G = torch.empty((n, M, M), dtype=torch.float64, device=Z.device)
+    b = torch.empty((n, R, M), dtype=torch.float64, device=Z.device)
+    for r0 in range(0, R, GRAM_MAX_R):
+        r = min(GRAM_MAX_R, R - r0)
+        nb = lib.gpz_kernel_gram_workspace_bytes(N, M, n, r, _dt(Z))
+        if nb == 0:
+            raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+        ws = _workspace(Z.device, nb)
+        bpart = b if r == R else torch.empty((n, r, M), dtype=torch.float64, device=Z.device)
+        rc = lib.gpz_kernel_gram(C.byref(desc), _ptr(Z), M, _ptr(X), N, d, _ptr(F[r0:r0 + r] if not spec.batched else F), r,
+                                 float(jitter), _ptr(G), _ptr(bpart), _ptr(ws), ws.numel(), _stream(Z.device))
+        _lib.check(rc, "gpz_kernel_gram")
+        if bpart is not b:
+            b[:, r0:r0 + r] = bpart
+    return G, b
+
+
 def _nmf_args(X, W, H, who: str):
     _need_cuda(X, W, H)
     if X.dim() != 2 or W.dim() != 2 or H.dim() != 2 or W.shape[0] != X.shape[0] or H.shape[1] != X.shape[1] or W.shape[1] != H.shape[0]:

@@ -701,6 +701,136 @@ def kmeans_inducing_points(X, M, *, init="k-means++", max_iter=300, tol=1e-4, ra
     return centres, info
 
 
+def project_factors_to_inducing(kernel, Z, X, F, *, jitter=1e-5, whitened=False, kzz_jitter=0.0, return_info=False):
+    """Start for ``gp.mu`` by kernel least squares: per latent ``alpha = (K_zx K_xz + jitter I)^-1 K_zx f``, so that
+    ``K_xz alpha ~ f``, and ``mu = K_zz alpha`` -- what Slideseqv2_estimate_lengthscales.ipynb (``build_model_scracth``:
+    ``L1 = cholesky(add_jitter(Kzx @ Kxz, 1e-5)); alpha = cholesky_solve(Kzx @ F, L1); mu = Kzz @ alpha``) and
+    NSF_Hybrid_benchmark.ipynb (``torch.pinverse(Kzx @ Kxz)``) compose by hand from a materialised ``kernel(Z, X)``.  Here
+    the Gram matrix and the right-hand sides come from one HIP pass over X (``ops.kernel_gram``, gpz_kernel_gram) that never
+    stores K_zx and adds in a fixed order; the factorisation (``ops.cholesky``) and the solves are fp64.
+
+    ``kernel``: ``RBF``, ``NSF_RBF``, ``batched_RBF``, ``batched_Matern12`` / ``32`` / ``52`` of this package (a multi-group
+    kernel or a user-defined ``covariance`` raises NotImplementedError).  Z (M,d), X (N,d), F (L,N): one row per latent, the
+    notebooks' ``factors.T[:L]``.  A kernel with per-latent parameters pairs latent l with row l (their counts must
+    agree); a scalar-parameter kernel has one Gram matrix, factored once, for all L rows.
+
+    Returns ``mu`` (L,M): ``whitened=False`` (for ``SVGP``) ``K_zz alpha`` with K_zz as the kernel gives it, without jitter,
+    as in the notebook; ``whitened=True`` (for ``WSVGP``) ``Lz^T alpha`` with ``Lz = chol(K_zz + kzz_jitter I)`` -- pass
+    ``gp.jitter``.  ``return_info=True`` adds a dict: ``alpha`` (L,M), ``gram_diag_min`` / ``gram_diag_max`` (floats, of
+    the factored matrix, jitter included) and ``residual`` (L,) = ||K_xz alpha - f||^2 / ||f||^2, evaluated without a second
+    pass over X as ``(f.f - 2 alpha.b + alpha.G alpha) / f.f`` in fp64 with the jitter taken out of G: a difference of
+    numbers near f.f, so a nearly exact fit (residual below about 1e-6 on the fp32 path, 1e-12 in fp64) loses its digits and
+    may come out slightly negative.
+
+    Precision: fp32 covariance entries (the bits ``kernel(Z, X)`` holds) and fp32 products inside one N-split when Z, X and
+    the kernel's parameters are all float32, fp64 otherwise; Gram matrix, right-hand side, factorisation and solves are
+    fp64 in both cases.  On the fp32 path an entry of the Gram matrix is good to about 1e-6 of its largest diagonal entry:
+    where K_zx K_xz is nearly singular (inducing points drawn from the spots, a lengthscale above their spacing) a jitter
+    below that cannot keep it positive definite -- pass float64 coordinates, which cost the fp64 rate of the one pass.
+    Repeated calls agree bit for bit.  Inputs are numpy arrays or torch tensors, host or CUDA; the
+    work runs on the GPU of the first CUDA argument, else on the current one.  ``mu`` and ``alpha`` are of F's kind (numpy,
+    or a tensor on F's device), float32 for float32 F, else float64.
+
+    ValueError, before anything touches a GPU: wrong ranks, row counts that differ, d outside 1..4, an L mismatch,
+    ``jitter < 0`` or ``kzz_jitter < 0``, N = 0 or M = 0, M > 8192, a non-finite value in a host input (a CUDA input is
+    checked by one device reduction before any launch).  torch.linalg.LinAlgError: ``K_zx K_xz + jitter I`` (or, whitened,
+    ``K_zz + kzz_jitter I``) is not positive definite."""
+    import numpy as np
+    from . import kernels as _k
+
+    who = "project_factors_to_inducing"
+    if isinstance(kernel, _k._MGGPMixin):
+        raise NotImplementedError(f"{who}: multi-group kernels ({type(kernel).__name__}) are not supported")
+    if not isinstance(kernel, _k._HipKernel):
+        raise TypeError(f"{who}: {type(kernel).__name__} is not a kernel of gpzoo.kernels")
+    kernel._check_covariance()
+
+    def as_tensor(a):
+        return a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+    f_is_tensor = isinstance(F, torch.Tensor)
+    Zt, Xt, Ft = as_tensor(Z), as_tensor(X), as_tensor(F)
+    for name, t, want in (("Z", Zt, "(M, d)"), ("X", Xt, "(N, d)"), ("F", Ft, "(L, N)")):
+        if t.dim() != 2:
+            raise ValueError(f"{who}: {name} must be {want}, got shape {tuple(t.shape)}")
+    (M, d), N, L = Zt.shape, Xt.shape[0], Ft.shape[0]
+    if Xt.shape[1] != d:
+        raise ValueError(f"{who}: X has {Xt.shape[1]} coordinates per point, Z {d}")
+    if not 1 <= d <= 4:
+        raise ValueError(f"{who}: coordinates of dimension {d} unsupported (1..4)")
+    if Ft.shape[1] != N:
+        raise ValueError(f"{who}: {N} rows of X but {Ft.shape[1]} columns of F")
+    if N < 1 or M < 1 or L < 1:
+        raise ValueError(f"{who}: nothing to project (N={N}, M={M}, L={L})")
+    if M > 8192 or N >= 2 ** 31:
+        raise ValueError(f"{who}: M={M}, N={N} unsupported (M <= 8192, N < 2**31)")
+    for name, v in (("jitter", jitter), ("kzz_jitter", kzz_jitter)):
+        if not (isinstance(v, (int, float, np.floating, np.integer)) and v >= 0):
+            raise ValueError(f"{who}: {name}={v!r} must be a number >= 0")
+    spec = kernel._spec()
+    if spec.batched and spec.L != L:
+        raise ValueError(f"{who}: the kernel has parameters for {spec.L} latents, F has {L} rows")
+    floats = [t if t.is_floating_point() else t.double() for t in (Zt, Xt, Ft, spec.sigma, spec.lengthscale)]
+    finite = [torch.isfinite(t).all() for t in floats]
+    host = [f for f in finite if not f.is_cuda]
+    if host and not bool(torch.stack(host).all()):
+        raise ValueError(f"{who}: Z, X, F or a kernel parameter holds a non-finite value")
+    dev_flags = [f for f in finite if f.is_cuda]
+
+    from . import ops
+    Zt, Xt, Ft, sig, ell = floats
+    dev = next((t.device for t in (Ft, Zt, Xt, sig) if t.is_cuda), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev_flags and not bool(torch.stack([f.to(dev) for f in dev_flags]).all()):
+        raise ValueError(f"{who}: Z, X, F or a kernel parameter holds a non-finite value")
+    ct = torch.float32 if all(t.dtype == torch.float32 for t in (Zt, Xt, sig, ell)) else torch.float64
+    out_dtype = torch.float32 if Ft.dtype == torch.float32 else torch.float64
+    Zd, Xd = Zt.to(device=dev, dtype=ct).contiguous(), Xt.to(device=dev, dtype=ct).contiguous()
+    Fd = Ft.to(device=dev, dtype=torch.float64).contiguous()
+    spec = ops.KernelSpec(spec.kind, sig.to(device=dev, dtype=ct).contiguous(), ell.to(device=dev, dtype=ct).contiguous(),
+                          spec.batched)
+
+    G, b = ops.kernel_gram(spec, Zd, Xd, Fd.to(ct), float(jitter))          # (n, M, M), (n, R, M) fp64
+    Lg = ops.cholesky(G)
+
+    def solve(Lc, rhs):          # (Lc Lc^T)^-1 rhs by two triangular solves; rhs (n, M, 1)
+        y = ops.solve_triangular_lower(Lc, rhs.contiguous())
+        return torch.linalg.solve_triangular(Lc.transpose(-1, -2), y, upper=True)[:, :, 0]
+
+    Kzz = ops.kfill(spec, Zd, Zd).double()                                    # (L, M, M) or (M, M)
+    if whitened:
+        eye = torch.eye(M, dtype=torch.float64, device=dev)
+        T = torch.tril(ops.cholesky(Kzz + float(kzz_jitter) * eye)).transpose(-1, -2)
+    else:
+        T = Kzz
+    if spec.batched:
+        alpha = solve(Lg, b.transpose(-1, -2))                                # (L, M)
+        mu = (T * alpha[:, None, :]).sum(-1)
+    else:
+        # one factorisation, then row by row: row l of a call with L rows is computed exactly as a call with that row alone
+        alpha = torch.cat([solve(Lg, b[:, l, :, None]) for l in range(L)])
+        mu = torch.stack([(T * alpha[l][None, :]).sum(-1) for l in range(L)])
+
+    def like_f(t):
+        t = t.to(out_dtype)
+        if not f_is_tensor:
+            return t.cpu().numpy()
+        return t if Ft.is_cuda else t.cpu()
+
+    if not return_info:
+        return like_f(mu)
+    diag = torch.diagonal(G, dim1=-2, dim2=-1)
+    ff = (Fd * Fd).sum(dim=1)
+    bL = b[:, 0, :] if spec.batched else b[0]                                 # (L, M)
+    Ga = (G @ alpha[:, :, None])[:, :, 0] if spec.batched else (G[0] @ alpha.t()).t()
+    quad = (alpha * Ga).sum(dim=1) - float(jitter) * (alpha * alpha).sum(dim=1)
+    residual = (ff - 2.0 * (alpha * bL).sum(dim=1) + quad) / ff
+    info = dict(alpha=like_f(alpha), gram_diag_min=float(diag.min()), gram_diag_max=float(diag.max()),
+                residual=like_f(residual))
+    return like_f(mu), info
+
+
 # Host-side data preparation of the reference's utilities module (AnnData conversion, plotting, ...) is outside the
 # accelerated path and not rebuilt here.  The names resolve so that
 # ``from gpzoo.utilities import train_hybrid, anndata_to_train_val`` -- the notebooks' import lines -- keep

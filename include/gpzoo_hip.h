@@ -29,7 +29,10 @@
  * gpz_knn_mean and gpz_knn_mean_workspace_bytes -- the exact K-nearest mean of the factors at the inducing points behind
  * smooth_spatial_factors (utilities.py:50-68, sklearn's KNeighborsRegressor.predict);
  * gpz_kmeans_seed, gpz_kmeans_lloyd, gpz_kmeans_assign and their *_workspace_bytes queries -- k-means++ seeding and Lloyd's
- * iterations behind kmeans_inducing_points (the notebooks' sklearn KMeans(n_clusters=M).fit(X).cluster_centers_ for Z).
+ * iterations behind kmeans_inducing_points (the notebooks' sklearn KMeans(n_clusters=M).fit(X).cluster_centers_ for Z);
+ * gpz_kernel_gram, gpz_kernel_gram_workspace_bytes and gpz_kernel_gram_plan -- the normal equations K_zx K_xz + jitter I and
+ * K_zx F^T of the kernel least-squares start for gp.mu behind project_factors_to_inducing (the notebooks' hand-written
+ * Kzx @ Kxz / cholesky_solve composition), in one pass over X without a stored K_zx.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -448,6 +451,34 @@ int gpz_kmeans_lloyd(const void* X, int64_t N, int32_t d, int32_t dtype, double*
 size_t gpz_kmeans_assign_workspace_bytes(int64_t N, int32_t d, int64_t M);
 int gpz_kmeans_assign(const void* X, int64_t N, int32_t d, int32_t dtype, const double* C, int64_t M, int32_t keep_labels,
                       int32_t* labels, double* d2_out, double* inertia_out, void* ws, size_t ws_bytes, void* stream);
+
+/* Normal equations of the kernel least-squares projection of factors onto the inducing points -- what
+ * Slideseqv2_estimate_lengthscales.ipynb (build_model_scracth: L1 = cholesky(add_jitter(Kzx @ Kxz, 1e-5)),
+ * alpha = cholesky_solve(Kzx @ F, L1), mu = Kzz @ alpha) and NSF_Hybrid_benchmark.ipynb (torch.pinverse(Kzx @ Kxz)) form
+ * from a materialised Kzx = kernel(Z, X):
+ *   G[l] = K_zx K_xz + jitter I   (n_latent, M, M) fp64, full symmetric (the upper triangle is the mirrored lower one),
+ *   b[l] = K_zx F[l]^T            (n_latent, R, M) fp64,        K_zx = k_l(Z, X),
+ * in ONE pass over X: neither K_zx nor an N-sized piece of it is written to memory.  k: kinds GPZ_KERNEL_RBF, _MATERN32,
+ * _MATERN12, _MATERN52 (anything else is refused); Z (M,d), X (N,d) and F (n_latent, R, N) of k->dtype, R right-hand sides
+ * per latent (a scalar-parameter kernel passes n_latent = 1 and its L factor rows as R).  Limits, argument errors on the
+ * host before any launch: 1 <= d <= 4, 1 <= R <= 64, 1 <= N < 2^31, 1 <= M <= 8192, n_latent <= 65535, jitter >= 0.
+ * Arithmetic: k->dtype = GPZ_F32 generates the covariance entries in fp32 -- the bits gpz_kfill writes -- and multiplies
+ * and adds them in fp32 (v_mfma_f32_16x16x4_f32) inside one N-split of at most 16 384 columns; GPZ_F64 does both in fp64
+ * (v_mfma_f64_16x16x4_f64).  The splits' partial sums are added in ascending split order in fp64 in both cases.  No
+ * floating-point atomics, no kernel waits on another workgroup (one plain grid and one reduction launch): two calls on
+ * the same input agree bit for bit.
+ * gpz_kernel_gram_plan (host only, no device needed): tile = rows and columns of an output tile (128), col_step = columns
+ * of X one step of a workgroup covers (32 fp32, 16 fp64), n_splits and cols_per_split (a multiple of col_step, at least
+ * 4 col_step; the last split may be shorter): n_splits = ceil(N / cols_per_split), chosen so that a split has at most
+ * 16 384 columns and the launch at least 512 workgroups where N allows.  Any out pointer may be NULL.
+ * Workspace: the splits' partial tiles only, n_splits x n_latent x (nt (nt + 1) / 2 x 128 x 128 + nt x RB x 128) values
+ * of k->dtype, nt = ceil(M / 128), RB = 16 for R <= 16 else 64 (plus alignment): for a fixed number of splits it does not
+ * depend on N, and from M = 1024 on it is smaller than n_splits x sizeof(G).  The query returns 0 for a refused shape. */
+int gpz_kernel_gram_plan(int64_t N, int64_t M, int32_t n_latent, int32_t dtype, int32_t* tile, int32_t* col_step,
+                         int32_t* n_splits, int64_t* cols_per_split);
+size_t gpz_kernel_gram_workspace_bytes(int64_t N, int64_t M, int32_t n_latent, int32_t R, int32_t dtype);
+int gpz_kernel_gram(const gpz_kernel_desc* k, const void* Z, int64_t M, const void* X, int64_t N, int32_t d, const void* F,
+                    int32_t R, double jitter, double* G, double* b, void* ws, size_t ws_bytes, void* stream);
 
 /* Multi-GPU: latent GPs shard across ranks with no data-path collective; the only exchange is
  * the sum of each rank's partial ELBO -- one ncclAllReduce(sum, fp64) over RCCL/xGMI.  The reference has no
