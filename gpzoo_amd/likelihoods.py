@@ -80,10 +80,218 @@ class _PoissonLogLik(torch.autograd.Function):
         return g * dmean, g * dscale, g * dW, g * dV, None, None, None
 
 
+class SparseCounts:
+    """A (D genes, N spots) count matrix held as its non-zeros, in the two orders gpz_poisson_nsf_sparse reads: by spot
+    (``col_ptr`` int64 (N+1), ``col_gene`` int32, ``col_val`` fp32) and by gene (``row_ptr`` int64 (D+1), ``row_spot`` int32,
+    ``row_perm`` int32 = position of the same non-zero in the by-spot order).  Built once with torch sorts (stable, so the
+    order is fixed); explicit zeros are dropped and duplicate entries summed.
+
+    ``y`` may be a dense (D, N) tensor, a torch sparse tensor (COO, CSR or CSC layout), or any object with ``indptr``,
+    ``indices``, ``data``, ``shape`` and ``format in ('csr', 'csc')`` -- what ``adata.X`` is (scipy is not imported).
+
+    ``y[:, idx]`` with a 1-D integer tensor of DISTINCT spots is a light view (this object + ``idx`` + its inverse ``pos``):
+    no counts are copied.  It is the expression the mini-batch training loops evaluate, so they, ``train`` and
+    ``train_hybrid`` take a ``SparseCounts`` where they take a dense ``y`` (``fused=True``, the default).  Spots out of
+    range or listed twice raise IndexError: at the end of an enclosing ``ops.deferred_info()`` block (the training loops'
+    steps; the kernel meanwhile reads clamped indices, never out of bounds), otherwise at once, which reads one flag from
+    the device.  Any other index form raises TypeError."""
+
+    def __init__(self, y):
+        self.base, self.idx, self.pos = self, None, None
+        gene, spot, val, (D, N) = _coo_triplets(y)
+        D, N = int(D), int(N)
+        if D < 1 or N < 1:
+            raise ValueError(f"SparseCounts: a (genes, spots) matrix expected, got shape {(D, N)}")
+        gene, spot = gene.to(torch.int64).reshape(-1), spot.to(torch.int64).reshape(-1)
+        val = val.reshape(-1)
+        if gene.numel() != spot.numel() or gene.numel() != val.numel():
+            raise ValueError("SparseCounts: index and value arrays of different lengths")
+        if gene.numel() and (int(gene.min()) < 0 or int(gene.max()) >= D or int(spot.min()) < 0 or int(spot.max()) >= N):
+            raise IndexError(f"SparseCounts: an index lies outside the shape {(D, N)}")
+        # by spot, genes ascending inside a spot; duplicates (equal keys, adjacent after the sort) are summed in fp64 in
+        # their stored order, then zeros are dropped
+        key, order = torch.sort(spot * D + gene, stable=True)
+        v = val[order].to(torch.float64)
+        if key.numel():
+            last = torch.ones_like(key, dtype=torch.bool)
+            last[:-1] = key[1:] != key[:-1]
+            csum = torch.cumsum(v, 0)[last]
+            v = torch.diff(csum, prepend=csum.new_zeros(1))
+            key = key[last]
+        keep = v != 0
+        key, v = key[keep], v[keep]
+        spot, gene = torch.div(key, D, rounding_mode="floor"), key % D
+        if key.numel() >= 2 ** 31:
+            raise ValueError("SparseCounts: 2^31 or more non-zeros")
+        self.shape = (D, N)
+        self.col_val = v.to(torch.float32).contiguous()
+        self.col_gene = gene.to(torch.int32).contiguous()
+        self.col_ptr = _offsets(spot, N)
+        perm = torch.sort(gene, stable=True).indices          # by gene, spots ascending inside a gene
+        self.row_perm = perm.to(torch.int32).contiguous()
+        self.row_spot = spot[perm].to(torch.int32).contiguous()
+        self.row_ptr = _offsets(gene, D)
+
+    _PARTS = ("col_ptr", "col_gene", "col_val", "row_ptr", "row_spot", "row_perm")
+
+    @property
+    def device(self):
+        return self.base.col_val.device
+
+    @property
+    def nnz(self) -> int:
+        """Stored non-zeros; of a view, those of its spots (read from the device)."""
+        if self.base is self:
+            return int(self.col_val.numel())
+        cp = self.base.col_ptr
+        return int((cp[self.idx.long() + 1] - cp[self.idx.long()]).sum())
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device == self.device:
+            return self
+        out = object.__new__(SparseCounts)
+        if self.base is self:
+            out.base, out.idx, out.pos, out.shape = out, None, None, self.shape
+            for k in self._PARTS:
+                setattr(out, k, getattr(self, k).to(device))
+        else:
+            out.base, out.idx, out.pos, out.shape = self.base.to(device), self.idx.to(device), self.pos.to(device), self.shape
+        return out
+
+    def cuda(self, device=None):
+        return self.to(torch.device("cuda") if device is None else device)
+
+    def cpu(self):
+        return self.to("cpu")
+
+    def _spots(self):
+        """The spot of every stored value, in the by-spot order."""
+        b = self.base
+        return torch.repeat_interleave(torch.arange(b.shape[1], device=self.device), torch.diff(b.col_ptr))
+
+    def to_dense(self):
+        b = self.base
+        out = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+        gene, col, val = b.col_gene.long(), b._spots(), b.col_val
+        if b is not self:
+            col = self.pos.long()[col]
+            inside = col >= 0
+            gene, col, val = gene[inside], col[inside], val[inside]
+        out[gene, col] = val
+        return out
+
+    def __getitem__(self, key):
+        if not (isinstance(key, tuple) and len(key) == 2 and isinstance(key[0], slice) and key[0] == slice(None)
+                and isinstance(key[1], torch.Tensor) and key[1].dim() == 1
+                and key[1].dtype in (torch.int32, torch.int64)):
+            raise TypeError("SparseCounts supports y[:, idx] with a 1-D integer tensor of distinct spots only "
+                            "(y.to_dense() gives the array)")
+        if self.base is not self:
+            raise TypeError("SparseCounts: y[:, idx] of a view; index the SparseCounts itself")
+        N = self.shape[1]
+        want = key[1].to(device=self.device, dtype=torch.int64)
+        B = int(want.numel())
+        if B < 1 or B > N:
+            raise IndexError(f"SparseCounts: {B} distinct spots out of {N}")
+        want = torch.where(want < 0, want + N, want)              # negative indices count from the end, as for a tensor
+        idx = want.clamp(0, N - 1)
+        ar = torch.arange(B, dtype=torch.int32, device=self.device)
+        pos = torch.full((N,), -1, dtype=torch.int32, device=self.device)
+        pos[idx] = ar
+        ok = (idx == want).all() & (pos[idx] == ar).all()
+
+        def fail():
+            raise IndexError(f"SparseCounts: y[:, idx] needs distinct spots in [0, {N}): an index is out of range or repeated")
+        from .ops import _deferring
+        d = _deferring()
+        if d is not None:
+            d.add_flag(ok, fail)
+        elif not bool(ok):
+            fail()
+        out = object.__new__(SparseCounts)
+        out.base, out.idx, out.pos, out.shape = self, idx.to(torch.int32), pos, (self.shape[0], B)
+        return out
+
+    def __repr__(self):
+        return f"SparseCounts(shape={tuple(self.shape)}, device={self.device}{'' if self.base is self else ', view'})"
+
+
+def _offsets(sorted_ids, n):
+    """(n + 1,) int64 start offsets of the runs of an ascending id array."""
+    out = torch.zeros(n + 1, dtype=torch.int64, device=sorted_ids.device)
+    if sorted_ids.numel():
+        out[1:] = torch.cumsum(torch.bincount(sorted_ids, minlength=n), 0)
+    return out
+
+
+def _expand_ptr(ptr, n):
+    ptr = ptr.to(torch.int64)
+    return torch.repeat_interleave(torch.arange(n, device=ptr.device), torch.diff(ptr))
+
+
+def _coo_triplets(y):
+    """(gene, spot, value, shape) of whatever SparseCounts accepts; duplicates and zeros still in."""
+    if isinstance(y, SparseCounts):
+        b = y.base
+        if b is not y:
+            raise TypeError("SparseCounts: built from a view; use y.to_dense() or the parent")
+        return b.col_gene, b._spots(), b.col_val, b.shape
+    if isinstance(y, torch.Tensor):
+        y = y.detach()
+        if y.dim() != 2:
+            raise ValueError(f"SparseCounts: a (genes, spots) matrix expected, got {y.dim()} dimensions")
+        if y.layout == torch.strided:
+            gene, spot = torch.nonzero(y, as_tuple=True)
+            return gene, spot, y[gene, spot], y.shape
+        if y.layout == torch.sparse_coo:
+            ind = y._indices()
+            return ind[0], ind[1], y._values(), y.shape
+        if y.layout == torch.sparse_csr:
+            return _expand_ptr(y.crow_indices(), y.shape[0]), y.col_indices(), y.values(), y.shape
+        if y.layout == torch.sparse_csc:
+            return y.row_indices(), _expand_ptr(y.ccol_indices(), y.shape[1]), y.values(), y.shape
+        raise TypeError(f"SparseCounts: tensor layout {y.layout} unsupported (strided, COO, CSR, CSC)")
+    fmt = getattr(y, "format", None)
+    if fmt in ("csr", "csc") and all(hasattr(y, k) for k in ("indptr", "indices", "data", "shape")):
+        indptr, indices, data = (torch.as_tensor(getattr(y, k)) for k in ("indptr", "indices", "data"))
+        D, N = y.shape
+        if indptr.numel() != (D if fmt == "csr" else N) + 1:
+            raise ValueError(f"SparseCounts: indptr of {indptr.numel()} entries for a {fmt} matrix of shape {(D, N)}")
+        major = _expand_ptr(indptr, D if fmt == "csr" else N)
+        return (major, indices, data, (D, N)) if fmt == "csr" else (indices, major, data, (D, N))
+    raise TypeError(f"SparseCounts: cannot read counts from {type(y).__name__} (a dense or sparse torch tensor, or an "
+                    "object with indptr, indices, data, shape and format 'csr' / 'csc')")
+
+
+class _SparsePoissonLogLik(torch.autograd.Function):
+    """_PoissonLogLik for a SparseCounts (or its view y[:, idx]) through gpz_poisson_nsf_sparse."""
+
+    @staticmethod
+    def forward(ctx, mean, scale, W_pos, V_pos, eps, y, with_lgamma):
+        from . import ops
+        ll, dmean, dscale, dW, dV = ops.poisson_nsf_sparse(mean, scale, eps, W_pos, V_pos, y, None, with_lgamma)
+        ctx.save_for_backward(dmean.to(mean.dtype), dscale.to(scale.dtype), dW.to(W_pos.dtype), dV.to(V_pos.dtype))
+        return ll.to(mean.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        dmean, dscale, dW, dV = ctx.saved_tensors
+        return g * dmean, g * dscale, g * dW, g * dV, None, None, None
+
+
+def _loglik_function(y):
+    """The autograd function of the fused Poisson step for this form of the counts: the caller chooses by what they pass."""
+    return _SparsePoissonLogLik if isinstance(y, SparseCounts) else _PoissonLogLik
+
+
 def poisson_expected_loglik(qF_list, W_list, V_pos, y, E=10, with_lgamma=True, eps=None):
     """Fused Monte-Carlo E_q[log p(y | F)] for rate = V * sum_k W_k exp(F_k), F_k ~ qF_k.
 
-    qF_list: Normal distributions over (L_k, N) factors; W_list: positive (D, L_k) loadings."""
+    qF_list: Normal distributions over (L_k, N) factors; W_list: positive (D, L_k) loadings; y: the (D, N) counts, dense
+    (gpz_poisson_nsf) or a ``SparseCounts`` / its view ``y[:, idx]`` (gpz_poisson_nsf_sparse)."""
     mean = torch.cat([q.mean for q in qF_list], dim=0)
     scale = torch.cat([q.scale for q in qF_list], dim=0)
     W = torch.cat(list(W_list), dim=1)
@@ -91,7 +299,7 @@ def poisson_expected_loglik(qF_list, W_list, V_pos, y, E=10, with_lgamma=True, e
         import torch.distributions.normal as tdn
         eps = torch.cat([tdn._standard_normal((E,) + tuple(q.mean.shape), dtype=mean.dtype, device=mean.device)
                          for q in qF_list], dim=1)
-    return _PoissonLogLik.apply(mean, scale, W, V_pos, eps, y, with_lgamma)
+    return _loglik_function(y).apply(mean, scale, W, V_pos, eps, y, with_lgamma)
 
 
 class PoissonFactorization(nn.Module):
@@ -276,8 +484,8 @@ class Hybrid_NSF_Exact(Hybrid_NSF2):
         sp = torch.nn.functional.softplus
         m = torch.cat([qF1.mean + 0.5 * qF1.scale ** 2, qF2.mean + 0.5 * qF2.scale ** 2], dim=0)
         zero = torch.zeros_like(m)
-        ll = _PoissonLogLik.apply(m, zero, torch.cat([sp(self.sf.W), sp(self.cf.W)], dim=1), sp(V), zero[None], y,
-                                  with_lgamma)
+        ll = _loglik_function(y).apply(m, zero, torch.cat([sp(self.sf.W), sp(self.cf.W)], dim=1), sp(V), zero[None], y,
+                                       with_lgamma)
         return ll / y.shape[0], qF1, qU, pU, qF2, pF2
 
 

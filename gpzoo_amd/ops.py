@@ -1176,6 +1176,71 @@ def poisson_nsf(mean, scale, eps, W_pos, V_pos, y, with_lgamma: bool = True):
     return (total, *acc)
 
 
+def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
+    """How ``poisson_nsf_sparse`` covers a shape (gpz_poisson_nsf_sparse_plan, a host-only query: no device needed):
+    ``gene_chunk`` (non-zeros of a gene row per wave of the gene pass), ``spot_chunk`` (the same for a spot's column; 0:
+    columns are not split), ``n_gene_chunks`` (length of the gene pass's work list), ``samples_per_group`` (samples the spot
+    pass holds on chip at a time), ``factors_padded`` (Lt rounded up to the kernel instance), ``workspace_bytes``."""
+    lib = _lib.load()
+    gc, sc, spg, fp, nch = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = lib.gpz_poisson_nsf_sparse_plan(int(N), int(B), int(D), int(Lt), int(E), int(nnz), C.byref(gc), C.byref(sc),
+                                         C.byref(nch), C.byref(spg), C.byref(fp))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, spot_chunk=sc.value, n_gene_chunks=nch.value, samples_per_group=spg.value,
+                factors_padded=fp.value,
+                workspace_bytes=int(lib.gpz_poisson_nsf_sparse_workspace_bytes(int(N), int(B), int(D), int(nnz), int(Lt), int(E))))
+
+
+@_on_device
+def poisson_nsf_sparse(mean, scale, eps, W_pos, V_pos, counts, idx=None, with_lgamma: bool = True):
+    """``poisson_nsf`` for counts held as their non-zeros (gpz_poisson_nsf_sparse): the same 5-tuple
+    (loglik fp64 scalar, dmean, dscale, dW, dV), as exact sums over the non-zeros -- O(nnz E Lt + E Lt B + D Lt) work.
+
+    counts: a ``likelihoods.SparseCounts`` (D, N), or the view ``counts[:, idx]`` of one.  mean, scale (Lt,B); eps (E,Lt,B);
+    W_pos (D,Lt); V_pos (B,) with B = N, or B = len(idx) for a view.  ``idx``: shorthand for ``counts[:, idx]``.
+    Any number of samples goes through one call.  Nothing here waits for the device: the call can be captured in a graph."""
+    from .likelihoods import SparseCounts
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"poisson_nsf_sparse: counts must be a SparseCounts, got {type(counts).__name__}")
+    if idx is not None:
+        counts = counts[:, idx]
+    _need_cuda(mean, scale, eps, W_pos, V_pos)
+    dev = mean.device
+    if counts.device != dev:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {counts.device}, the model on {dev}: move them with counts.to(device)")
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale = mean.detach().to(f32).contiguous(), scale.detach().to(f32).contiguous()
+    eps = eps.detach().to(f32).contiguous()
+    W_pos, V_pos = W_pos.detach().to(f32).contiguous(), V_pos.detach().to(f32).contiguous()
+    if W_pos.data_ptr() % 16:
+        W_pos = W_pos.clone()            # the entry reads rows of W 16 bytes at a time (include/gpzoo_hip.h)
+    base = counts.base
+    D, N = base.shape
+    Lt, B = mean.shape
+    E = eps.shape[0]
+    if counts.shape != (W_pos.shape[0], B) or scale.shape != (Lt, B) or eps.shape != (E, Lt, B) or \
+            W_pos.shape != (D, Lt) or V_pos.shape != (B,):
+        raise ValueError(f"poisson_nsf_sparse: counts {tuple(counts.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, "
+                         f"eps {tuple(eps.shape)}, W {tuple(W_pos.shape)}, V {tuple(V_pos.shape)} do not fit together")
+    ll = torch.empty(2, dtype=torch.float64, device=dev)
+    dmean, dscale = torch.empty((Lt, B), dtype=f32, device=dev), torch.empty((Lt, B), dtype=f32, device=dev)
+    dW, dV = torch.empty((D, Lt), dtype=f32, device=dev), torch.empty((B,), dtype=f32, device=dev)
+    nbytes = lib.gpz_poisson_nsf_sparse_workspace_bytes(N, B, D, base.nnz, Lt, E)
+    if nbytes == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ws = _workspace(dev, nbytes)
+    rc = lib.gpz_poisson_nsf_sparse(_ptr(mean), _ptr(scale), _ptr(eps), _ptr(W_pos), _ptr(V_pos), _ptr(base.col_ptr),
+                                    _ptr(base.col_gene), _ptr(base.col_val), _ptr(base.row_ptr), _ptr(base.row_spot),
+                                    _ptr(base.row_perm), _ptr(counts.idx), _ptr(counts.pos), N, B, D, base.nnz, Lt, E,
+                                    int(with_lgamma), _ptr(ll), _ptr(dmean), _ptr(dscale), _ptr(dW), _ptr(dV), _ptr(ws),
+                                    ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_poisson_nsf_sparse")
+    total = ll[0] - ll[1] if with_lgamma else ll[0].clone()
+    return total, dmean, dscale, dW, dV
+
+
 def profile_enable(on: bool = True):
     _lib.check(_lib.load().gpz_profile_enable(int(on)), "gpz_profile_enable")
 

@@ -99,6 +99,14 @@ def _spots(X, batch_size):
     return torch.multinomial(torch.ones(X.shape[0], device=X.device), num_samples=batch_size, replacement=False)
 
 
+def _fused_counts_only(model, y, fused):
+    """A SparseCounts has no (E,D,N) form: only the fused step takes it."""
+    from .likelihoods import SparseCounts
+    if isinstance(y, SparseCounts) and not (fused and hasattr(model, "expected_loglik")):
+        raise TypeError("SparseCounts go through the fused Poisson step only: pass fused=True to a model with "
+                        "expected_loglik (pY.log_prob(y) needs the dense array, y.to_dense())")
+
+
 class GraphedStep:
     """One optimisation step -- ``loss = loss_fn(); loss.backward(); optimizer.step()`` -- captured ONCE as a HIP graph
     and replayed: at the notebooks' sizes (N ~ 1e3, M ~ 1e2) an eager step is a hundred launches of a few microseconds
@@ -179,6 +187,7 @@ def train(model, optimizer, X, y, device=None, steps=200, E=20, fused=True, sync
     ``graph``: the step is captured once as a HIP graph and replayed (``GraphedStep``: same objective, same updates;
     the optimiser is switched to ``capturable``; errors surface after the failing step's update instead of before)."""
     from .ops import deferred_info
+    _fused_counts_only(model, y, fused)
     losses = []
     if graph and steps > 0:
         def loss_fn():
@@ -226,6 +235,7 @@ def train_batched(model, optimizer, X, y, device=None, steps=200, E=20, batch_si
     materialised).  The index draw stays on the device (the reference samples on the host every step).
     Models without ``forward_batched`` (plain GP likelihoods) get ``model(X[idx])`` on the sampled spots."""
     from .ops import deferred_info
+    _fused_counts_only(model, y, fused)
     losses = []
     for _ in range(steps):
         idx = _spots(X, min(batch_size, X.shape[0]))
@@ -254,6 +264,7 @@ def train_hybrid(model, optimizer, X, y, device=None, steps=200, E=20, fused=Tru
     """Full-batch driver of the hybrid (spatial + non-spatial) models, reference utilities.py:530-558."""
     from torch import distributions
     from .ops import deferred_info
+    _fused_counts_only(model, y, fused)
     losses = []
     for _ in range(steps):
         optimizer.zero_grad()
@@ -276,6 +287,7 @@ def train_hybrid_batched(model, optimizer, X, y, device=None, steps=200, E=20, b
     ``y log(rate) - rate`` (no log y! term), both KL terms are subtracted, W / W2 are clamped at zero."""
     from torch import distributions
     from .ops import deferred_info
+    _fused_counts_only(model, y, fused)
     losses = []
     for _ in range(steps):
         idx = _spots(X, batch_size)

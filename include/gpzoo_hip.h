@@ -32,7 +32,9 @@
  * iterations behind kmeans_inducing_points (the notebooks' sklearn KMeans(n_clusters=M).fit(X).cluster_centers_ for Z);
  * gpz_kernel_gram, gpz_kernel_gram_workspace_bytes and gpz_kernel_gram_plan -- the normal equations K_zx K_xz + jitter I and
  * K_zx F^T of the kernel least-squares start for gp.mu behind project_factors_to_inducing (the notebooks' hand-written
- * Kzx @ Kxz / cholesky_solve composition), in one pass over X without a stored K_zx.
+ * Kzx @ Kxz / cholesky_solve composition), in one pass over X without a stored K_zx;
+ * gpz_poisson_nsf_sparse, gpz_poisson_nsf_sparse_workspace_bytes and gpz_poisson_nsf_sparse_plan -- gpz_poisson_nsf for
+ * counts stored as their non-zeros: the same outputs as exact sums over the non-zeros.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -283,6 +285,39 @@ int gpz_poisson_nsf(const float* mean, const float* scale, const float* eps, con
                     const float* V, const float* y, int64_t N, int64_t D, int32_t Lt, int32_t E,
                     int32_t with_lgamma, double* loglik, float* dmean, float* dscale, float* dW,
                     float* dV, void* ws, size_t ws_bytes, void* stream);
+
+/* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
+ * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
+ * loglik and the four gradients are exact sums over the non-zeros plus O(E Lt B + D Lt) dense terms: the same numbers as
+ * gpz_poisson_nsf on the dense array, for nnz E Lt work.  No array of D x B or D x N elements exists, workspace included.
+ * Counts of the WHOLE data set (D genes x N spots, nnz stored values) in two orders:
+ *   by spot: col_ptr int64 (N + 1), col_gene int32 (nnz), col_val fp32 (nnz) -- spot n owns [col_ptr[n], col_ptr[n + 1]);
+ *   by gene: row_ptr int64 (D + 1), row_spot int32 (nnz), row_perm int32 (nnz) = position of the same non-zero in the
+ *            by-spot order (its value is col_val[row_perm[p]]).
+ * Stored zeros contribute nothing (0 log(.) is never formed).  The arrays are trusted: indices in range, the two orders
+ * consistent (gpzoo_amd.likelihoods.SparseCounts builds and checks them).
+ * Batch: idx int32 (B,) = the global spot of each batch column, DISTINCT spots, and pos int32 (N,) = its inverse, -1 outside
+ * the batch.  Both NULL: B == N and the identity.  mean, scale (Lt, B), eps (E, Lt, B), V (B,) are the batch's; W (D, Lt).
+ * Outputs as gpz_poisson_nsf: loglik[2] fp64, dmean, dscale (Lt, B), dW (D, Lt), dV (B,), the mean over E applied.
+ * 1 <= Lt <= 64; any E >= 1 (the kernels loop over the samples); N, D, nnz < 2^31.  W and ws must be 16-byte aligned.
+ * Argument errors (null pointers, extents, Lt, a small workspace, alignment) return -1 before any launch.
+ * No floating-point atomics, no workgroup waits on another, every sum in a fixed order: two calls agree bit for bit.
+ * gpz_poisson_nsf_sparse_plan (host only, no device needed): gene_chunk = non-zeros of one gene row per wave of the gene
+ * pass (512; a longer row is cut into chunks whose partial sums are added in chunk order), spot_chunk = the same for a
+ * spot's column (0: columns are not split), n_gene_chunks = length of the gene pass's work list (D + nnz / gene_chunk, an
+ * upper bound of the chunks in use), samples_per_group = samples the spot pass holds on chip at a time (E when they all
+ * fit), factors_padded = Lt rounded up to the kernel instance.  Any out pointer may be NULL.
+ * The workspace query returns 0 for refused arguments. */
+int gpz_poisson_nsf_sparse_plan(int64_t N, int64_t B, int64_t D, int32_t Lt, int32_t E, int64_t nnz, int32_t* gene_chunk,
+                                int32_t* spot_chunk, int64_t* n_gene_chunks, int32_t* samples_per_group,
+                                int32_t* factors_padded);
+size_t gpz_poisson_nsf_sparse_workspace_bytes(int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t E);
+int gpz_poisson_nsf_sparse(const float* mean, const float* scale, const float* eps, const float* W, const float* V,
+                           const int64_t* col_ptr, const int32_t* col_gene, const float* col_val, const int64_t* row_ptr,
+                           const int32_t* row_spot, const int32_t* row_perm, const int32_t* idx, const int32_t* pos,
+                           int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t E, int32_t with_lgamma,
+                           double* loglik, float* dmean, float* dscale, float* dW, float* dV, void* ws, size_t ws_bytes,
+                           void* stream);
 
 /* K nearest rows of Z for every row of X, ascending by (Euclidean distance, index): the neighbour
  * bookkeeping of VNNGP, argsort(cdist(X, Z))[:, :K] (gp.py:31, 64).  idx (N,K) int64.  K <= 32. */
