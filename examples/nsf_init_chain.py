@@ -6,7 +6,12 @@
 on synthetic counts, against the same model started from mu = 0 and random loadings.
 
     PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30
-                                                   --inducing-from {subset,kmeans} --mu-from {smooth,projection}]
+                                                   --inducing-from {subset,kmeans} --mu-from {smooth,projection}
+                                                   --sparse-counts DENSITY]
+
+``--sparse-counts DENSITY`` thins the counts to about that fraction of non-zeros and runs the whole chain on them as a
+``SparseCounts``: the size factors and the NMF start from ``counts.T``, the fit from ``counts``.  The dense count array
+then never reaches the device.
 """
 import argparse
 
@@ -16,7 +21,7 @@ import torch.nn as nn
 
 from gpzoo.gp import SVGP
 from gpzoo.kernels import NSF_RBF
-from gpzoo.likelihoods import NSF2
+from gpzoo.likelihoods import NSF2, SparseCounts
 from gpzoo.utilities import (init_softplus, kmeans_inducing_points, project_factors_to_inducing, regularized_nmf,
                              rescale_spatial_coords, scanpy_sizefactors, smooth_spatial_factors, train)
 
@@ -36,7 +41,7 @@ def model_for(X, Y, Z, L, dev, mu=None, W=None):
     gp.mu = nn.Parameter(torch.zeros(L, len(Z)) if mu is None else torch.as_tensor(mu, dtype=torch.float32))
     gp.Lu = nn.Parameter(1e-2 * torch.eye(len(Z)).repeat(L, 1, 1))
     kernel.sigma.requires_grad_(False); kernel.lengthscale.requires_grad_(False)                 # as in the notebooks
-    model = NSF2(gp, torch.as_tensor(Y.T), L=L)
+    model = NSF2(gp, Y if isinstance(Y, SparseCounts) else torch.as_tensor(Y.T), L=L)       # only the shape (D, N) is read
     if W is not None:
         model.W = nn.Parameter(torch.as_tensor(init_softplus(W), dtype=torch.float32))           # softplus(model.W) = W
     return model.to(dev)
@@ -54,16 +59,26 @@ def main():
     ap.add_argument("--mu-from", "--mu_from", choices=("smooth", "projection"), default="smooth",
                     help="gp.mu: the kNN mean of the factors at Z (smooth_spatial_factors), or their kernel least-squares "
                          "projection onto Z (project_factors_to_inducing, the notebooks' Kzx @ Kxz composition)")
+    ap.add_argument("--sparse-counts", type=float, default=None, metavar="DENSITY",
+                    help="keep about this fraction of the counts as non-zeros and run the chain through SparseCounts")
     a = ap.parse_args()
     dev = torch.device("cuda")
     rng = np.random.default_rng(0)
     X, Y = synthetic_counts(a.spots, a.genes, a.factors, rng)
     L, M = a.factors, a.inducing
+    nmf_kw = dict(solver="mu", init="nndsvdar", beta_loss="kullback-leibler", max_iter=200, random_state=0)
 
     X = rescale_spatial_coords(X)                                                                # roughly (-2, 2)
-    sz = scanpy_sizefactors(Y)
-    F, W = regularized_nmf(torch.as_tensor(Y, device=dev), L, sz=sz, solver="mu", init="nndsvdar",
-                           beta_loss="kullback-leibler", max_iter=200, random_state=0)
+    if a.sparse_counts is not None:
+        Y = Y * (rng.random(Y.shape) < a.sparse_counts)
+        Y = SparseCounts(torch.as_tensor(Y.T)).to(dev)                                           # (D, N), non-zeros only
+        print(f"sparse counts: {Y.nnz} non-zeros, {Y.nnz / (a.spots * a.genes):.1%} of {a.genes} x {a.spots}")
+        sz = scanpy_sizefactors(Y.T)
+        sz = np.maximum(sz, sz[sz > 0].min())           # a spot thinned to nothing says nothing about its depth; log(sz) stays finite
+        F, W = regularized_nmf(Y.T, L, sz=sz, **nmf_kw)
+    else:
+        sz = scanpy_sizefactors(Y)
+        F, W = regularized_nmf(torch.as_tensor(Y, device=dev), L, sz=sz, **nmf_kw)
     if a.inducing_from == "kmeans":
         Z = kmeans_inducing_points(X, M, random_state=0)
     else:
@@ -81,7 +96,8 @@ def main():
         print(f"  projection: residual per factor {np.array2string(info['residual'], precision=3)}, "
               f"diag(G) in [{info['gram_diag_min']:.3g}, {info['gram_diag_max']:.3g}]")
 
-    Xd, Yd = torch.as_tensor(X, device=dev), torch.as_tensor(Y.T, device=dev)
+    Xd = torch.as_tensor(X, device=dev)
+    Yd = Y if isinstance(Y, SparseCounts) else torch.as_tensor(Y.T, device=dev)
     for name, model in ((start, model_for(X, Y, Z, L, dev, mu=U.T, W=W)),
                         ("mu = 0, random loadings", model_for(X, Y, Z, L, dev))):
         with torch.no_grad():

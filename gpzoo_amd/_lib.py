@@ -110,6 +110,16 @@ _SIGNATURES = {
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "gpz_nmf_kl_divergence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gpz_nmf_kl_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gpz_nmf_kl_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "gpz_nmf_kl_sparse_update": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gpz_nmf_kl_sparse_divergence": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gpz_counts_matmul_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "gpz_counts_matmul": (C.c_int, [C.c_void_p] * 8 + [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                                       C.c_size_t, C.c_void_p]),
     "gpz_knn_mean_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64]),
     "gpz_knn_mean": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -215,8 +215,69 @@ class SparseCounts:
         out.base, out.idx, out.pos, out.shape = self, idx.to(torch.int32), pos, (self.shape[0], B)
         return out
 
+    @property
+    def T(self):
+        """The (N spots, D genes) orientation of the same counts, a ``TransposedCounts``: what ``regularized_nmf`` and
+        ``scanpy_sizefactors`` take (obs x feat).  Nothing is copied.  Of a view ``y[:, idx]``: TypeError (the
+        factorisation is of the whole data set)."""
+        if self.base is not self:
+            raise TypeError("SparseCounts: .T of a view y[:, idx]; the NMF start is computed from the whole data set "
+                            "(take .T of the SparseCounts itself)")
+        return TransposedCounts(self)
+
     def __repr__(self):
         return f"SparseCounts(shape={tuple(self.shape)}, device={self.device}{'' if self.base is self else ', view'})"
+
+
+class TransposedCounts:
+    """``counts.T``: a ``SparseCounts`` (D genes, N spots) read as the (N, D) obs x feat matrix X[n, d] = counts[d, n].
+    Holds the counts object and the dtype (``torch.float32`` unless ``.double()``) a factorisation of it runs in; no
+    counts are copied.  ``.T`` gives the counts back."""
+
+    def __init__(self, counts, dtype=torch.float32):
+        if not isinstance(counts, SparseCounts) or counts.base is not counts:
+            raise TypeError("TransposedCounts: a whole SparseCounts expected (counts.T)")
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"TransposedCounts: dtype {dtype} unsupported (torch.float32, torch.float64)")
+        self.counts, self.dtype = counts, dtype
+
+    @property
+    def T(self):
+        return self.counts
+
+    @property
+    def shape(self):
+        return (self.counts.shape[1], self.counts.shape[0])
+
+    @property
+    def device(self):
+        return self.counts.device
+
+    @property
+    def nnz(self) -> int:
+        return self.counts.nnz
+
+    def to(self, device):
+        moved = self.counts.to(device)
+        return self if moved is self.counts else TransposedCounts(moved, self.dtype)
+
+    def cuda(self, device=None):
+        return self.to(torch.device("cuda") if device is None else device)
+
+    def cpu(self):
+        return self.to("cpu")
+
+    def double(self):
+        return self if self.dtype == torch.float64 else TransposedCounts(self.counts, torch.float64)
+
+    def float(self):
+        return self if self.dtype == torch.float32 else TransposedCounts(self.counts, torch.float32)
+
+    def to_dense(self):
+        return self.counts.to_dense().T.contiguous()
+
+    def __repr__(self):
+        return f"TransposedCounts(shape={self.shape}, dtype={self.dtype}, device={self.device})"
 
 
 def _offsets(sorted_ids, n):

@@ -7,6 +7,10 @@ tensor's device in fp64 by subspace iteration, and agree with sklearn's wherever
 the L-th singular value).  Nothing of size N or D travels to the host: the orthonormalisations are CholeskyQR2, whose
 only host work is on (L+10) x (L+10) matrices, and no GPU solver library is involved.  The two large products per pass
 (X Q and X^T Q) are ``torch.matmul``: this is a handful of iterations' worth of arithmetic, run once.
+
+X may also be the transposed view of a ``likelihoods.SparseCounts`` (``counts.T``, obs x feat): the two large products then
+go through ``ops.counts_matmul`` over the stored non-zeros and the mean is the fp64 sum of the stored values over N D;
+everything else runs as for a dense X on the small dense factors.  No dense or ``torch.sparse`` form of X is made.
 """
 from __future__ import annotations
 
@@ -33,26 +37,42 @@ def _orthonormalise(Y):
     return Y
 
 
+def _is_counts(X):
+    from .likelihoods import TransposedCounts
+    return isinstance(X, TransposedCounts)
+
+
+def _products(X):
+    """(Q -> X Q, Q -> X^T Q, Y -> Y^T X) in fp64 for a dense tensor or a ``TransposedCounts``."""
+    if _is_counts(X):
+        from . import ops
+        xtq = lambda Q: ops.counts_matmul(X, Q, transpose=True)
+        return (lambda Q: ops.counts_matmul(X, Q)), xtq, (lambda Y: xtq(Y).T)
+    A = X.to(torch.float64)
+    return (lambda Q: A @ Q), (lambda Q: A.T @ Q), (lambda Y: Y.T @ A)
+
+
 def leading_triplets(X, L, random_state=None, n_oversamples=10):
     """(U (N,L), S (L,), V (L,D)) fp64 on X's device: the L leading singular triplets of X by subspace iteration with
     sklearn's sizes (L + 10 columns; 7 passes when L < 0.1 min(N, D), else 4) from
-    ``RandomState(random_state).normal(size=(D, L + 10))``."""
-    A = X.to(torch.float64)
-    N, D = A.shape
+    ``RandomState(random_state).normal(size=(D, L + 10))``.  X: a dense tensor or a ``TransposedCounts``."""
+    xq, xtq, ytx = _products(X)
+    N, D = X.shape
+    device = X.device
     k = L + n_oversamples
     passes = 7 if L < 0.1 * min(N, D) else 4
     rng = np.random.RandomState(random_state) if not isinstance(random_state, np.random.RandomState) else random_state
-    Q = torch.as_tensor(rng.normal(size=(D, k)), dtype=torch.float64, device=A.device)
+    Q = torch.as_tensor(rng.normal(size=(D, k)), dtype=torch.float64, device=device)
     for _ in range(passes):
-        Q = _orthonormalise(A @ Q)           # (N, k)
-        Q = _orthonormalise(A.T @ Q)         # (D, k)
-    Y = _orthonormalise(A @ Q)               # (N, k') orthonormal basis of the leading left subspace
-    B = Y.T @ A                              # (k', D)
+        Q = _orthonormalise(xq(Q))           # (N, k)
+        Q = _orthonormalise(xtq(Q))          # (D, k)
+    Y = _orthonormalise(xq(Q))               # (N, k') orthonormal basis of the leading left subspace
+    B = ytx(Y)                               # (k', D)
     lam, E = np.linalg.eigh((B @ B.T).cpu().numpy())
     order = np.argsort(-lam)[:L]
     S = np.sqrt(np.clip(lam[order], 0.0, None))
-    E = torch.as_tensor(np.ascontiguousarray(E[:, order]), dtype=torch.float64, device=A.device)    # (k', <=L)
-    S_dev = torch.as_tensor(S, dtype=torch.float64, device=A.device)
+    E = torch.as_tensor(np.ascontiguousarray(E[:, order]), dtype=torch.float64, device=device)    # (k', <=L)
+    S_dev = torch.as_tensor(S, dtype=torch.float64, device=device)
     U = Y @ E
     V = (E.T @ B) / torch.where(S_dev > 0, S_dev, torch.ones_like(S_dev)).unsqueeze(1)
     if U.shape[1] < L:                       # X of rank below L: the missing triplets are zero
@@ -70,15 +90,17 @@ def _fill_zeros(M, values_for):
 
 
 def initialize_nmf(X, L, init=None, random_state=None, eps=1e-6):
-    """Starting ``(W0 (N,L), H0 (L,D))`` of an NMF of X (N,D) >= 0 (a float tensor on any device), of X's dtype and on
-    X's device, following sklearn's ``_initialize_nmf``: ``init`` one of 'random', 'nndsvd', 'nndsvda', 'nndsvdar' or
+    """Starting ``(W0 (N,L), H0 (L,D))`` of an NMF of X (N,D) >= 0 (a float tensor on any device, or ``counts.T`` of a
+    ``SparseCounts``, on a CUDA device for the NNDSVD family), of X's dtype and on X's device, following sklearn's
+    ``_initialize_nmf``: ``init`` one of 'random', 'nndsvd', 'nndsvda', 'nndsvdar' or
     None (= 'nndsvda' when L <= min(N, D), else 'random').  'random' and the random fill of 'nndsvdar' use numpy's
     ``RandomState(random_state)`` draw for draw like sklearn (H before W for 'random'; W's zeros in row-major order, then
     H's, from a fresh generator for the fill), so they reproduce sklearn's values wherever the zero patterns agree."""
     if init not in INITS:
         raise ValueError(f"initialize_nmf: init={init!r} unsupported (one of {INITS})")
-    if not isinstance(X, torch.Tensor) or X.dim() != 2 or not X.is_floating_point():
-        raise ValueError("initialize_nmf: X must be a 2-D floating-point tensor")
+    counts = _is_counts(X)
+    if not counts and (not isinstance(X, torch.Tensor) or X.dim() != 2 or not X.is_floating_point()):
+        raise ValueError("initialize_nmf: X must be a 2-D floating-point tensor or the .T of a SparseCounts")
     N, D = X.shape
     L = int(L)
     if L < 1:
@@ -88,7 +110,7 @@ def initialize_nmf(X, L, init=None, random_state=None, eps=1e-6):
     if init is None:
         init = "nndsvda" if L <= min(N, D) else "random"
     np_dtype = np.float32 if X.dtype == torch.float32 else np.float64
-    mean = float(X.to(torch.float64).mean())
+    mean = float(X.T.col_val.sum(dtype=torch.float64)) / (N * D) if counts else float(X.to(torch.float64).mean())
 
     if init == "random":
         avg = np.sqrt(np_dtype(mean) / L) if np_dtype is np.float32 else np.sqrt(mean / L)

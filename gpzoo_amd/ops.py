@@ -1017,31 +1017,151 @@ def nmf_kl_mu(X, W0, H0, max_iter: int = 200, tol: float = 1e-4):
     X = X.detach().contiguous()
     W, H = W0.detach().clone().contiguous(), H0.detach().clone().contiguous()
     lib, N, D, L, nb = _nmf_args(X, W, H, "nmf_kl_mu")
-    max_iter = int(max_iter)
 
     def update(k):
         ws = _workspace(X.device, nb)
         rc = lib.gpz_nmf_kl_update(_ptr(X), _ptr(W), _ptr(H), N, D, L, _dt(X), k, _ptr(ws), ws.numel(), _stream(X.device))
         _lib.check(rc, "gpz_nmf_kl_update")
 
+    out = torch.empty(1, dtype=torch.float64, device=X.device)
+    return W, H, _nmf_mu_loop(update, lambda: _nmf_divergence(lib, X, W, H, N, D, L, nb, out), int(max_iter), tol)
+
+
+def _nmf_mu_loop(update, divergence, max_iter: int, tol: float) -> int:
+    """sklearn's control flow around ``update(k)`` (k iterations in place) and ``divergence()`` (a float): the divergence
+    before the loop and after every 10th iteration; ``tol = 0``: ``max_iter`` iterations and no read-back.  Returns n_iter."""
     if max_iter < 1:
-        return W, H, 0
+        return 0
     if not tol > 0:
         update(max_iter)
-        return W, H, max_iter
-    out = torch.empty(1, dtype=torch.float64, device=X.device)
-    error_at_init = previous = _nmf_divergence(lib, X, W, H, N, D, L, nb, out)
+        return max_iter
+    error_at_init = previous = divergence()
     n_iter = 0
     while n_iter < max_iter:
         k = min(10, max_iter - n_iter)
         update(k)
         n_iter += k
         if n_iter % 10 == 0:
-            error = _nmf_divergence(lib, X, W, H, N, D, L, nb, out)
+            error = divergence()
             if (previous - error) / error_at_init < tol:
                 break
             previous = error
-    return W, H, n_iter
+    return n_iter
+
+
+def _whole_counts(counts, who: str):
+    """The ``SparseCounts`` behind ``counts`` (itself or its ``.T``); views ``y[:, idx]`` are refused."""
+    from .likelihoods import SparseCounts, TransposedCounts
+    if isinstance(counts, TransposedCounts):
+        counts = counts.T
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"{who}: counts must be a SparseCounts or its .T, got {type(counts).__name__}")
+    if counts.base is not counts:
+        raise TypeError(f"{who}: counts is a view y[:, idx]; the whole SparseCounts is needed")
+    return counts
+
+
+def _count_ptrs(c):
+    return [_ptr(getattr(c, k)) for k in c._PARTS]
+
+
+def _nmf_sparse_args(counts, W, H, who: str):
+    c = _whole_counts(counts, who)
+    _need_cuda(W, H)
+    if c.device != W.device:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {c.device}, the factors on {W.device}: move them with counts.to(device)")
+    D, N = c.shape
+    if W.dim() != 2 or H.dim() != 2 or W.shape[0] != N or H.shape[1] != D or W.shape[1] != H.shape[0]:
+        raise ValueError(f"{who}: counts (D, N) with W (N, L) and H (L, D) expected, got {tuple(c.shape)}, {tuple(W.shape)} and "
+                         f"{tuple(H.shape)}")
+    if W.dtype != H.dtype:
+        raise TypeError(f"{who}: W and H must share one dtype, got {W.dtype} and {H.dtype}")
+    lib = _lib.load()
+    L = W.shape[1]
+    nb = lib.gpz_nmf_kl_sparse_workspace_bytes(N, D, c.nnz, L, _dt(W))
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return lib, c, N, D, L, nb
+
+
+def _nmf_sparse_divergence(lib, c, W, H, N, D, L, nb, out):
+    ws = _workspace(W.device, nb)
+    rc = lib.gpz_nmf_kl_sparse_divergence(*_count_ptrs(c), _ptr(W), _ptr(H), N, D, c.nnz, L, _dt(W), _ptr(out), _ptr(ws),
+                                          ws.numel(), _stream(W.device))
+    _lib.check(rc, "gpz_nmf_kl_sparse_divergence")
+    return float(out.item())
+
+
+@_on_device
+def nmf_kl_divergence_sparse(counts, W, H) -> float:
+    """``nmf_kl_divergence`` of X (N, D) = counts^T for counts held as their non-zeros (gpz_nmf_kl_sparse_divergence):
+    ``counts`` is a ``likelihoods.SparseCounts`` (D genes, N spots) or its ``.T``, W (N, L), H (L, D) fp32 or fp64 on the
+    counts' device.  Summed in fp64 in a fixed order over the by-spot order."""
+    W, H = W.detach().contiguous(), H.detach().contiguous()
+    lib, c, N, D, L, nb = _nmf_sparse_args(counts, W, H, "nmf_kl_divergence_sparse")
+    out = torch.empty(1, dtype=torch.float64, device=W.device)
+    return _nmf_sparse_divergence(lib, c, W, H, N, D, L, nb, out)
+
+
+@_on_device
+def nmf_kl_mu_sparse(counts, W0, H0, max_iter: int = 200, tol: float = 1e-4):
+    """``nmf_kl_mu`` of X (N, D) = counts^T over the stored non-zeros (gpz_nmf_kl_sparse_update): O(nnz L) per iteration,
+    no N x D array anywhere.  ``counts``: a ``likelihoods.SparseCounts`` (D genes, N spots, not a view) or its ``.T``;
+    W0 (N, L), H0 (L, D) on its device, one dtype (fp32 or fp64), L <= 64.  Returns ``(W, H, n_iter)``; W0 and H0 are
+    copied.  Control flow, stopping rule and reproducibility are those of ``nmf_kl_mu``."""
+    W, H = W0.detach().clone().contiguous(), H0.detach().clone().contiguous()
+    lib, c, N, D, L, nb = _nmf_sparse_args(counts, W, H, "nmf_kl_mu_sparse")
+
+    def update(k):
+        ws = _workspace(W.device, nb)
+        rc = lib.gpz_nmf_kl_sparse_update(*_count_ptrs(c), _ptr(W), _ptr(H), N, D, c.nnz, L, _dt(W), k, _ptr(ws), ws.numel(),
+                                          _stream(W.device))
+        _lib.check(rc, "gpz_nmf_kl_sparse_update")
+
+    out = torch.empty(1, dtype=torch.float64, device=W.device)
+    return W, H, _nmf_mu_loop(update, lambda: _nmf_sparse_divergence(lib, c, W, H, N, D, L, nb, out), int(max_iter), tol)
+
+
+def nmf_kl_sparse_plan(N: int, D: int, L: int, nnz: int, dtype=torch.float32) -> dict:
+    """How ``nmf_kl_mu_sparse`` covers a shape (gpz_nmf_kl_sparse_plan, a host-only query: no device needed):
+    ``spot_chunk`` and ``gene_chunk`` (non-zeros of a spot's / a gene's row per wave; 0: rows are not split),
+    ``n_gene_chunks`` (upper bound of the gene pass's work list), ``factors_padded`` (L rounded up to the kernel instance),
+    ``colsum_rows`` (rows per block of the partial sums behind colsum(W) and rowsum(H)), ``workspace_bytes``."""
+    lib = _lib.load()
+    dt = GPZ_F32 if dtype == torch.float32 else GPZ_F64 if dtype == torch.float64 else -1
+    sc, gc, fp, cr, nch = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = lib.gpz_nmf_kl_sparse_plan(int(N), int(D), int(nnz), int(L), dt, C.byref(sc), C.byref(gc), C.byref(nch), C.byref(fp),
+                                    C.byref(cr))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(spot_chunk=sc.value, gene_chunk=gc.value, n_gene_chunks=nch.value, factors_padded=fp.value,
+                colsum_rows=cr.value,
+                workspace_bytes=int(lib.gpz_nmf_kl_sparse_workspace_bytes(int(N), int(D), int(nnz), int(L), dt)))
+
+
+@_on_device
+def counts_matmul(counts, Q, transpose: bool = False):
+    """``X @ Q`` (N, k) for Q (D, k), or with ``transpose`` ``X.T @ Q`` (D, k) for Q (N, k), X (N, D) = counts^T held as its
+    non-zeros (gpz_counts_matmul): fp64, k <= 128, every sum in a fixed order.  ``counts``: a ``SparseCounts`` or its ``.T``."""
+    c = _whole_counts(counts, "counts_matmul")
+    _need_cuda(Q)
+    if c.device != Q.device:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {c.device}, Q on {Q.device}: move them with counts.to(device)")
+    D, N = c.shape
+    Q = Q.detach().to(torch.float64).contiguous()
+    if Q.dim() != 2 or Q.shape[0] != (N if transpose else D):
+        raise ValueError(f"counts_matmul: Q ({N if transpose else D}, k) expected, got {tuple(Q.shape)}")
+    k = Q.shape[1]
+    lib = _lib.load()
+    nb = lib.gpz_counts_matmul_workspace_bytes(N, D, c.nnz, k, int(bool(transpose)))
+    if nb == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    out = torch.empty((D if transpose else N, k), dtype=torch.float64, device=Q.device)
+    ws = _workspace(Q.device, nb)
+    rc = lib.gpz_counts_matmul(*_count_ptrs(c), _ptr(Q), _ptr(out), N, D, c.nnz, k, int(bool(transpose)), _ptr(ws), ws.numel(),
+                               _stream(Q.device))
+    _lib.check(rc, "gpz_counts_matmul")
+    return out
 
 
 @_on_device

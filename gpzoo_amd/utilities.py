@@ -446,6 +446,12 @@ def regularized_nmf(Y, L, sz=1, pseudocount=1e-2, factors=None, loadings=None, s
     reference, which scales a float ``loadings`` argument in place when ``shrinkage`` is outside (0, 1), the caller's
     arrays are never modified.
 
+    Y may be ``counts.T`` of a ``likelihoods.SparseCounts`` (the counts the model trains on, held as their non-zeros): the
+    start and the updates then run over the stored values in the view's dtype (``counts.T`` float32, ``counts.T.double()``
+    float64) through ``ops.counts_matmul`` and ``ops.nmf_kl_mu_sparse`` -- O(nnz L) per iteration, no N x D array -- with
+    the same keywords, checks (the values checked are the stored ones), post-processing and output dtypes.  The
+    ``SparseCounts`` itself (genes x spots) raises TypeError: there is no silent transposition.
+
     Otherwise the factorisation runs on the GPU -- Y's own if it is a CUDA tensor, else the current one: float32 stays
     float32, everything else is computed in float64 (as sklearn does); ``nmf.initialize_nmf`` gives sklearn's starting
     values and ``ops.nmf_kl_mu`` (gpz_nmf_kl_update) its multiplicative updates with its stopping rule.  The keywords are
@@ -461,8 +467,9 @@ def regularized_nmf(Y, L, sz=1, pseudocount=1e-2, factors=None, loadings=None, s
     if factors is None or loadings is None:
         init, max_iter, tol, random_state = _nmf_options(kwargs)
         from . import nmf, ops
-        Yt = Y.detach() if isinstance(Y, torch.Tensor) else torch.as_tensor(np.asarray(Y))
-        if Yt.dim() != 2:
+        sparse = _transposed_counts(Y, "regularized_nmf")
+        Yt = Y if sparse else Y.detach() if isinstance(Y, torch.Tensor) else torch.as_tensor(np.asarray(Y))
+        if not sparse and Yt.dim() != 2:
             raise ValueError(f"regularized_nmf: Y must be (obs, feat), got shape {tuple(Yt.shape)}")
         if not 1 <= L_int <= 64:
             raise ValueError(f"regularized_nmf: L={L_int} unsupported (1..64)")
@@ -471,12 +478,16 @@ def regularized_nmf(Y, L, sz=1, pseudocount=1e-2, factors=None, loadings=None, s
         n_sz = np.shape(sz)
         if len(n_sz) and n_sz[0] not in (1, Yt.shape[0]):
             raise ValueError(f"regularized_nmf: {n_sz[0]} size factors for {Yt.shape[0]} observations")
-        dev = Yt.device if Yt.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        Yt = Yt.to(device=dev, dtype=torch.float32 if Yt.dtype == torch.float32 else torch.float64).contiguous()
-        if not bool((torch.isfinite(Yt) & (Yt >= 0)).all()):
+        dev = Yt.device if Yt.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+        if sparse:
+            Yt = Yt.to(dev)
+            vals = Yt.T.col_val
+        else:
+            Yt = vals = Yt.to(device=dev, dtype=torch.float32 if Yt.dtype == torch.float32 else torch.float64).contiguous()
+        if not bool((torch.isfinite(vals) & (vals >= 0)).all()):
             raise ValueError("regularized_nmf: Y holds a negative or non-finite value")
         W0, H0 = nmf.initialize_nmf(Yt, L_int, init=init, random_state=random_state)
-        Wd, Hd, _ = ops.nmf_kl_mu(Yt, W0, H0, max_iter=max_iter, tol=tol)
+        Wd, Hd, _ = (ops.nmf_kl_mu_sparse if sparse else ops.nmf_kl_mu)(Yt, W0, H0, max_iter=max_iter, tol=tol)
         eF, W = Wd.cpu().numpy(), Hd.cpu().numpy().T
     else:
         eF, W = np.asarray(factors), np.asarray(loadings)
@@ -502,11 +513,25 @@ def init_softplus(mat, minval=1e-5):
     return out
 
 
+def _transposed_counts(Y, who):
+    """True for ``counts.T`` of a ``SparseCounts``; the ``SparseCounts`` itself (genes x spots) is refused, not transposed."""
+    from .likelihoods import SparseCounts, TransposedCounts
+    if isinstance(Y, SparseCounts):
+        raise TypeError(f"{who}: Y is a SparseCounts (genes x spots); pass its .T (obs x feat)")
+    return isinstance(Y, TransposedCounts)
+
+
 def scanpy_sizefactors(Y):
     """(N,1) size factors of the count matrix Y (obs x feat): the row totals over their median (reference
-    utilities.py:232-234)."""
+    utilities.py:232-234).  Y may be ``counts.T`` of a ``SparseCounts``: the spot totals are then the fp64 segment sums of
+    the stored values on the counts' device, and the (N,1) float64 numpy array comes back."""
     import numpy as np
-    totals = Y.sum(axis=1, keepdims=True)
+    if _transposed_counts(Y, "scanpy_sizefactors"):
+        c = Y.T
+        run = torch.cat([c.col_val.new_zeros(1, dtype=torch.float64), torch.cumsum(c.col_val.to(torch.float64), 0)])
+        totals = torch.diff(run[c.col_ptr]).cpu().numpy().reshape(-1, 1)
+    else:
+        totals = Y.sum(axis=1, keepdims=True)
     return totals / np.median(totals)
 
 

@@ -34,7 +34,10 @@
  * K_zx F^T of the kernel least-squares start for gp.mu behind project_factors_to_inducing (the notebooks' hand-written
  * Kzx @ Kxz / cholesky_solve composition), in one pass over X without a stored K_zx;
  * gpz_poisson_nsf_sparse, gpz_poisson_nsf_sparse_workspace_bytes and gpz_poisson_nsf_sparse_plan -- gpz_poisson_nsf for
- * counts stored as their non-zeros: the same outputs as exact sums over the non-zeros.
+ * counts stored as their non-zeros: the same outputs as exact sums over the non-zeros;
+ * gpz_nmf_kl_sparse_update, gpz_nmf_kl_sparse_divergence, gpz_nmf_kl_sparse_workspace_bytes and gpz_nmf_kl_sparse_plan --
+ * gpz_nmf_kl_update / _divergence over the same stored non-zeros, and gpz_counts_matmul with its workspace query -- the
+ * products of those counts with a thin dense matrix that the NNDSVD start of that factorisation needs.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -418,6 +421,43 @@ int gpz_nmf_kl_update(const void* X, void* W, void* H, int64_t N, int64_t D, int
                       void* ws, size_t ws_bytes, void* stream);
 int gpz_nmf_kl_divergence(const void* X, const void* W, const void* H, int64_t N, int64_t D, int64_t L, int32_t dtype,
                           double* out, void* ws, size_t ws_bytes, void* stream);
+
+/* The same NMF for counts held as their non-zeros (gpzoo_amd.likelihoods.SparseCounts, the six arrays of
+ * gpz_poisson_nsf_sparse): the counts are (D genes, N spots) and X[n,d] = counts[d,n], so the by-spot order lists the
+ * non-zeros of a row of X (the W update reads it) and the by-gene order those of a column (the H update reads it).
+ * Q = X / max(W H, EPS) is zero wherever X is: both numerators are sums over the stored values, the denominators are
+ * rowsum(H) and colsum(W), and the divergence is sum_{x > EPS} x log(x / max(p, EPS)) + colsum(W) . rowsum(H) - sum x.
+ * One iteration has the semantics of gpz_nmf_kl_update (same clamps, same zero-sum rules, H < float64 epsilon -> 0; a spot
+ * or gene without non-zeros gets a zero numerator) for O(nnz L) work; nothing of N x D or of nnz elements is allocated.
+ * W (N,L) and H (L,D) row-major of `dtype`, updated in place; col_val is fp32 whatever the dtype.  1 <= L <= 64 (padded to
+ * the kernel instance 4 8 12 16 20 24 32 40 48 64 with zeros), N, D >= 1, nnz >= 0 (the four per-non-zero arrays may be
+ * NULL when nnz == 0), N, D, nnz < 2^31; ws 16-byte aligned.  Argument errors return -1 before any launch and the
+ * workspace query then returns 0.  No floating-point atomics, no workgroup waits on another, every sum in a fixed order:
+ * two calls agree bit for bit and one call of 2 k iterations equals two of k.
+ * gpz_nmf_kl_sparse_plan (host only, no device needed): spot_chunk = non-zeros of a spot's row per wave of the W pass (0:
+ * rows are not split), gene_chunk = the same for a gene's row in the H pass (a longer row is cut into chunks whose
+ * partial sums are added in chunk order), n_gene_chunks = D + nnz / gene_chunk, an upper bound of the chunks in use,
+ * factors_padded = L rounded up to the kernel instance, colsum_rows = rows per block of the partial sums behind
+ * colsum(W) and rowsum(H).  Any out pointer may be NULL. */
+int gpz_nmf_kl_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t L, int32_t dtype, int32_t* spot_chunk,
+                           int32_t* gene_chunk, int64_t* n_gene_chunks, int32_t* factors_padded, int32_t* colsum_rows);
+size_t gpz_nmf_kl_sparse_workspace_bytes(int64_t N, int64_t D, int64_t nnz, int32_t L, int32_t dtype);
+int gpz_nmf_kl_sparse_update(const int64_t* col_ptr, const int32_t* col_gene, const float* col_val, const int64_t* row_ptr,
+                             const int32_t* row_spot, const int32_t* row_perm, void* W, void* H, int64_t N, int64_t D,
+                             int64_t nnz, int32_t L, int32_t dtype, int64_t iters, void* ws, size_t ws_bytes, void* stream);
+int gpz_nmf_kl_sparse_divergence(const int64_t* col_ptr, const int32_t* col_gene, const float* col_val,
+                                 const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const void* W,
+                                 const void* H, int64_t N, int64_t D, int64_t nnz, int32_t L, int32_t dtype, double* out,
+                                 void* ws, size_t ws_bytes, void* stream);
+
+/* Products of the same counts with a thin fp64 matrix, for the subspace iteration behind the NNDSVD start:
+ * transpose = 0: out (N,k) = X Q, Q (D,k);  transpose = 1: out (D,k) = X^T Q, Q (N,k);  row-major, 1 <= k <= 128.
+ * One wave per spot, or per chunk of a gene's row with the chunk partials added in chunk order; the stored values of a row
+ * are added in their stored order: bitwise repeatable.  Argument errors as above. */
+size_t gpz_counts_matmul_workspace_bytes(int64_t N, int64_t D, int64_t nnz, int32_t k, int32_t transpose);
+int gpz_counts_matmul(const int64_t* col_ptr, const int32_t* col_gene, const float* col_val, const int64_t* row_ptr,
+                      const int32_t* row_spot, const int32_t* row_perm, const double* Q, double* out, int64_t N, int64_t D,
+                      int64_t nnz, int32_t k, int32_t transpose, void* ws, size_t ws_bytes, void* stream);
 
 /* Exact K-nearest mean: for each of M query points Z (M,d) the mean of F (N,L) over the K points of X (N,d) nearest to it
  * -- sklearn's KNeighborsRegressor(n_neighbors=K).fit(X, F).predict(Z) with uniform weights (smooth_spatial_factors,
