@@ -7,8 +7,13 @@ from the spots, NSF2 likelihood, kernel hyper-parameters frozen, `train_batched`
 
 ``--sparse-counts DENSITY`` thins the counts to that fraction of non-zeros (real Slide-seq / Visium matrices are a few per
 cent dense) and fits through ``SparseCounts``: the same model and the same loop, the Poisson step over the non-zeros only.
+
+``--holdout FRAC`` holds that fraction of the spots out (``train_val_split``, the split of the reference's
+``anndata_to_train_val``), fits on the rest and prints the Poisson deviance of the held-out spots under the predictive mean
+rate and the share of the null model's deviance it explains (``model.deviance``); it works with ``--sparse-counts`` too.
 """
 import argparse
+import math
 import time
 
 import torch
@@ -17,7 +22,7 @@ import torch.nn as nn
 from gpzoo.gp import SVGP
 from gpzoo.kernels import NSF_RBF
 from gpzoo.likelihoods import NSF2, SparseCounts
-from gpzoo.utilities import train_batched
+from gpzoo.utilities import init_softplus, train_batched, train_val_split
 
 
 def synthetic_counts(N, D, L, gen):
@@ -41,6 +46,9 @@ def main():
     ap.add_argument("--samples", type=int, default=3)
     ap.add_argument("--sparse-counts", type=float, default=None, metavar="DENSITY",
                     help="keep about this fraction of the counts as non-zeros and fit through SparseCounts")
+    ap.add_argument("--lr", type=float, default=1e-2, help="Adam's learning rate")
+    ap.add_argument("--holdout", type=float, default=None, metavar="FRAC",
+                    help="hold this fraction of the spots out and print their deviance under the fitted model")
     a = ap.parse_args()
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
@@ -54,15 +62,31 @@ def main():
         print(f"{Y.nnz} non-zeros ({100.0 * Y.nnz / (a.spots * a.genes):.1f} %): {held / 2 ** 20:.1f} MiB held in both orders, "
               f"{dense_bytes / 2 ** 20:.1f} MiB as a dense fp32 array")
 
+    val = None
+    if a.holdout is not None:
+        # the spots are drawn independently, so the first ones are a random subset; size factors per split as scanpy's
+        tr, val = train_val_split(X, Y, train_frac=1.0 - a.holdout, sz="scanpy")
+        if val is None:
+            raise SystemExit(f"--holdout {a.holdout} holds no spot out of {a.spots}")
+        X, Y = tr["X"], tr["y"]
+        print(f"{Y.shape[1]} spots to fit, {val['y'].shape[1]} held out")
+
     kernel = NSF_RBF(sigma=1.0, lengthscale=20.0, L=L)
     gp = SVGP(kernel, dim=2, M=M, jitter=1e-1)
-    gp.Z = nn.Parameter(X[torch.randperm(a.spots, generator=gen)[:M]].clone(), requires_grad=False)
+    gp.Z = nn.Parameter(X[torch.randperm(X.shape[0], generator=gen)[:M]].clone(), requires_grad=False)
     gp.mu = nn.Parameter(torch.zeros(L, M))
     gp.Lu = nn.Parameter(1e-2 * torch.randn(L, M, M, generator=gen))
     kernel.sigma.requires_grad_(False); kernel.lengthscale.requires_grad_(False)   # as in the notebooks
-    model = NSF2(gp, Y, L=L).to(dev)
+    model = NSF2(gp, Y, L=L)
+    if val is not None:
+        # size factors as fixed offsets (each spot's depth over the median): the held-out spots then have theirs too
+        model.V = nn.Parameter(torch.from_numpy(init_softplus(tr["sz"].clamp_min(1e-3).numpy())), requires_grad=False)
+        # ... and the factors start at the level of the data: V softplus(W) exp(mu) summed over L factors ~ the mean count
+        level = float(Y.col_val.sum() / (Y.shape[0] * Y.shape[1]) if isinstance(Y, SparseCounts) else Y.mean())
+        gp.mu.data.fill_(math.log(max(level, 1e-6) / L))
+    model = model.to(dev)
     X, Y = X.to(dev), Y.to(dev)
-    opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=1e-2)
+    opt = torch.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=a.lr)
 
     train_batched(model, opt, X, Y, dev, steps=3, E=a.samples, batch_size=a.batch)          # warm-up (workspaces, caches)
     torch.cuda.synchronize()
@@ -71,10 +95,21 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     k = max(a.steps // 10, 1)
-    print(f"N={a.spots} spots, D={a.genes} genes, L={L} factors, M={M} inducing points, batch {a.batch}, E={a.samples}")
+    print(f"N={X.shape[0]} spots, D={a.genes} genes, L={L} factors, M={M} inducing points, batch {a.batch}, E={a.samples}")
     print("loss (mean of first / last %d steps): %.1f -> %.1f" % (k, sum(losses[:k]) / k, sum(losses[-k:]) / k))
     print("%.1f ms per step (forward + backward + Adam), %.1f s for %d steps" % (1e3 * dt / a.steps, dt, a.steps))
     assert sum(losses[-k:]) < sum(losses[:k])
+    if val is not None:
+        fit = model.deviance(X, Y)
+        V_val = val["sz"].to(dev).clamp_min(1e-3)
+        t0 = time.perf_counter()
+        r = model.deviance(val["X"].to(dev), val["y"].to(dev), V=V_val)
+        total, explained = float(r.total), float(r.explained)                              # waits for the device
+        dt = time.perf_counter() - t0
+        print("training spots:  deviance %.4g (%.4f per entry), explained %.3f" % (float(fit.total), float(fit.mean), float(fit.explained)))
+        print("held-out spots:  deviance %.4g (%.4f per entry), explained %.3f, sum mu / sum y %.3f  [%.1f ms]"
+              % (total, float(r.mean), explained, float(r.sum_mu / r.sum_y), 1e3 * dt))
+        assert total == total and abs(total) != float("inf") and 0.0 < explained < 1.0
 
 
 if __name__ == "__main__":

@@ -9,6 +9,8 @@ as the reference, plus ``expected_loglik`` -- the fused fp32 training-step form
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 from torch import distributions
@@ -363,6 +365,70 @@ def poisson_expected_loglik(qF_list, W_list, V_pos, y, E=10, with_lgamma=True, e
     return _loglik_function(y).apply(mean, scale, W, V_pos, eps, y, with_lgamma)
 
 
+class PoissonDeviance(NamedTuple):
+    """What ``poisson_deviance`` returns; every tensor is fp64 and carries no graph.  ``mean`` = total / (D B);
+    ``explained`` = 1 - total / null_total and ``explained_per_gene`` likewise (NaN where the null deviance is 0);
+    ``sum_mu / sum_y`` is the calibration of the size factors."""
+    total: torch.Tensor
+    mean: torch.Tensor
+    per_gene: torch.Tensor
+    per_spot: torch.Tensor
+    null_total: torch.Tensor
+    null_per_gene: torch.Tensor
+    explained: torch.Tensor
+    explained_per_gene: torch.Tensor
+    sum_y: torch.Tensor
+    sum_mu: torch.Tensor
+
+
+def _explained(dev, null):
+    return torch.where(null == 0, torch.full_like(null, float("nan")), 1.0 - dev / torch.where(null == 0, torch.ones_like(null), null))
+
+
+def poisson_deviance(qF_list, W_list, V_pos, y, *, lognormal_mean=True):
+    """Poisson deviance of the counts ``y`` under the predictive mean rate mu = V * sum_k W_k E_q[exp F_k], exactly (no
+    sampling): E_q[exp F] = exp(mean + scale^2 / 2), or the plug-in exp(mean) with ``lognormal_mean=False``.  The unit
+    deviance is 2 (y log(y / mu) - y + mu), 2 mu where y = 0; the null model is one constant rate per gene given V.
+
+    qF_list: Normal distributions over (L_k, B) factors at the B spots being scored; W_list: positive (D, L_k) loadings;
+    V_pos (B,) positive size factors; y: the (D, B) counts, dense (gpz_poisson_deviance) or a ``SparseCounts`` / its view
+    ``y[:, idx]`` (gpz_poisson_deviance_sparse).  The (D, B) rate is never materialised.  Returns a ``PoissonDeviance``."""
+    from . import ops
+    with torch.no_grad():
+        mean = torch.cat([q.mean for q in qF_list], dim=0)
+        scale = torch.cat([q.scale for q in qF_list], dim=0)
+        W = torch.cat(list(W_list), dim=1)
+        if isinstance(y, SparseCounts):
+            r = ops.poisson_deviance_sparse(mean, scale, W, V_pos, y, None, lognormal_mean)
+        else:
+            r = ops.poisson_deviance(mean, scale, W, V_pos, y, lognormal_mean)
+        D, B = y.shape
+        return PoissonDeviance(total=r["total"], mean=r["total"] / (D * B), per_gene=r["per_gene"], per_spot=r["per_spot"],
+                               null_total=r["null_total"], null_per_gene=r["null_per_gene"],
+                               explained=_explained(r["total"], r["null_total"]),
+                               explained_per_gene=_explained(r["per_gene"], r["null_per_gene"]),
+                               sum_y=r["sum_y"], sum_mu=r["sum_mu"])
+
+
+def _deviance_size_factors(raw_V, idx, V, n_spots, who):
+    """The positive size factors of ``deviance``: the caller's ``V`` or softplus of the model's (indexed by ``idx``)."""
+    if V is None:
+        V = torch.nn.functional.softplus(raw_V)
+        V = V if idx is None else V[idx]
+    V = torch.as_tensor(V).reshape(-1)
+    if V.numel() != n_spots:
+        raise ValueError(f"{who}.deviance: {V.numel()} size factors for {n_spots} spots"
+                         + ("" if idx is not None else " (held-out spots need explicit positive size factors V=)"))
+    return V
+
+
+def _hybrid_spots(n_fitted, n_spots, idx, V, who):
+    """The hybrids' non-spatial factors exist only for the fitted spots."""
+    if idx is None and n_spots != n_fitted:
+        raise ValueError(f"{who}.deviance: the non-spatial factors exist only for the {n_fitted} fitted spots, so {n_spots} "
+                         "other spots cannot be scored" + (" (V= does not change that)" if V is not None else ""))
+
+
 class PoissonFactorization(nn.Module):
     """softplus(W) @ exp(F): base of PNMF / NSF2 / the hybrids; reference likelihoods.py:39-53."""
 
@@ -421,6 +487,15 @@ class NSF2(PoissonFactorization):
                                      torch.nn.functional.softplus(V), y, E=E, with_lgamma=with_lgamma, eps=eps)
         return ll, qF, qU, pU
 
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+        """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate: a ``PoissonDeviance``.
+        ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors."""
+        with torch.no_grad():
+            Xb = X if idx is None else X[idx]
+            Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+            qF = self.prior(X=Xb, **kwargs)[0]
+            return poisson_deviance([qF], [torch.nn.functional.softplus(self.W)], Vp, y, lognormal_mean=lognormal_mean)
+
 
 class NSF(nn.Module):
     """Same model with W, V held directly; reference likelihoods.py:227-268."""
@@ -452,6 +527,15 @@ class NSF(nn.Module):
                                      E=E, with_lgamma=with_lgamma, eps=eps)
         return ll, qF, qU, pU
 
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+        """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate: a ``PoissonDeviance``.
+        ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors."""
+        with torch.no_grad():
+            Xb = X if idx is None else X[idx]
+            Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+            qF = self.gp(X=Xb, **kwargs)[0]
+            return poisson_deviance([qF], [torch.nn.functional.softplus(self.W)], Vp, y, lognormal_mean=lognormal_mean)
+
 
 class MGGP_NSF(NSF):
     """NSF over a multi-group GP (groupsX is positional); reference likelihoods.py:341-374."""
@@ -480,6 +564,16 @@ class MGGP_NSF(NSF):
         ll = poisson_expected_loglik([qF], [torch.nn.functional.softplus(self.W)], V if idx is None else V[idx], y,
                                      E=E, with_lgamma=with_lgamma, eps=eps)
         return ll, qF, qU, pU
+
+    def deviance(self, X, y, groupsX=None, idx=None, V=None, lognormal_mean=True, **kwargs):
+        """``NSF.deviance`` with the group ids of the spots being scored (``groupsX[idx]`` with ``idx``)."""
+        if groupsX is None:
+            raise TypeError("MGGP_NSF.deviance needs groupsX")
+        with torch.no_grad():
+            Xb, gb = (X, groupsX) if idx is None else (X[idx], groupsX[idx])
+            Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+            qF = self._gp(Xb, gb, False)[0]
+            return poisson_deviance([qF], [torch.nn.functional.softplus(self.W)], Vp, y, lognormal_mean=lognormal_mean)
 
 
 class Hybrid_NSF2(nn.Module):
@@ -520,6 +614,18 @@ class Hybrid_NSF2(nn.Module):
         ll = poisson_expected_loglik([qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], sp(V), y, E=E,
                                      with_lgamma=with_lgamma, eps=eps)
         return ll, qF1, qU, pU, qF2, pF2
+
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+        """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate of both factor sets: a
+        ``PoissonDeviance``.  The non-spatial factors exist only for the fitted spots: other spots raise ValueError."""
+        with torch.no_grad():
+            Xb = X if idx is None else X[idx]
+            _hybrid_spots(self.V.shape[0], Xb.shape[0], idx, V, type(self).__name__)
+            Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+            qF1 = self.sf.prior(X=Xb, **kwargs)[0]
+            qF2 = (self.cf.prior() if idx is None else self.cf.prior.forward_batched(idx))[0]
+            sp = torch.nn.functional.softplus
+            return poisson_deviance([qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], Vp, y, lognormal_mean=lognormal_mean)
 
 
 class Hybrid_NSF_Exact(Hybrid_NSF2):
@@ -592,3 +698,16 @@ class Hybrid_NSF(NSF):
         ll = poisson_expected_loglik([qF, qF2], [self.W, self.W2], V if idx is None else V[idx], y, E=E,
                                      with_lgamma=with_lgamma, eps=eps)
         return ll, qF, qU, pU, qF2, pF2
+
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+        """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate of both factor sets (raw
+        loadings W, W2 as in ``_hybrid``).  The non-spatial factors exist only for the fitted spots: other spots raise
+        ValueError."""
+        with torch.no_grad():
+            Xb = X if idx is None else X[idx]
+            _hybrid_spots(self.V.shape[0], Xb.shape[0], idx, V, type(self).__name__)
+            Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+            mF, rs = (self.mF, self.scale_qF) if idx is None else (self.mF[:, idx], self.scale_qF[:, idx])
+            qF = self.gp(X=Xb, **kwargs)[0]
+            qF2 = distributions.Normal(mF, torch.nn.functional.softplus(rs), validate_args=False)
+            return poisson_deviance([qF, qF2], [self.W, self.W2], Vp, y, lognormal_mean=lognormal_mean)

@@ -1361,6 +1361,121 @@ def poisson_nsf_sparse(mean, scale, eps, W_pos, V_pos, counts, idx=None, with_lg
     return total, dmean, dscale, dW, dV
 
 
+def _deviance_result(per_gene, per_spot, null_per_gene, scalars):
+    return dict(per_gene=per_gene, per_spot=per_spot, null_per_gene=null_per_gene, total=scalars[0], sum_y=scalars[1],
+                sum_mu=scalars[2], null_total=scalars[3])
+
+
+def poisson_deviance_plan(N: int, D: int, Lt: int) -> dict:
+    """How ``poisson_deviance`` covers a shape (gpz_poisson_deviance_plan, a host-only query: no device needed):
+    ``spots_per_tile`` x ``genes_per_tile`` (one wave's tile), ``genes_per_block`` (one workgroup's genes = one per-spot
+    partial slab), ``gene_slices`` (number of those), ``spot_slices`` (per-gene partial slabs) of ``tiles_per_spot_slice``
+    tiles each, ``factors_padded``, ``workspace_bytes``."""
+    lib = _lib.load()
+    v = [C.c_int32() for _ in range(5)]
+    tper, fp = C.c_int64(), C.c_int32()
+    rc = lib.gpz_poisson_deviance_plan(int(N), int(D), int(Lt), *(C.byref(x) for x in v), C.byref(tper), C.byref(fp))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(spots_per_tile=v[0].value, genes_per_tile=v[1].value, genes_per_block=v[2].value, gene_slices=v[3].value,
+                spot_slices=v[4].value, tiles_per_spot_slice=tper.value, factors_padded=fp.value,
+                workspace_bytes=int(lib.gpz_poisson_deviance_workspace_bytes(int(N), int(D), int(Lt))))
+
+
+def poisson_deviance_sparse_plan(N: int, B: int, D: int, Lt: int, nnz: int) -> dict:
+    """The same for ``poisson_deviance_sparse`` (gpz_poisson_deviance_sparse_plan): ``gene_chunk`` (non-zeros of a gene row
+    per wave), ``spot_chunk`` (0: columns are not split), ``n_gene_chunks``, ``factors_padded``, ``workspace_bytes``."""
+    lib = _lib.load()
+    gc, sc, fp, nch = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = lib.gpz_poisson_deviance_sparse_plan(int(N), int(B), int(D), int(Lt), int(nnz), C.byref(gc), C.byref(sc),
+                                              C.byref(nch), C.byref(fp))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, spot_chunk=sc.value, n_gene_chunks=nch.value, factors_padded=fp.value,
+                workspace_bytes=int(lib.gpz_poisson_deviance_sparse_workspace_bytes(int(N), int(B), int(D), int(nnz), int(Lt))))
+
+
+@_on_device
+def poisson_deviance(mean, scale, W_pos, V_pos, y, lognormal_mean: bool = True):
+    """Poisson deviance of the counts under the predictive mean rate (gpz_poisson_deviance): mu = V W m with
+    m = exp(mean + scale^2 / 2) (``lognormal_mean``; exp(mean) without) and dev = 2 (y log(y / mu) - y + mu), 2 mu at y = 0.
+
+    mean, scale (Lt,N); W_pos (D,Lt) and V_pos (N,) positive; y (D,N), read once; the (D,N) rate is never materialised.
+    Returns a dict of fp64 tensors without a graph: ``per_gene`` (D,), ``per_spot`` (N,), ``null_per_gene`` (D,) -- the
+    deviance of one constant rate per gene given V -- and the 0-d ``total``, ``sum_y``, ``sum_mu``, ``null_total``.
+    Nothing here waits for the device."""
+    _need_cuda(mean, scale, W_pos, V_pos, y)
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale = mean.detach().to(f32).contiguous(), scale.detach().to(f32).contiguous()
+    W_pos, V_pos, y = W_pos.detach().to(f32).contiguous(), V_pos.detach().to(f32).contiguous(), y.detach().to(f32).contiguous()
+    if W_pos.data_ptr() % 16:
+        W_pos = W_pos.clone()            # the entry wants W 16-byte aligned (include/gpzoo_hip.h)
+    Lt, N = mean.shape
+    D = y.shape[0]
+    if y.shape != (D, N) or scale.shape != (Lt, N) or W_pos.shape != (D, Lt) or V_pos.shape != (N,):
+        raise ValueError(f"poisson_deviance: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, "
+                         f"W {tuple(W_pos.shape)}, V {tuple(V_pos.shape)} do not fit together")
+    dev = mean.device
+    f64 = torch.float64
+    per_gene, null_per_gene = torch.empty(D, dtype=f64, device=dev), torch.empty(D, dtype=f64, device=dev)
+    per_spot, scalars = torch.empty(N, dtype=f64, device=dev), torch.empty(4, dtype=f64, device=dev)
+    nbytes = lib.gpz_poisson_deviance_workspace_bytes(N, D, Lt)
+    if nbytes == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ws = _workspace(dev, nbytes)
+    rc = lib.gpz_poisson_deviance(_ptr(mean), _ptr(scale), _ptr(W_pos), _ptr(V_pos), _ptr(y), N, D, Lt, int(bool(lognormal_mean)),
+                                  _ptr(per_gene), _ptr(per_spot), _ptr(null_per_gene), _ptr(scalars), _ptr(ws), ws.numel(),
+                                  _stream(dev))
+    _lib.check(rc, "gpz_poisson_deviance")
+    return _deviance_result(per_gene, per_spot, null_per_gene, scalars)
+
+
+@_on_device
+def poisson_deviance_sparse(mean, scale, W_pos, V_pos, counts, idx=None, lognormal_mean: bool = True):
+    """``poisson_deviance`` for counts held as their non-zeros (gpz_poisson_deviance_sparse): the same dict, as exact sums
+    over the stored values plus O((D + B) Lt) dense terms.
+
+    counts: a ``likelihoods.SparseCounts`` (D, N), or the view ``counts[:, idx]`` of one.  mean, scale (Lt,B); W_pos (D,Lt);
+    V_pos (B,) with B = N, or B = len(idx) for a view; ``per_spot`` follows the view's order.  ``idx``: shorthand for
+    ``counts[:, idx]`` (its validation is deferred inside ``deferred_info()``).  Nothing here waits for the device."""
+    from .likelihoods import SparseCounts
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"poisson_deviance_sparse: counts must be a SparseCounts, got {type(counts).__name__}")
+    if idx is not None:
+        counts = counts[:, idx]
+    _need_cuda(mean, scale, W_pos, V_pos)
+    dev = mean.device
+    if counts.device != dev:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {counts.device}, the model on {dev}: move them with counts.to(device)")
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale = mean.detach().to(f32).contiguous(), scale.detach().to(f32).contiguous()
+    W_pos, V_pos = W_pos.detach().to(f32).contiguous(), V_pos.detach().to(f32).contiguous()
+    if W_pos.data_ptr() % 16:
+        W_pos = W_pos.clone()
+    base = counts.base
+    D, N = base.shape
+    Lt, B = mean.shape
+    if counts.shape != (W_pos.shape[0], B) or scale.shape != (Lt, B) or W_pos.shape != (D, Lt) or V_pos.shape != (B,):
+        raise ValueError(f"poisson_deviance_sparse: counts {tuple(counts.shape)}, mean {tuple(mean.shape)}, "
+                         f"scale {tuple(scale.shape)}, W {tuple(W_pos.shape)}, V {tuple(V_pos.shape)} do not fit together")
+    f64 = torch.float64
+    per_gene, null_per_gene = torch.empty(D, dtype=f64, device=dev), torch.empty(D, dtype=f64, device=dev)
+    per_spot, scalars = torch.empty(B, dtype=f64, device=dev), torch.empty(4, dtype=f64, device=dev)
+    nbytes = lib.gpz_poisson_deviance_sparse_workspace_bytes(N, B, D, base.nnz, Lt)
+    if nbytes == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ws = _workspace(dev, nbytes)
+    rc = lib.gpz_poisson_deviance_sparse(_ptr(mean), _ptr(scale), _ptr(W_pos), _ptr(V_pos), _ptr(base.col_ptr),
+                                         _ptr(base.col_gene), _ptr(base.col_val), _ptr(base.row_ptr), _ptr(base.row_spot),
+                                         _ptr(base.row_perm), _ptr(counts.idx), _ptr(counts.pos), N, B, D, base.nnz, Lt,
+                                         int(bool(lognormal_mean)), _ptr(per_gene), _ptr(per_spot), _ptr(null_per_gene),
+                                         _ptr(scalars), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_poisson_deviance_sparse")
+    return _deviance_result(per_gene, per_spot, null_per_gene, scalars)
+
+
 def profile_enable(on: bool = True):
     _lib.check(_lib.load().gpz_profile_enable(int(on)), "gpz_profile_enable")
 

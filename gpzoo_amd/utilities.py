@@ -521,18 +521,72 @@ def _transposed_counts(Y, who):
     return isinstance(Y, TransposedCounts)
 
 
+def _spot_totals(Y, who="train_val_split"):
+    """(N,1) row totals of Y (obs x feat): numpy's own sum, or of ``counts.T`` the fp64 segment sums of the stored values."""
+    if _transposed_counts(Y, who):
+        c = Y.T
+        run = torch.cat([c.col_val.new_zeros(1, dtype=torch.float64), torch.cumsum(c.col_val.to(torch.float64), 0)])
+        return torch.diff(run[c.col_ptr]).cpu().numpy().reshape(-1, 1)
+    return Y.sum(axis=1, keepdims=True)
+
+
 def scanpy_sizefactors(Y):
     """(N,1) size factors of the count matrix Y (obs x feat): the row totals over their median (reference
     utilities.py:232-234).  Y may be ``counts.T`` of a ``SparseCounts``: the spot totals are then the fp64 segment sums of
     the stored values on the counts' device, and the (N,1) float64 numpy array comes back."""
     import numpy as np
-    if _transposed_counts(Y, "scanpy_sizefactors"):
-        c = Y.T
-        run = torch.cat([c.col_val.new_zeros(1, dtype=torch.float64), torch.cumsum(c.col_val.to(torch.float64), 0)])
-        totals = torch.diff(run[c.col_ptr]).cpu().numpy().reshape(-1, 1)
-    else:
-        totals = Y.sum(axis=1, keepdims=True)
+    totals = _spot_totals(Y, "scanpy_sizefactors")
     return totals / np.median(totals)
+
+
+def train_val_split(X, y, train_frac=0.95, sz="constant"):
+    """The train / validation split of the reference's ``anndata_to_train_val`` (utilities.py:192-230) in this project's
+    orientation: ``y`` is the (D genes, N spots) count matrix, a dense tensor or a whole ``SparseCounts``, ``X`` the (N, d)
+    coordinates.  The first ``round(train_frac * N)`` spots train, the rest are held out (the spots are assumed
+    pre-shuffled).  ``sz``: "constant" (ones), "mean" (a spot's mean count) or "scanpy" (spot totals over their median,
+    per split as the reference computes it).
+
+    Returns ``(Dtr, Dval)``, dicts with ``X`` (rows of X, not rescaled here), ``y`` (D, n), ``sz`` (n,) and ``idx`` (the
+    spots' positions in the input); ``Dval`` is None when nothing is held out.  Of a ``SparseCounts`` each split's ``y`` is
+    a whole ``SparseCounts`` again (built once from the filtered non-zeros), so the training loops can take ``y[:, idx]``
+    of it; the held-out ``sz`` are the explicit size factors ``model.deviance(..., V=)`` wants."""
+    from .likelihoods import SparseCounts
+    if sz not in ("constant", "mean", "scanpy"):
+        raise ValueError("unrecognized size factors 'sz'")
+    sparse = isinstance(y, SparseCounts)
+    if sparse and y.base is not y:
+        raise TypeError("train_val_split: y is a view y[:, idx]; split the SparseCounts itself")
+    if not sparse:
+        y = torch.as_tensor(y)
+        if y.dim() != 2:
+            raise ValueError(f"train_val_split: a (genes, spots) matrix expected, got {y.dim()} dimensions")
+    D, N = y.shape
+    if X.shape[0] != N:
+        raise ValueError(f"train_val_split: {X.shape[0]} rows of X for {N} spots (y is genes x spots)")
+    Ntr = round(train_frac * N)
+    if not 1 <= Ntr <= N:
+        raise ValueError(f"train_val_split: train_frac = {train_frac} leaves {Ntr} of {N} spots to train on")
+    if sparse:
+        gene, spot, val = y.col_gene.long(), y._spots(), y.col_val
+
+    def part(lo, hi):
+        n = hi - lo
+        if sparse:
+            keep = (spot >= lo) & (spot < hi)
+            yp = SparseCounts(torch.sparse_coo_tensor(torch.stack([gene[keep], spot[keep] - lo]), val[keep], (D, n)))
+            dtype, device = torch.float32, y.device
+        else:
+            yp = y[:, lo:hi]
+            dtype, device = (y.dtype if y.is_floating_point() else torch.float32), y.device
+        if sz == "constant":
+            s = torch.ones(n, dtype=dtype, device=device)
+        else:
+            Yp = yp.T if sparse else yp.T.cpu().numpy()            # obs x feat, as the reference holds it
+            s = scanpy_sizefactors(Yp) if sz == "scanpy" else _spot_totals(Yp) / D
+            s = torch.as_tensor(s).reshape(-1).to(device=device, dtype=dtype)
+        return dict(X=X[lo:hi], y=yp, sz=s, idx=torch.arange(lo, hi))
+
+    return part(0, Ntr), (part(Ntr, N) if Ntr < N else None)
 
 
 def rescale_spatial_coords(X, box_side=4):

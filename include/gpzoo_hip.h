@@ -37,7 +37,11 @@
  * counts stored as their non-zeros: the same outputs as exact sums over the non-zeros;
  * gpz_nmf_kl_sparse_update, gpz_nmf_kl_sparse_divergence, gpz_nmf_kl_sparse_workspace_bytes and gpz_nmf_kl_sparse_plan --
  * gpz_nmf_kl_update / _divergence over the same stored non-zeros, and gpz_counts_matmul with its workspace query -- the
- * products of those counts with a thin dense matrix that the NNDSVD start of that factorisation needs.
+ * products of those counts with a thin dense matrix that the NNDSVD start of that factorisation needs;
+ * gpz_poisson_deviance and gpz_poisson_deviance_sparse, each with its *_workspace_bytes and host-only *_plan query -- the
+ * Poisson deviance of counts (dense, or stored as their non-zeros) under the predictive mean rate of a fitted factor model,
+ * per gene, per spot and in total, with the null model's deviance: the score of held-out spots, which the reference's
+ * anndata_to_train_val prepares (Dval) and nothing in it computes.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -321,6 +325,55 @@ int gpz_poisson_nsf_sparse(const float* mean, const float* scale, const float* e
                            int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t E, int32_t with_lgamma,
                            double* loglik, float* dmean, float* dscale, float* dW, float* dV, void* ws, size_t ws_bytes,
                            void* stream);
+
+/* Poisson deviance under the predictive mean rate of a fitted factor model (csrc/deviance.hip), without materialising the
+ * (D, N) rate.  fp32 inputs, fp64 outputs, no gradients.  mean, scale (Lt, N): q(F) moments of all factors at the N spots being
+ * scored; W (D, Lt), V (N,): POSITIVE loadings / size factors; y (D, N) counts, read exactly once.
+ *   m[l,n]   = exp(mean[l,n] + scale[l,n]^2 / 2)   (lognormal_mean != 0: E_q[exp F] exactly; 0: the plug-in exp(mean))
+ *   mu[d,n]  = V[n] sum_l W[d,l] m[l,n]
+ *   dev[d,n] = 2 (y log(y / mu) - y + mu), the log term exactly 0 at y = 0 (0 log 0 is never formed), so dev = 2 mu there
+ * Outputs: per_gene (D,) = sum_n dev; per_spot (N,) = sum_d dev; null_per_gene (D,) = the deviance of the null model
+ * mu0[d,n] = V[n] r_d, r_d = sum_n y[d,n] / sum_n V[n] (one constant rate per gene given the size factors), exactly 0 for a gene
+ * without counts; scalars (4,) = {total, sum y, sum mu, null total}.  sum mu / sum y is the calibration of the size factors.
+ * The null model's three per-gene sums (sum y, sum y log y, sum y log V) come from the same pass over y.
+ * The rate tile is v_mfma_f32_16x16x4_f32 with the factors padded as gpz_poisson_nsf pads them; the unit deviance is formed
+ * on the accumulator registers and reduced along both axes into partial slabs, which finishing kernels add in a fixed order
+ * in fp64.  No floating-point atomics, no workgroup waits on another: two calls agree bit for bit.
+ * 1 <= Lt <= 64; N, D < 2^31; N need not be a multiple of 4.  W and ws must be 16-byte aligned.  Argument errors (null
+ * pointers, extents, Lt, a small workspace, alignment) return -1 before any launch; the workspace query then returns 0.
+ * gpz_poisson_deviance_plan (host only, no device needed; any out pointer may be NULL): spots_per_tile x genes_per_tile = the
+ * tile of one wave (64 x 16); genes_per_block = genes of one workgroup (64), gene_slices = ceil(D / genes_per_block) = the
+ * number of per-spot partial slabs; spot_slices = number of per-gene partial slabs, each covering tiles_per_spot_slice
+ * consecutive tiles; factors_padded = Lt rounded up to the kernel instance. */
+int gpz_poisson_deviance_plan(int64_t N, int64_t D, int32_t Lt, int32_t* spots_per_tile, int32_t* genes_per_tile,
+                              int32_t* genes_per_block, int32_t* gene_slices, int32_t* spot_slices,
+                              int64_t* tiles_per_spot_slice, int32_t* factors_padded);
+size_t gpz_poisson_deviance_workspace_bytes(int64_t N, int64_t D, int32_t Lt);
+int gpz_poisson_deviance(const float* mean, const float* scale, const float* W, const float* V, const float* y, int64_t N,
+                         int64_t D, int32_t Lt, int32_t lognormal_mean, double* per_gene, double* per_spot,
+                         double* null_per_gene, double* scalars, void* ws, size_t ws_bytes, void* stream);
+
+/* gpz_poisson_deviance for counts stored as their non-zeros: the six arrays, idx / pos and the batch convention of
+ * gpz_poisson_nsf_sparse (both NULL: B == N and the identity); mean, scale (Lt, B), V (B,), W (D, Lt).  Where y = 0 the unit
+ * deviance is 2 mu and sum mu factorises -- per gene sum_l W[d,l] a[l], a[l] = sum_n V[n] m[l,n]; per spot V[n] sum_l c[l] m[l,n],
+ * c[l] = sum_d W[d,l] -- so every output is that dense term plus a sum over the stored values of 2 (y log(y / mu) - y):
+ * O(nnz Lt + (D + B) Lt) work.  A gene or spot without stored values gets exactly the dense term; spots of the base matrix
+ * outside the view contribute nothing, to the null model's sums either.  per_spot (B,) follows idx's order.
+ * No array of D x B or D x N elements exists, workspace included, and the workspace holds nothing of nnz elements: the pass
+ * by gene forms mu again at each non-zero (its chunk list has D + nnz / gene_chunk entries, which the query accounts for).
+ * Same limits, alignment, error and reproducibility contract as gpz_poisson_deviance; nnz < 2^31.
+ * gpz_poisson_deviance_sparse_plan (host only): gene_chunk = non-zeros of one gene row per wave (512; a longer row is cut
+ * into chunks whose partial sums are added in chunk order), spot_chunk = the same for a spot's column (0: columns are not
+ * split), n_gene_chunks = D + nnz / gene_chunk, factors_padded = Lt rounded up to the kernel instance. */
+int gpz_poisson_deviance_sparse_plan(int64_t N, int64_t B, int64_t D, int32_t Lt, int64_t nnz, int32_t* gene_chunk,
+                                     int32_t* spot_chunk, int64_t* n_gene_chunks, int32_t* factors_padded);
+size_t gpz_poisson_deviance_sparse_workspace_bytes(int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt);
+int gpz_poisson_deviance_sparse(const float* mean, const float* scale, const float* W, const float* V, const int64_t* col_ptr,
+                                const int32_t* col_gene, const float* col_val, const int64_t* row_ptr,
+                                const int32_t* row_spot, const int32_t* row_perm, const int32_t* idx, const int32_t* pos,
+                                int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t lognormal_mean,
+                                double* per_gene, double* per_spot, double* null_per_gene, double* scalars, void* ws,
+                                size_t ws_bytes, void* stream);
 
 /* K nearest rows of Z for every row of X, ascending by (Euclidean distance, index): the neighbour
  * bookkeeping of VNNGP, argsort(cdist(X, Z))[:, :K] (gp.py:31, 64).  idx (N,K) int64.  K <= 32. */
