@@ -11,6 +11,10 @@ cent dense) and fits through ``SparseCounts``: the same model and the same loop,
 ``--holdout FRAC`` holds that fraction of the spots out (``train_val_split``, the split of the reference's
 ``anndata_to_train_val``), fits on the rest and prints the Poisson deviance of the held-out spots under the predictive mean
 rate and the share of the null model's deviance it explains (``model.deviance``); it works with ``--sparse-counts`` too.
+
+``--likelihood nb`` draws overdispersed (gamma-Poisson) counts with a known inverse dispersion per gene, fits the model with
+``likelihood="nb"`` (the fused negative-binomial step) and prints the fitted theta next to the true one.  The NB step takes
+dense counts, so it does not combine with ``--sparse-counts``.
 """
 import argparse
 import math
@@ -25,13 +29,18 @@ from gpzoo.likelihoods import NSF2, SparseCounts
 from gpzoo.utilities import init_softplus, train_batched, train_val_split
 
 
-def synthetic_counts(N, D, L, gen):
-    """Smooth non-negative spatial factors on a 2-D tissue, gene loadings and Poisson counts."""
+def synthetic_counts(N, D, L, gen, theta=None):
+    """Smooth non-negative spatial factors on a 2-D tissue, gene loadings and Poisson counts -- gamma-Poisson ones with
+    inverse dispersion ``theta`` (D,) per gene when given (mean as before, variance mean + mean^2 / theta)."""
     X = (torch.rand(N, 2, generator=gen) - 0.5) * 200.0
     centres = (torch.rand(L, 2, generator=gen) - 0.5) * 160.0
     F = torch.exp(-((X[None] - centres[:, None]) ** 2).sum(-1) / (2 * 35.0 ** 2))          # (L,N)
     W = torch.rand(D, L, generator=gen) ** 3 * 4.0
-    Y = torch.poisson(W @ F + 0.05, generator=gen)
+    rate = W @ F + 0.05
+    if theta is not None:
+        torch.manual_seed(int(torch.randint(0, 2 ** 31 - 1, (1,), generator=gen)))        # Gamma.sample takes no generator
+        rate = torch.distributions.Gamma(theta[:, None].expand_as(rate), theta[:, None] / rate).sample()
+    Y = torch.poisson(rate, generator=gen)
     return X, Y
 
 
@@ -49,10 +58,17 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-2, help="Adam's learning rate")
     ap.add_argument("--holdout", type=float, default=None, metavar="FRAC",
                     help="hold this fraction of the spots out and print their deviance under the fitted model")
+    ap.add_argument("--likelihood", choices=["poisson", "nb"], default="poisson",
+                    help="nb: gamma-Poisson counts and the negative-binomial model with one inverse dispersion per gene")
     a = ap.parse_args()
+    if a.likelihood == "nb" and a.sparse_counts is not None:
+        raise SystemExit("--likelihood nb takes dense counts: drop --sparse-counts")
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
-    X, Y = synthetic_counts(a.spots, a.genes, a.factors, gen)
+    theta_true = None
+    if a.likelihood == "nb":
+        theta_true = torch.exp(math.log(0.5) + (math.log(20.0) - math.log(0.5)) * torch.rand(a.genes, generator=gen))
+    X, Y = synthetic_counts(a.spots, a.genes, a.factors, gen, theta_true)
     L, M = a.factors, a.inducing
     if a.sparse_counts is not None:
         Y = Y * (torch.rand(Y.shape, generator=gen) < a.sparse_counts)
@@ -77,7 +93,7 @@ def main():
     gp.mu = nn.Parameter(torch.zeros(L, M))
     gp.Lu = nn.Parameter(1e-2 * torch.randn(L, M, M, generator=gen))
     kernel.sigma.requires_grad_(False); kernel.lengthscale.requires_grad_(False)   # as in the notebooks
-    model = NSF2(gp, Y, L=L)
+    model = NSF2(gp, Y, L=L, likelihood=a.likelihood)
     if val is not None:
         # size factors as fixed offsets (each spot's depth over the median): the held-out spots then have theirs too
         model.V = nn.Parameter(torch.from_numpy(init_softplus(tr["sz"].clamp_min(1e-3).numpy())), requires_grad=False)
@@ -99,6 +115,14 @@ def main():
     print("loss (mean of first / last %d steps): %.1f -> %.1f" % (k, sum(losses[:k]) / k, sum(losses[-k:]) / k))
     print("%.1f ms per step (forward + backward + Adam), %.1f s for %d steps" % (1e3 * dt / a.steps, dt, a.steps))
     assert sum(losses[-k:]) < sum(losses[:k])
+    if theta_true is not None:
+        fit_theta = torch.nn.functional.softplus(model.theta.detach()).cpu()
+        order = torch.argsort(theta_true)
+        pick = order[torch.linspace(0, a.genes - 1, min(8, a.genes)).long()]
+        print("theta (true -> fitted, genes across the range): " + ", ".join(f"{float(theta_true[i]):.2f} -> {float(fit_theta[i]):.2f}" for i in pick))
+        lt, lf = torch.log(theta_true), torch.log(fit_theta)
+        print("median fitted theta %.2f (true %.2f, start 10); correlation of log theta %.2f"
+              % (float(fit_theta.median()), float(theta_true.median()), float(torch.corrcoef(torch.stack([lt, lf]))[0, 1])))
     if val is not None:
         fit = model.deviance(X, Y)
         V_val = val["sz"].to(dev).clamp_min(1e-3)

@@ -6,6 +6,9 @@ torch distributions exactly like reference likelihoods.py:7-36.  The Poisson
 factor models (SURVEY §8f "next" #2) follow below: same classes and return tuples
 as the reference, plus ``expected_loglik`` -- the fused fp32 training-step form
 (``gpz_poisson_nsf``; fp64 models are evaluated in fp32 there and cast back).
+``likelihood="nb"`` on any of the count models swaps the Poisson noise for a negative binomial with one inverse
+dispersion per gene (the nsf paper's ``lik="nb"``): ``pY`` is a torch NegativeBinomial and ``expected_loglik`` runs
+the fused ``gpz_nb_nsf`` step.
 """
 from __future__ import annotations
 
@@ -365,6 +368,73 @@ def poisson_expected_loglik(qF_list, W_list, V_pos, y, E=10, with_lgamma=True, e
     return _loglik_function(y).apply(mean, scale, W, V_pos, eps, y, with_lgamma)
 
 
+class _NBLogLik(torch.autograd.Function):
+    """(1/E) sum_e sum_dn log NegativeBinomial(y | total_count = theta_d, mean = V Z_e) through gpz_nb_nsf (forward and
+    gradients in one fused pass; backward only scales them)."""
+
+    @staticmethod
+    def forward(ctx, mean, scale, W_pos, V_pos, theta_pos, eps, y, with_lgamma):
+        from . import ops
+        ll, dmean, dscale, dW, dV, dtheta = ops.nb_nsf(mean, scale, eps, W_pos, V_pos, theta_pos, y, with_lgamma)
+        ctx.save_for_backward(dmean.to(mean.dtype), dscale.to(scale.dtype), dW.to(W_pos.dtype), dV.to(V_pos.dtype),
+                              dtheta.to(theta_pos.dtype))
+        return ll.to(mean.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        dmean, dscale, dW, dV, dtheta = ctx.saved_tensors
+        return g * dmean, g * dscale, g * dW, g * dV, g * dtheta, None, None, None
+
+
+def nb_expected_loglik(qF_list, W_list, V_pos, theta_pos, y, E=10, with_lgamma=True, eps=None):
+    """``poisson_expected_loglik`` under pY = NegativeBinomial(total_count=theta[:, None], logits=log(rate) - log(theta[:, None])),
+    rate = V * sum_k W_k exp(F_k): theta_pos (D,) positive inverse dispersions, variance rate + rate^2 / theta.  ``eps`` is
+    drawn exactly as there.  y: the dense (D, N) counts (gpz_nb_nsf; a ``SparseCounts`` raises TypeError -- the zero-count
+    term depends on the rate, so the step has no sum over the non-zeros)."""
+    mean = torch.cat([q.mean for q in qF_list], dim=0)
+    scale = torch.cat([q.scale for q in qF_list], dim=0)
+    W = torch.cat(list(W_list), dim=1)
+    if eps is None:   # one draw per factor set, in order, through the function Normal.rsample itself uses
+        import torch.distributions.normal as tdn
+        eps = torch.cat([tdn._standard_normal((E,) + tuple(q.mean.shape), dtype=mean.dtype, device=mean.device)
+                         for q in qF_list], dim=1)
+    return _NBLogLik.apply(mean, scale, W, V_pos, theta_pos, eps, y, with_lgamma)
+
+
+LIKELIHOODS = ("poisson", "nb")
+
+
+def _init_likelihood(module, likelihood, theta0, D):
+    """The ``likelihood=`` / ``theta0=`` keywords of the count models.  "poisson" adds nothing (the parameters stay the
+    reference's); "nb" adds ``theta`` (D,), raw, with softplus(theta) = theta0 (``init_softplus``)."""
+    if likelihood not in LIKELIHOODS:
+        raise ValueError(f"{type(module).__name__}: likelihood={likelihood!r} unknown (one of {LIKELIHOODS})")
+    module.likelihood = likelihood
+    if likelihood == "nb":
+        import numpy as np
+        from .utilities import init_softplus
+        if not float(theta0) > 0:
+            raise ValueError(f"{type(module).__name__}: theta0 must be positive, got {theta0}")
+        raw = init_softplus(np.full((D,), float(theta0), dtype=np.float64))
+        module.theta = nn.Parameter(torch.as_tensor(raw, dtype=torch.get_default_dtype()))
+
+
+def _count_dist(module, rate):
+    """pY of a count model over its rate: Poisson, or the negative binomial with the model's per-gene theta."""
+    if getattr(module, "likelihood", "poisson") == "nb":
+        th = torch.nn.functional.softplus(module.theta)[:, None]
+        return _dist(distributions.NegativeBinomial, total_count=th, logits=torch.log(rate) - torch.log(th))
+    return _dist(distributions.Poisson, rate)
+
+
+def _expected_loglik(module, qF_list, W_list, V_pos, y, E, with_lgamma, eps):
+    """The fused training-step value of a count model under its likelihood."""
+    if getattr(module, "likelihood", "poisson") == "nb":
+        return nb_expected_loglik(qF_list, W_list, V_pos, torch.nn.functional.softplus(module.theta), y, E=E,
+                                  with_lgamma=with_lgamma, eps=eps)
+    return poisson_expected_loglik(qF_list, W_list, V_pos, y, E=E, with_lgamma=with_lgamma, eps=eps)
+
+
 class PoissonDeviance(NamedTuple):
     """What ``poisson_deviance`` returns; every tensor is fp64 and carries no graph.  ``mean`` = total / (D B);
     ``explained`` = 1 - total / null_total and ``explained_per_gene`` likewise (NaN where the null deviance is 0);
@@ -430,13 +500,16 @@ def _hybrid_spots(n_fitted, n_spots, idx, V, who):
 
 
 class PoissonFactorization(nn.Module):
-    """softplus(W) @ exp(F): base of PNMF / NSF2 / the hybrids; reference likelihoods.py:39-53."""
+    """softplus(W) @ exp(F): base of PNMF / NSF2 / the hybrids; reference likelihoods.py:39-53.
+    ``likelihood="nb"`` (here and on every count model below): negative-binomial noise with the per-gene parameter
+    ``theta`` (raw; softplus(theta) = theta0 at the start) in place of Poisson noise."""
 
-    def __init__(self, prior, y, L=10):
+    def __init__(self, prior, y, L=10, likelihood="poisson", theta0=10.0):
         super().__init__()
         D, N = y.shape
         self.prior = prior
         self.W = nn.Parameter(torch.rand((D, L)))
+        _init_likelihood(self, likelihood, theta0, D)
 
     def get_rate(self, prior_samples):
         return torch.matmul(torch.nn.functional.softplus(self.W), torch.exp(prior_samples))   # (E, D, N)
@@ -445,8 +518,8 @@ class PoissonFactorization(nn.Module):
 class PNMF(PoissonFactorization):
     """Non-spatial Poisson NMF over a GaussianPrior; reference likelihoods.py:56-72."""
 
-    def __init__(self, prior, y, L=10):
-        super().__init__(prior=prior, y=y, L=L)
+    def __init__(self, prior, y, L=10, likelihood="poisson", theta0=10.0):
+        super().__init__(prior=prior, y=y, L=L, likelihood=likelihood, theta0=theta0)
         D, N = y.shape
         self.V = nn.Parameter(torch.ones((N,)))
         self.X = nn.Parameter(torch.zeros((N, 2)), requires_grad=False)
@@ -454,28 +527,28 @@ class PNMF(PoissonFactorization):
     def forward(self, E=10, **kwargs):
         qF, pF = self.prior()
         Z = self.get_rate(qF.rsample((E,)))
-        pY = _dist(distributions.Poisson, torch.nn.functional.softplus(self.V) * Z)
+        pY = _count_dist(self, torch.nn.functional.softplus(self.V) * Z)
         return pY, qF, pF
 
 
 class NSF2(PoissonFactorization):
     """Non-negative spatial factorisation over an SVGP prior; reference likelihoods.py:74-97."""
 
-    def __init__(self, gp, y, L=10):
-        super().__init__(prior=gp, y=y, L=L)
+    def __init__(self, gp, y, L=10, likelihood="poisson", theta0=10.0):
+        super().__init__(prior=gp, y=y, L=L, likelihood=likelihood, theta0=theta0)
         D, N = y.shape
         self.V = nn.Parameter(torch.ones((N,)))
 
     def forward(self, X, E=10, verbose=False, **kwargs):
         qF, qU, pU = self.prior(X=X, verbose=verbose, **kwargs)
         Z = self.get_rate(qF.rsample((E,)))
-        pY = _dist(distributions.Poisson, torch.nn.functional.softplus(self.V) * Z)
+        pY = _count_dist(self, torch.nn.functional.softplus(self.V) * Z)
         return pY, qF, qU, pU
 
     def forward_batched(self, X, idx, E=10, verbose=False, **kwargs):
         qF, qU, pU = self.prior(X=X[idx], verbose=verbose, **kwargs)
         Z = self.get_rate(qF.rsample((E,)))
-        pY = _dist(distributions.Poisson, torch.nn.functional.softplus(self.V[idx]) * Z)
+        pY = _count_dist(self, torch.nn.functional.softplus(self.V[idx]) * Z)
         return pY, qF, qU, pU
 
     def expected_loglik(self, X, y, idx=None, E=10, eps=None, with_lgamma=True, **kwargs):
@@ -483,13 +556,15 @@ class NSF2(PoissonFactorization):
         Xb = X if idx is None else X[idx]
         V = self.V if idx is None else self.V[idx]
         qF, qU, pU = self.prior(X=Xb, **kwargs)
-        ll = poisson_expected_loglik([qF], [torch.nn.functional.softplus(self.W)],
-                                     torch.nn.functional.softplus(V), y, E=E, with_lgamma=with_lgamma, eps=eps)
+        ll = _expected_loglik(self, [qF], [torch.nn.functional.softplus(self.W)], torch.nn.functional.softplus(V), y, E,
+                              with_lgamma, eps)
         return ll, qF, qU, pU
 
     def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
         """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate: a ``PoissonDeviance``.
-        ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors."""
+        ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors.
+        The same for ``likelihood="nb"``: the Poisson deviance of the mean rate is what the nsf paper reports for every
+        likelihood."""
         with torch.no_grad():
             Xb = X if idx is None else X[idx]
             Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
@@ -500,12 +575,13 @@ class NSF2(PoissonFactorization):
 class NSF(nn.Module):
     """Same model with W, V held directly; reference likelihoods.py:227-268."""
 
-    def __init__(self, gp, y, L=10):
+    def __init__(self, gp, y, L=10, likelihood="poisson", theta0=10.0):
         super().__init__()
         D, N = y.shape
         self.gp = gp
         self.W = nn.Parameter(torch.rand((D, L)))
         self.V = nn.Parameter(torch.ones((N,)))
+        _init_likelihood(self, likelihood, theta0, D)
 
     def _rate(self, qF, V, E):
         F = torch.exp(qF.rsample((E,)))
@@ -513,23 +589,25 @@ class NSF(nn.Module):
 
     def forward(self, X, E=10, verbose=False, **kwargs):
         qF, qU, pU = self.gp(X=X, verbose=verbose, **kwargs)
-        return _dist(distributions.Poisson, self._rate(qF, torch.nn.functional.softplus(self.V), E)), qF, qU, pU
+        return _count_dist(self, self._rate(qF, torch.nn.functional.softplus(self.V), E)), qF, qU, pU
 
     def forward_batched(self, X, idx, E=10, verbose=False, **kwargs):
         qF, qU, pU = self.gp(X=X[idx], verbose=verbose, **kwargs)
-        return _dist(distributions.Poisson, self._rate(qF, torch.nn.functional.softplus(self.V)[idx], E)), qF, qU, pU
+        return _count_dist(self, self._rate(qF, torch.nn.functional.softplus(self.V)[idx], E)), qF, qU, pU
 
     def expected_loglik(self, X, y, idx=None, E=10, eps=None, with_lgamma=True, **kwargs):
         Xb = X if idx is None else X[idx]
         V = torch.nn.functional.softplus(self.V)
         qF, qU, pU = self.gp(X=Xb, **kwargs)
-        ll = poisson_expected_loglik([qF], [torch.nn.functional.softplus(self.W)], V if idx is None else V[idx], y,
-                                     E=E, with_lgamma=with_lgamma, eps=eps)
+        ll = _expected_loglik(self, [qF], [torch.nn.functional.softplus(self.W)], V if idx is None else V[idx], y, E,
+                              with_lgamma, eps)
         return ll, qF, qU, pU
 
     def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
         """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate: a ``PoissonDeviance``.
-        ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors."""
+        ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors.
+        The same for ``likelihood="nb"``: the Poisson deviance of the mean rate is what the nsf paper reports for every
+        likelihood."""
         with torch.no_grad():
             Xb = X if idx is None else X[idx]
             Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
@@ -547,11 +625,11 @@ class MGGP_NSF(NSF):
 
     def forward(self, X, groupsX, E=10, verbose=False):
         qF, qU, pU = self._gp(X, groupsX, verbose)
-        return _dist(distributions.Poisson, self._rate(qF, torch.nn.functional.softplus(self.V), E)), qF, qU, pU
+        return _count_dist(self, self._rate(qF, torch.nn.functional.softplus(self.V), E)), qF, qU, pU
 
     def forward_batched(self, X, groupsX, idx, E=10, verbose=False):
         qF, qU, pU = self._gp(X[idx], groupsX[idx], verbose)
-        return _dist(distributions.Poisson, self._rate(qF, torch.nn.functional.softplus(self.V)[idx], E)), qF, qU, pU
+        return _count_dist(self, self._rate(qF, torch.nn.functional.softplus(self.V)[idx], E)), qF, qU, pU
 
     def expected_loglik(self, X, y, groupsX=None, idx=None, E=10, eps=None, with_lgamma=True, **kwargs):
         """Fused training-step form; the group ids follow the sampled spots (``groupsX[idx]``, as in
@@ -561,8 +639,8 @@ class MGGP_NSF(NSF):
         Xb, gb = (X, groupsX) if idx is None else (X[idx], groupsX[idx])
         V = torch.nn.functional.softplus(self.V)
         qF, qU, pU = self._gp(Xb, gb, False)
-        ll = poisson_expected_loglik([qF], [torch.nn.functional.softplus(self.W)], V if idx is None else V[idx], y,
-                                     E=E, with_lgamma=with_lgamma, eps=eps)
+        ll = _expected_loglik(self, [qF], [torch.nn.functional.softplus(self.W)], V if idx is None else V[idx], y, E,
+                              with_lgamma, eps)
         return ll, qF, qU, pU
 
     def deviance(self, X, y, groupsX=None, idx=None, V=None, lognormal_mean=True, **kwargs):
@@ -579,16 +657,17 @@ class MGGP_NSF(NSF):
 class Hybrid_NSF2(nn.Module):
     """Spatial (GP) + non-spatial (GaussianPrior) factors; reference likelihoods.py:100-164."""
 
-    def __init__(self, gp, prior, y, L=10, T=10):
+    def __init__(self, gp, prior, y, L=10, T=10, likelihood="poisson", theta0=10.0):
         super().__init__()
         D, N = y.shape
         self.sf = PoissonFactorization(prior=gp, y=y, L=L)
         self.cf = PoissonFactorization(prior=prior, y=y, L=T)
         self.V = nn.Parameter(torch.ones((N,)))
+        _init_likelihood(self, likelihood, theta0, D)      # one theta per gene for the sum of both factor sets
 
     def _pY(self, qF1, qF2, V, E):
         Z = self.sf.get_rate(qF1.rsample((E,))) + self.cf.get_rate(qF2.rsample((E,)))
-        return _dist(distributions.Poisson, V * Z)
+        return _count_dist(self, V * Z)
 
     def forward(self, X, E=10, verbose=False, **kwargs):
         qF1, qU, pU = self.sf.prior(X=X, verbose=verbose, **kwargs)
@@ -611,8 +690,7 @@ class Hybrid_NSF2(nn.Module):
         qF1, qU, pU = self.sf.prior(X=Xb, **kwargs)
         qF2, pF2 = self.cf.prior() if idx is None else self.cf.prior.forward_batched(idx)
         sp = torch.nn.functional.softplus
-        ll = poisson_expected_loglik([qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], sp(V), y, E=E,
-                                     with_lgamma=with_lgamma, eps=eps)
+        ll = _expected_loglik(self, [qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], sp(V), y, E, with_lgamma, eps)
         return ll, qF1, qU, pU, qF2, pF2
 
     def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
@@ -635,7 +713,7 @@ class Hybrid_NSF_Exact(Hybrid_NSF2):
 
     def _pY(self, qF1, qF2, V, E):
         Z = self.sf.get_rate(qF1.mean + 0.5 * qF1.scale ** 2) + self.cf.get_rate(qF2.mean + 0.5 * qF2.scale ** 2)
-        return _dist(distributions.Poisson, V * Z)
+        return _count_dist(self, V * Z)
 
     def expected_loglik(self, X, y, idx=None, E=10, eps=None, with_lgamma=True, **kwargs):
         """The closed-form objective of THIS class as the reference's loops evaluate it -- not the sampled one of
@@ -651,8 +729,11 @@ class Hybrid_NSF_Exact(Hybrid_NSF2):
         sp = torch.nn.functional.softplus
         m = torch.cat([qF1.mean + 0.5 * qF1.scale ** 2, qF2.mean + 0.5 * qF2.scale ** 2], dim=0)
         zero = torch.zeros_like(m)
-        ll = _loglik_function(y).apply(m, zero, torch.cat([sp(self.sf.W), sp(self.cf.W)], dim=1), sp(V), zero[None], y,
-                                       with_lgamma)
+        Wc = torch.cat([sp(self.sf.W), sp(self.cf.W)], dim=1)
+        if self.likelihood == "nb":
+            ll = _NBLogLik.apply(m, zero, Wc, sp(V), sp(self.theta), zero[None], y, with_lgamma)
+        else:
+            ll = _loglik_function(y).apply(m, zero, Wc, sp(V), zero[None], y, with_lgamma)
         return ll / y.shape[0], qF1, qU, pU, qF2, pF2
 
 
@@ -660,8 +741,8 @@ class Hybrid_NSF(NSF):
     """NSF plus mean-field non-spatial factors held in the module (raw, un-soft-plussed loadings);
     reference likelihoods.py:271-338."""
 
-    def __init__(self, gp, y, L=10, non_spatial_factors=10):
-        super().__init__(gp=gp, y=y, L=L)
+    def __init__(self, gp, y, L=10, non_spatial_factors=10, likelihood="poisson", theta0=10.0):
+        super().__init__(gp=gp, y=y, L=L, likelihood=likelihood, theta0=theta0)
         D, N = y.shape
         self.W2 = nn.Parameter(torch.rand((D, non_spatial_factors)))
         self.mF = nn.Parameter(torch.zeros((non_spatial_factors, N)))
@@ -673,7 +754,7 @@ class Hybrid_NSF(NSF):
         F = torch.exp(torch.cat((qF.rsample((E,)), qF2.rsample((E,))), dim=1))
         Z = torch.matmul(torch.cat((self.W, self.W2), dim=1), F)
         pF2 = _dist(distributions.Normal, torch.zeros_like(mF), torch.ones_like(scale2))
-        return _dist(distributions.Poisson, V * Z), qF2, pF2
+        return _count_dist(self, V * Z), qF2, pF2
 
     def forward(self, X, E=10, verbose=False, **kwargs):
         qF, qU, pU = self.gp(X=X, verbose=verbose, **kwargs)
@@ -695,8 +776,7 @@ class Hybrid_NSF(NSF):
         scale2 = torch.nn.functional.softplus(rs)
         qF2 = _dist(distributions.Normal, mF, scale2)
         pF2 = _dist(distributions.Normal, torch.zeros_like(mF), torch.ones_like(scale2))
-        ll = poisson_expected_loglik([qF, qF2], [self.W, self.W2], V if idx is None else V[idx], y, E=E,
-                                     with_lgamma=with_lgamma, eps=eps)
+        ll = _expected_loglik(self, [qF, qF2], [self.W, self.W2], V if idx is None else V[idx], y, E, with_lgamma, eps)
         return ll, qF, qU, pU, qF2, pF2
 
     def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):

@@ -1296,6 +1296,77 @@ def poisson_nsf(mean, scale, eps, W_pos, V_pos, y, with_lgamma: bool = True):
     return (total, *acc)
 
 
+def nb_nsf_plan(N: int, D: int, Lt: int, E: int) -> dict:
+    """How ``nb_nsf`` covers a shape (gpz_nb_nsf_plan, a host-only query: no device needed): ``factors_padded`` (Lt rounded
+    up to the kernel instance), ``aligned_rows`` (N % 4 == 0: rows of y move 16 bytes at a time), ``gene_slices`` and
+    ``spot_slices`` (partial slabs of the spot pass and of the gene pass), ``workspace_bytes``."""
+    lib = _lib.load()
+    fp, al, gsl, ssl = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib.gpz_nb_nsf_plan(int(N), int(D), int(Lt), int(E), C.byref(fp), C.byref(al), C.byref(gsl), C.byref(ssl))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(factors_padded=fp.value, aligned_rows=bool(al.value), gene_slices=gsl.value, spot_slices=ssl.value,
+                workspace_bytes=int(lib.gpz_nb_nsf_workspace_bytes(int(N), int(D), int(Lt), int(E))))
+
+
+@_on_device
+def nb_nsf(mean, scale, eps, W_pos, V_pos, theta_pos, y, with_lgamma: bool = True):
+    """Fused Monte-Carlo negative-binomial log-likelihood of the NSF models and its gradients (gpz_nb_nsf): the step of
+    ``poisson_nsf`` for pY = NegativeBinomial(total_count=theta[:, None], logits=log(rate) - log(theta[:, None])).
+
+    mean, scale (Lt,N); eps (E,Lt,N); W_pos (D,Lt), V_pos (N,) and theta_pos (D,) positive; y (D,N) dense.  Returns
+    (loglik fp64 scalar, dmean, dscale, dW, dV, dtheta) with the mean over the E samples already applied.
+    Up to 32 samples go through one call; more are split, each part weighted by its share of the samples (the terms
+    that do not depend on the sample then count once).  Nothing here waits for the device: the call can be captured in
+    a graph.  A ``SparseCounts`` raises TypeError: -theta log1p(mu / theta) does not vanish where y = 0, so the step has
+    no O(nnz) form."""
+    from .likelihoods import SparseCounts
+    if isinstance(y, SparseCounts):
+        raise TypeError("nb_nsf: the negative-binomial step takes dense counts (its zero-count term depends on the rate, "
+                        "so there is no sum over the non-zeros): pass y.to_dense()")
+    _need_cuda(mean, scale, eps, W_pos, V_pos, theta_pos, y)
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale, eps, W_pos, V_pos, theta_pos, y = (t.detach().to(f32).contiguous()
+                                                    for t in (mean, scale, eps, W_pos, V_pos, theta_pos, y))
+    # the entry wants 16-byte aligned arrays (include/gpzoo_hip.h); a contiguous view keeps its storage offset
+    mean, scale, eps, W_pos, V_pos, theta_pos, y = (t if t.data_ptr() % 16 == 0 else t.clone()
+                                                    for t in (mean, scale, eps, W_pos, V_pos, theta_pos, y))
+    Lt, N = mean.shape
+    E, D = eps.shape[0], y.shape[0]
+    if scale.shape != (Lt, N) or eps.shape != (E, Lt, N) or W_pos.shape != (D, Lt) or V_pos.shape != (N,) or \
+            theta_pos.shape != (D,) or y.shape != (D, N):
+        raise ValueError(f"nb_nsf: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, eps "
+                         f"{tuple(eps.shape)}, W {tuple(W_pos.shape)}, V {tuple(V_pos.shape)}, theta {tuple(theta_pos.shape)} "
+                         "do not fit together")
+    dev = mean.device
+    eg = 32                                  # samples per call (NMAXE of csrc/nb.hip)
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    acc = [torch.zeros((Lt, N), dtype=f32, device=dev), torch.zeros((Lt, N), dtype=f32, device=dev),
+           torch.zeros((D, Lt), dtype=f32, device=dev), torch.zeros((N,), dtype=f32, device=dev),
+           torch.zeros((D,), dtype=f32, device=dev)]
+    for e0 in range(0, E, eg):
+        ee = min(eg, E - e0)
+        ll = torch.empty(2, dtype=torch.float64, device=dev)
+        out = [torch.empty_like(t) for t in acc]
+        nbytes = lib.gpz_nb_nsf_workspace_bytes(N, D, Lt, ee)
+        if nbytes == 0:
+            raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+        ws = _workspace(dev, nbytes)
+        rc = lib.gpz_nb_nsf(_ptr(mean), _ptr(scale), _ptr(eps[e0:e0 + ee]), _ptr(W_pos), _ptr(V_pos), _ptr(theta_pos),
+                            _ptr(y), N, D, Lt, ee, int(with_lgamma and e0 == 0), _ptr(ll), _ptr(out[0]), _ptr(out[1]),
+                            _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(ws), ws.numel(), _stream(dev))
+        _lib.check(rc, "gpz_nb_nsf")
+        wgt = ee / E
+        # loglik[0] and dtheta carry the sample-independent terms in full in every part: the weights sum to one
+        total += wgt * ll[0]
+        if with_lgamma and e0 == 0:
+            total -= ll[1]          # the parameter-free lgamma(y+1) term is evaluated once
+        for a_, o_ in zip(acc, out):
+            a_.add_(o_, alpha=wgt)
+    return (total, *acc)
+
+
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
     """How ``poisson_nsf_sparse`` covers a shape (gpz_poisson_nsf_sparse_plan, a host-only query: no device needed):
     ``gene_chunk`` (non-zeros of a gene row per wave of the gene pass), ``spot_chunk`` (the same for a spot's column; 0:

@@ -348,8 +348,12 @@ def sharded_nsf_step(gp, X, W_rows_raw, V_raw, y_rows, eps, L: int, *, group=Non
     objective of utilities.py:600-632) on latent + gene shards: ``gp`` holds this rank's latents, ``W_rows_raw`` /
     ``y_rows`` its genes, ``V_raw`` (N,) and ``shared_params`` (e.g. the inducing points) are replicated.  Returns the
     loss  -(E_q log p(y|F) - sum KL)  of the WHOLE model (identical on all ranks); after the call every parameter's
-    ``.grad`` is the single-process gradient (the shards' own, or summed over the ranks for the replicated ones)."""
+    ``.grad`` is the single-process gradient (the shards' own, or summed over the ranks for the replicated ones).
+    The step is Poisson only: a count model built with ``likelihood="nb"`` in place of ``gp`` raises NotImplementedError."""
     import torch.nn.functional as Fn
+    if getattr(gp, "likelihood", "poisson") != "poisson":
+        raise NotImplementedError(f"sharded_nsf_step evaluates the Poisson likelihood only; {type(gp).__name__} was built with "
+                                  f"likelihood={gp.likelihood!r} (train it on one device: the gene-sharded step has no theta)")
     qF, qU, pU = gp(X, **(gp_kwargs or {}))
     ll = sharded_poisson_loglik(qF.mean, qF.scale, Fn.softplus(W_rows_raw), Fn.softplus(V_raw), y_rows, eps, L,
                                 group=group, comm=comm, local=local)

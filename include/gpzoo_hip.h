@@ -41,7 +41,9 @@
  * gpz_poisson_deviance and gpz_poisson_deviance_sparse, each with its *_workspace_bytes and host-only *_plan query -- the
  * Poisson deviance of counts (dense, or stored as their non-zeros) under the predictive mean rate of a fitted factor model,
  * per gene, per spot and in total, with the null model's deviance: the score of held-out spots, which the reference's
- * anndata_to_train_val prepares (Dval) and nothing in it computes.
+ * anndata_to_train_val prepares (Dval) and nothing in it computes;
+ * gpz_nb_nsf, gpz_nb_nsf_workspace_bytes and the host-only gpz_nb_nsf_plan -- the training step of gpz_poisson_nsf under a
+ * negative-binomial likelihood with one inverse dispersion per gene (the nsf paper's lik="nb").
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -292,6 +294,29 @@ int gpz_poisson_nsf(const float* mean, const float* scale, const float* eps, con
                     const float* V, const float* y, int64_t N, int64_t D, int32_t Lt, int32_t E,
                     int32_t with_lgamma, double* loglik, float* dmean, float* dscale, float* dW,
                     float* dV, void* ws, size_t ws_bytes, void* stream);
+
+/* gpz_poisson_nsf under a negative-binomial likelihood (csrc/nb.hip), torch's parameterisation:
+ * NegativeBinomial(total_count = theta[d], logits = log mu - log theta[d]) with mu = V[n] sum_l W[d,l] exp(F[e,l,n]), so
+ * the variance is mu + mu^2 / theta and theta -> infinity is the Poisson step.  theta (D,) positive joins W as a per-gene
+ * operand and dtheta (D,) the gradients; every other argument is as in gpz_poisson_nsf, the mean over E applied.
+ * loglik[0] = (1/E) sum_{e,d,n} [ y log(mu / (mu + theta)) - theta log1p(mu / theta) + lgamma(y + theta) - lgamma(theta) ],
+ * loglik[1] = sum_{d,n} lgamma(y + 1) (0 when with_lgamma == 0): the log-likelihood is loglik[0] - loglik[1].
+ * fp32, the three dense products on v_mfma_f32_16x16x4_f32, log1p compensated, the terms in y and theta alone summed per
+ * gene in fp64 by a pass of their own; the (E, D, N) rate never reaches memory and the workspace holds nothing of D x N
+ * elements.  No floating-point atomics, every sum in a fixed order: two calls agree bit for bit.
+ * 1 <= Lt <= 64, 1 <= E <= 32 per call, D < 2^31, E Lt N < 2^29; N need not be a multiple of 4.  Every array argument and
+ * ws must be 16-byte aligned.  Argument errors (null pointers, extents, Lt, E, a small workspace, alignment) return -1
+ * before any launch; the workspace query then returns 0 and leaves the reason in gpz_last_error.
+ * gpz_nb_nsf_plan (host only, no device needed; any out pointer may be NULL): factors_padded = Lt rounded up to the
+ * kernel instance, aligned_rows = 1 when N % 4 == 0 (rows of y and of the slabs move 16 bytes at a time), gene_slices and
+ * spot_slices = partial slabs of the spot pass and of the gene pass. */
+int gpz_nb_nsf_plan(int64_t N, int64_t D, int32_t Lt, int32_t E, int32_t* factors_padded, int32_t* aligned_rows,
+                    int32_t* gene_slices, int32_t* spot_slices);
+size_t gpz_nb_nsf_workspace_bytes(int64_t N, int64_t D, int32_t Lt, int32_t E);
+int gpz_nb_nsf(const float* mean, const float* scale, const float* eps, const float* W, const float* V,
+               const float* theta, const float* y, int64_t N, int64_t D, int32_t Lt, int32_t E, int32_t with_lgamma,
+               double* loglik, float* dmean, float* dscale, float* dW, float* dV, float* dtheta, void* ws,
+               size_t ws_bytes, void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
