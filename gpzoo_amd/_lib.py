@@ -83,6 +83,11 @@ _SIGNATURES = {
     "gpz_nb_nsf_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "gpz_nb_nsf": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32] +
                    [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_nb_nsf_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6),
+    "gpz_nb_nsf_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "gpz_nb_nsf_sparse": (C.c_int, [C.c_void_p] * 14 + [C.c_int64] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 7 +
+                          [C.c_size_t, C.c_void_p]),
     "gpz_poisson_nsf_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

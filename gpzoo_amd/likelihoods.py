@@ -386,11 +386,34 @@ class _NBLogLik(torch.autograd.Function):
         return g * dmean, g * dscale, g * dW, g * dV, g * dtheta, None, None, None
 
 
+class _SparseNBLogLik(torch.autograd.Function):
+    """_NBLogLik for a SparseCounts (or its view y[:, idx]) through gpz_nb_nsf_sparse."""
+
+    @staticmethod
+    def forward(ctx, mean, scale, W_pos, V_pos, theta_pos, eps, y, with_lgamma):
+        from . import ops
+        ll, dmean, dscale, dW, dV, dtheta = ops.nb_nsf_sparse(mean, scale, eps, W_pos, V_pos, theta_pos, y, None, with_lgamma)
+        ctx.save_for_backward(dmean.to(mean.dtype), dscale.to(scale.dtype), dW.to(W_pos.dtype), dV.to(V_pos.dtype),
+                              dtheta.to(theta_pos.dtype))
+        return ll.to(mean.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        dmean, dscale, dW, dV, dtheta = ctx.saved_tensors
+        return g * dmean, g * dscale, g * dW, g * dV, g * dtheta, None, None, None
+
+
+def _nb_loglik_function(y):
+    """The autograd function of the fused negative-binomial step for this form of the counts (``_loglik_function``'s sibling)."""
+    return _SparseNBLogLik if isinstance(y, SparseCounts) else _NBLogLik
+
+
 def nb_expected_loglik(qF_list, W_list, V_pos, theta_pos, y, E=10, with_lgamma=True, eps=None):
     """``poisson_expected_loglik`` under pY = NegativeBinomial(total_count=theta[:, None], logits=log(rate) - log(theta[:, None])),
     rate = V * sum_k W_k exp(F_k): theta_pos (D,) positive inverse dispersions, variance rate + rate^2 / theta.  ``eps`` is
-    drawn exactly as there.  y: the dense (D, N) counts (gpz_nb_nsf; a ``SparseCounts`` raises TypeError -- the zero-count
-    term depends on the rate, so the step has no sum over the non-zeros)."""
+    drawn exactly as there.  y: the (D, N) counts, dense (gpz_nb_nsf) or a ``SparseCounts`` / its view ``y[:, idx]``
+    (gpz_nb_nsf_sparse: the zero-count term -theta log1p(rate / theta) is a dense pass that reads no counts, the rest a sum
+    over the non-zeros)."""
     mean = torch.cat([q.mean for q in qF_list], dim=0)
     scale = torch.cat([q.scale for q in qF_list], dim=0)
     W = torch.cat(list(W_list), dim=1)
@@ -398,7 +421,7 @@ def nb_expected_loglik(qF_list, W_list, V_pos, theta_pos, y, E=10, with_lgamma=T
         import torch.distributions.normal as tdn
         eps = torch.cat([tdn._standard_normal((E,) + tuple(q.mean.shape), dtype=mean.dtype, device=mean.device)
                          for q in qF_list], dim=1)
-    return _NBLogLik.apply(mean, scale, W, V_pos, theta_pos, eps, y, with_lgamma)
+    return _nb_loglik_function(y).apply(mean, scale, W, V_pos, theta_pos, eps, y, with_lgamma)
 
 
 LIKELIHOODS = ("poisson", "nb")
@@ -529,6 +552,16 @@ class PNMF(PoissonFactorization):
         Z = self.get_rate(qF.rsample((E,)))
         pY = _count_dist(self, torch.nn.functional.softplus(self.V) * Z)
         return pY, qF, pF
+
+    def expected_loglik(self, X, y, idx=None, E=10, eps=None, with_lgamma=True, **kwargs):
+        """Fused form of ``forward``'s ``pY.log_prob(y).mean(0).sum()``: (E_q[log p(y | F)] as a scalar, qF, pF).  ``X`` is
+        accepted for the signature of the spatial models and unused; ``y``: dense counts or a ``SparseCounts`` (for a
+        batch, ``y[:, idx]`` together with ``idx``)."""
+        qF, pF = self.prior() if idx is None else self.prior.forward_batched(idx)
+        V = self.V if idx is None else self.V[idx]
+        ll = _expected_loglik(self, [qF], [torch.nn.functional.softplus(self.W)], torch.nn.functional.softplus(V), y, E,
+                              with_lgamma, eps)
+        return ll, qF, pF
 
 
 class NSF2(PoissonFactorization):
@@ -731,7 +764,7 @@ class Hybrid_NSF_Exact(Hybrid_NSF2):
         zero = torch.zeros_like(m)
         Wc = torch.cat([sp(self.sf.W), sp(self.cf.W)], dim=1)
         if self.likelihood == "nb":
-            ll = _NBLogLik.apply(m, zero, Wc, sp(V), sp(self.theta), zero[None], y, with_lgamma)
+            ll = _nb_loglik_function(y).apply(m, zero, Wc, sp(V), sp(self.theta), zero[None], y, with_lgamma)
         else:
             ll = _loglik_function(y).apply(m, zero, Wc, sp(V), zero[None], y, with_lgamma)
         return ll / y.shape[0], qF1, qU, pU, qF2, pF2

@@ -1432,6 +1432,95 @@ def poisson_nsf_sparse(mean, scale, eps, W_pos, V_pos, counts, idx=None, with_lg
     return total, dmean, dscale, dW, dV
 
 
+def nb_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
+    """How ``nb_nsf_sparse`` covers a shape (gpz_nb_nsf_sparse_plan, a host-only query: no device needed): ``gene_chunk``
+    (non-zeros of a gene row per wave of the gene pass), ``n_gene_chunks`` (length of its work list), ``factors_padded`` and
+    ``zero_factors_padded`` (Lt rounded up to the kernel instance of the non-zero and of the zero passes), ``gene_slices`` and
+    ``spot_slices`` (partial slabs of the zero part's two passes), ``samples_per_group`` and ``zero_samples_per_group``
+    (samples held on chip at a time), ``samples_per_call`` (more are split on the host; the other entries describe the
+    first call), ``workspace_bytes``."""
+    lib = _lib.load()
+    ee = min(int(E), 32)
+    gc, nch = C.c_int32(), C.c_int64()
+    fp, zfp, gsl, ssl, spg, zspg = (C.c_int32() for _ in range(6))
+    rc = lib.gpz_nb_nsf_sparse_plan(int(N), int(B), int(D), int(Lt), ee, int(nnz), C.byref(gc), C.byref(nch), C.byref(fp),
+                                    C.byref(zfp), C.byref(gsl), C.byref(ssl), C.byref(spg), C.byref(zspg))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, n_gene_chunks=nch.value, factors_padded=fp.value, zero_factors_padded=zfp.value,
+                gene_slices=gsl.value, spot_slices=ssl.value, samples_per_group=spg.value,
+                zero_samples_per_group=zspg.value, samples_per_call=ee,
+                workspace_bytes=int(lib.gpz_nb_nsf_sparse_workspace_bytes(int(N), int(B), int(D), int(nnz), int(Lt), ee)))
+
+
+@_on_device
+def nb_nsf_sparse(mean, scale, eps, W_pos, V_pos, theta_pos, counts, idx=None, with_lgamma: bool = True):
+    """``nb_nsf`` for counts held as their non-zeros (gpz_nb_nsf_sparse): the same 6-tuple
+    (loglik fp64 scalar, dmean, dscale, dW, dV, dtheta).  -theta log1p(mu / theta) needs no counts and is a dense pass over the
+    batch; everything that carries a factor y is a sum over the non-zeros.  Nothing of D x B elements exists.
+
+    counts: a ``likelihoods.SparseCounts`` (D, N), or the view ``counts[:, idx]`` of one.  mean, scale (Lt,B); eps (E,Lt,B);
+    W_pos (D,Lt); theta_pos (D,); V_pos (B,) with B = N, or B = len(idx) for a view.  ``idx``: shorthand for ``counts[:, idx]``.
+    Up to 32 samples go through one call; more are split as in ``nb_nsf`` (the sample-independent terms count once).
+    Nothing here waits for the device: the call can be captured in a graph."""
+    from .likelihoods import SparseCounts
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"nb_nsf_sparse: counts must be a SparseCounts, got {type(counts).__name__}")
+    if idx is not None:
+        counts = counts[:, idx]
+    _need_cuda(mean, scale, eps, W_pos, V_pos, theta_pos)
+    dev = mean.device
+    if counts.device != dev:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {counts.device}, the model on {dev}: move them with counts.to(device)")
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale, eps, W_pos, V_pos, theta_pos = (t.detach().to(f32).contiguous()
+                                                 for t in (mean, scale, eps, W_pos, V_pos, theta_pos))
+    # the entry wants 16-byte aligned arrays (include/gpzoo_hip.h); a contiguous view keeps its storage offset
+    mean, scale, eps, W_pos, V_pos, theta_pos = (t if t.data_ptr() % 16 == 0 else t.clone()
+                                                 for t in (mean, scale, eps, W_pos, V_pos, theta_pos))
+    base = counts.base
+    D, N = base.shape
+    if mean.dim() != 2 or eps.dim() != 3:
+        raise ValueError(f"nb_nsf_sparse: mean {tuple(mean.shape)} must be (Lt, B) and eps {tuple(eps.shape)} (E, Lt, B)")
+    Lt, B = mean.shape
+    E = eps.shape[0]
+    if counts.shape != (W_pos.shape[0], B) or scale.shape != (Lt, B) or eps.shape != (E, Lt, B) or \
+            W_pos.shape != (D, Lt) or V_pos.shape != (B,) or theta_pos.shape != (D,):
+        raise ValueError(f"nb_nsf_sparse: counts {tuple(counts.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, "
+                         f"eps {tuple(eps.shape)}, W {tuple(W_pos.shape)}, V {tuple(V_pos.shape)}, theta {tuple(theta_pos.shape)} "
+                         "do not fit together")
+    eg = 32                                  # samples per call (NMAXE of csrc/nb_sparse.hip)
+    total = torch.zeros((), dtype=torch.float64, device=dev)
+    shapes = ((Lt, B), (Lt, B), (D, Lt), (B,), (D,))
+    acc = [torch.zeros(s, dtype=f32, device=dev) for s in shapes] if E > eg else None
+    for e0 in range(0, E, eg):
+        ee = min(eg, E - e0)
+        ll = torch.empty(2, dtype=torch.float64, device=dev)
+        out = [torch.empty(s, dtype=f32, device=dev) for s in shapes]
+        nbytes = lib.gpz_nb_nsf_sparse_workspace_bytes(N, B, D, base.nnz, Lt, ee)
+        if nbytes == 0:
+            raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+        ws = _workspace(dev, nbytes)
+        rc = lib.gpz_nb_nsf_sparse(_ptr(mean), _ptr(scale), _ptr(eps[e0:e0 + ee]), _ptr(W_pos), _ptr(V_pos), _ptr(theta_pos),
+                                   _ptr(base.col_ptr), _ptr(base.col_gene), _ptr(base.col_val), _ptr(base.row_ptr),
+                                   _ptr(base.row_spot), _ptr(base.row_perm), _ptr(counts.idx), _ptr(counts.pos), N, B, D,
+                                   base.nnz, Lt, ee, int(with_lgamma and e0 == 0), _ptr(ll), _ptr(out[0]), _ptr(out[1]),
+                                   _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), _ptr(ws), ws.numel(), _stream(dev))
+        _lib.check(rc, "gpz_nb_nsf_sparse")
+        if E <= eg:                          # one call: its outputs are the result
+            total = ll[0] - ll[1] if with_lgamma else ll[0].clone()
+            return (total, *out)
+        wgt = ee / E
+        # loglik[0] and dtheta carry the sample-independent terms in full in every part: the weights sum to one
+        total += wgt * ll[0]
+        if with_lgamma and e0 == 0:
+            total -= ll[1]          # the parameter-free lgamma(y+1) term is evaluated once
+        for a_, o_ in zip(acc, out):
+            a_.add_(o_, alpha=wgt)
+    return (total, *acc)
+
+
 def _deviance_result(per_gene, per_spot, null_per_gene, scalars):
     return dict(per_gene=per_gene, per_spot=per_spot, null_per_gene=null_per_gene, total=scalars[0], sum_y=scalars[1],
                 sum_mu=scalars[2], null_total=scalars[3])

@@ -103,7 +103,7 @@ def _fused_counts_only(model, y, fused):
     """A SparseCounts has no (E,D,N) form: only the fused step takes it."""
     from .likelihoods import SparseCounts
     if isinstance(y, SparseCounts) and not (fused and hasattr(model, "expected_loglik")):
-        raise TypeError("SparseCounts go through the fused Poisson step only: pass fused=True to a model with "
+        raise TypeError("SparseCounts go through the fused step only: pass fused=True to a model with "
                         "expected_loglik (pY.log_prob(y) needs the dense array, y.to_dense())")
 
 

@@ -43,7 +43,9 @@
  * per gene, per spot and in total, with the null model's deviance: the score of held-out spots, which the reference's
  * anndata_to_train_val prepares (Dval) and nothing in it computes;
  * gpz_nb_nsf, gpz_nb_nsf_workspace_bytes and the host-only gpz_nb_nsf_plan -- the training step of gpz_poisson_nsf under a
- * negative-binomial likelihood with one inverse dispersion per gene (the nsf paper's lik="nb").
+ * negative-binomial likelihood with one inverse dispersion per gene (the nsf paper's lik="nb");
+ * gpz_nb_nsf_sparse, gpz_nb_nsf_sparse_workspace_bytes and the host-only gpz_nb_nsf_sparse_plan -- gpz_nb_nsf for counts
+ * stored as their non-zeros: a dense pass over the batch that reads no counts plus sums over the non-zeros.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -350,6 +352,39 @@ int gpz_poisson_nsf_sparse(const float* mean, const float* scale, const float* e
                            int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t E, int32_t with_lgamma,
                            double* loglik, float* dmean, float* dscale, float* dW, float* dV, void* ws, size_t ws_bytes,
                            void* stream);
+
+/* gpz_nb_nsf for counts stored as their non-zeros (csrc/nb_sparse.hip): the six arrays, idx / pos and the batch convention
+ * of gpz_poisson_nsf_sparse, with theta (D,) and dtheta (D,) as in gpz_nb_nsf.  With x = mu / theta the log-density is
+ *   { -theta log1p(x) }  +  { y log(mu / (mu + theta)) + lgamma(y + theta) - lgamma(theta) - lgamma(y + 1) }:
+ * the first brace needs no counts and runs over every (e, d, n) of the batch on the MFMA passes of gpz_nb_nsf without
+ * their y operand (two transcendentals per element, log1p compensated); the second brace, and every gradient term with
+ * a factor y, is zero where y is and is summed over the stored values of the batch -- one wave per batch spot (value, dV,
+ * dmean, dscale) and one per 512-entry chunk of a gene row (dW, dtheta; the terms of y and theta alone in fp64, by
+ * gpz_nb_nsf's recurrences for integer counts below 16 and lgamma / the digamma series otherwise).  A finishing kernel
+ * adds the two parts in a fixed order.  Outputs as gpz_nb_nsf on the batch's dense counts: loglik[2], dmean, dscale
+ * (Lt, B), dW (D, Lt), dV (B,), dtheta (D,), the mean over E applied.  A stored zero contributes exactly 0.
+ * Nothing of D x B elements is read, written or allocated; the only workspace arrays whose length depends on nnz are per
+ * chunk of the gene pass (D + nnz / gene_chunk entries).  No floating-point atomics, no workgroup waits on another:
+ * two calls agree bit for bit.
+ * 1 <= Lt <= 64, 1 <= E <= 32 per call, E Lt B < 2^29; N, D, nnz < 2^31.  mean, scale, eps, W, V, theta, the outputs and ws
+ * must be 16-byte aligned.  Argument errors (null pointers, extents, Lt, E, a small workspace, alignment) return -1 before
+ * any launch and name the entry in gpz_last_error; the workspace query then returns 0.
+ * gpz_nb_nsf_sparse_plan (host only, no device needed; any out pointer may be NULL): gene_chunk = non-zeros of one gene
+ * row per wave of the gene pass, n_gene_chunks = length of its work list (D + nnz / gene_chunk), factors_padded and
+ * zero_factors_padded = Lt rounded up to the kernel instance of the non-zero passes and of the zero passes, gene_slices and
+ * spot_slices = partial slabs of the zero part's spot pass and gene pass, samples_per_group and zero_samples_per_group =
+ * samples held on chip at a time by the non-zero spot pass and by the zero gene pass. */
+int gpz_nb_nsf_sparse_plan(int64_t N, int64_t B, int64_t D, int32_t Lt, int32_t E, int64_t nnz, int32_t* gene_chunk,
+                           int64_t* n_gene_chunks, int32_t* factors_padded, int32_t* zero_factors_padded,
+                           int32_t* gene_slices, int32_t* spot_slices, int32_t* samples_per_group,
+                           int32_t* zero_samples_per_group);
+size_t gpz_nb_nsf_sparse_workspace_bytes(int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t E);
+int gpz_nb_nsf_sparse(const float* mean, const float* scale, const float* eps, const float* W, const float* V,
+                      const float* theta, const int64_t* col_ptr, const int32_t* col_gene, const float* col_val,
+                      const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const int32_t* idx,
+                      const int32_t* pos, int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t E,
+                      int32_t with_lgamma, double* loglik, float* dmean, float* dscale, float* dW, float* dV,
+                      float* dtheta, void* ws, size_t ws_bytes, void* stream);
 
 /* Poisson deviance under the predictive mean rate of a fitted factor model (csrc/deviance.hip), without materialising the
  * (D, N) rate.  fp32 inputs, fp64 outputs, no gradients.  mean, scale (Lt, N): q(F) moments of all factors at the N spots being
