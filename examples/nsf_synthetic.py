@@ -14,7 +14,9 @@ cent dense) and fits through ``SparseCounts``: the same model and the same loop,
 rate and the share of the null model's deviance it explains (``model.deviance``); it works with ``--sparse-counts`` too.
 
 ``--likelihood nb`` draws overdispersed (gamma-Poisson) counts with a known inverse dispersion per gene, fits the model with
-``likelihood="nb"`` (the fused negative-binomial step) and prints the fitted theta next to the true one.  With
+``likelihood="nb"`` (the fused negative-binomial step) and prints the fitted theta next to the true one; with ``--holdout``
+it also prints the held-out NB deviance, the fraction of the NB null deviance it explains and ``loglik - poisson_loglik``,
+what the dispersion parameter earned on the held-out spots (``model.deviance(..., family="nb")``).  With
 ``--sparse-counts`` the thinned counts are no longer gamma-Poisson with the true theta, so the two columns need not agree.
 """
 import argparse
@@ -133,6 +135,15 @@ def main():
         print("held-out spots:  deviance %.4g (%.4f per entry), explained %.3f, sum mu / sum y %.3f  [%.1f ms]"
               % (total, float(r.mean), explained, float(r.sum_mu / r.sum_y), 1e3 * dt))
         assert total == total and abs(total) != float("inf") and 0.0 < explained < 1.0
+        if a.likelihood == "nb":
+            # the same spots under the model's own likelihood: the NB deviance with the fitted theta, and what theta earned
+            # over Poisson noise at the same rate, in log density (deviances of different families are not comparable)
+            nb = model.deviance(val["X"].to(dev), val["y"].to(dev), V=V_val, family="nb")
+            gain = nb.loglik_per_gene - nb.poisson_loglik_per_gene
+            print("held-out spots:  NB deviance %.4g (%.4f per entry), explained %.3f, loglik - poisson_loglik %.4g "
+                  "(%d of %d genes gain)" % (float(nb.total), float(nb.mean), float(nb.explained),
+                                             float(nb.loglik - nb.poisson_loglik), int((gain > 0).sum()), gain.numel()))
+            assert float(nb.total) == float(nb.total) and abs(float(nb.loglik)) != float("inf")
 
 
 if __name__ == "__main__":

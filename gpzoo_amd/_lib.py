@@ -104,6 +104,16 @@ _SIGNATURES = {
     "gpz_poisson_deviance_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "gpz_poisson_deviance_sparse": (C.c_int, [C.c_void_p] * 12 + [C.c_int64] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 5 +
                                     [C.c_size_t, C.c_void_p]),
+    "gpz_nb_deviance_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32] + [C.POINTER(C.c_int32)] * 5 +
+                             [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "gpz_nb_deviance_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gpz_nb_deviance": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 8 +
+                        [C.c_size_t, C.c_void_p]),
+    "gpz_nb_deviance_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "gpz_nb_deviance_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "gpz_nb_deviance_sparse": (C.c_int, [C.c_void_p] * 13 + [C.c_int64] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 8 +
+                               [C.c_size_t, C.c_void_p]),
     "gpz_knn": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                           C.c_void_p]),
     "gpz_vnngp_workspace_bytes": (C.c_size_t, [C.POINTER(SvgpProblem), C.c_int32]),

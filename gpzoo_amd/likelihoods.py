@@ -503,6 +503,95 @@ def poisson_deviance(qF_list, W_list, V_pos, y, *, lognormal_mean=True):
                                sum_y=r["sum_y"], sum_mu=r["sum_mu"])
 
 
+class NBDeviance(NamedTuple):
+    """What ``nb_deviance`` returns; every tensor is fp64 and carries no graph.  The first ten fields have the names and
+    meanings of ``PoissonDeviance``, for the negative-binomial unit deviance with the per-gene ``theta``.  ``loglik`` is the
+    NB log density of the counts, ``poisson_loglik`` the Poisson log density under the same rate: ``loglik -
+    poisson_loglik`` (in total, or ``loglik_per_gene - poisson_loglik_per_gene``) is what the dispersion parameter earned,
+    in comparable units -- deviances of different families are not comparable."""
+    total: torch.Tensor
+    mean: torch.Tensor
+    per_gene: torch.Tensor
+    per_spot: torch.Tensor
+    null_total: torch.Tensor
+    null_per_gene: torch.Tensor
+    explained: torch.Tensor
+    explained_per_gene: torch.Tensor
+    sum_y: torch.Tensor
+    sum_mu: torch.Tensor
+    loglik: torch.Tensor
+    loglik_per_gene: torch.Tensor
+    loglik_per_spot: torch.Tensor
+    poisson_loglik: torch.Tensor
+    poisson_loglik_per_gene: torch.Tensor
+    theta: torch.Tensor
+
+
+def nb_deviance(qF_list, W_list, V_pos, theta_pos, y, *, lognormal_mean=True):
+    """Negative-binomial scoring of the counts ``y`` under the predictive mean rate of ``poisson_deviance`` and one inverse
+    dispersion ``theta_pos`` (D,) > 0 per gene (variance mu + mu^2 / theta): the unit deviance
+    2 [y log(y / mu) - (y + theta) log1p((y - mu) / (mu + theta))], the log density log NB(y | mu, theta) and the Poisson log
+    density of the same mu, per gene, per spot and in total.
+
+    The null model is one constant rate per gene given V, r_d = sum_n y / sum_n V, with the gene's own theta.  That rate is
+    the null's maximum-likelihood rate when V is constant; otherwise it is a convention, the one ``PoissonDeviance`` uses.
+
+    Arguments as for ``poisson_deviance``; y dense (gpz_nb_deviance) or a ``SparseCounts`` / its view ``y[:, idx]``
+    (gpz_nb_deviance_sparse).  Returns an ``NBDeviance``."""
+    from . import ops
+    with torch.no_grad():
+        mean = torch.cat([q.mean for q in qF_list], dim=0)
+        scale = torch.cat([q.scale for q in qF_list], dim=0)
+        W = torch.cat(list(W_list), dim=1)
+        if isinstance(y, SparseCounts):
+            r = ops.nb_deviance_sparse(mean, scale, W, V_pos, theta_pos, y, None, lognormal_mean)
+        else:
+            r = ops.nb_deviance(mean, scale, W, V_pos, theta_pos, y, lognormal_mean)
+        D, B = y.shape
+        return NBDeviance(total=r["total"], mean=r["total"] / (D * B), per_gene=r["per_gene"], per_spot=r["per_spot"],
+                          null_total=r["null_total"], null_per_gene=r["null_per_gene"],
+                          explained=_explained(r["total"], r["null_total"]),
+                          explained_per_gene=_explained(r["per_gene"], r["null_per_gene"]),
+                          sum_y=r["sum_y"], sum_mu=r["sum_mu"], loglik=r["loglik"], loglik_per_gene=r["loglik_per_gene"],
+                          loglik_per_spot=r["loglik_per_spot"], poisson_loglik=r["poisson_loglik"],
+                          poisson_loglik_per_gene=r["poisson_loglik_per_gene"],
+                          theta=theta_pos.detach().to(torch.float32).double())
+
+
+def _deviance_theta(module, raw_W, family, theta):
+    """The per-gene theta ``deviance`` scores with, or None for the Poisson deviance.  ``family``: "poisson", "nb", or
+    "model" (the model's own likelihood).  ``theta``: positive, a scalar or (D,), in place of softplus(module.theta) --
+    it scores a Poisson-fitted model under a chosen dispersion (a tensor on the device is not checked for its sign: that
+    would wait for the device)."""
+    who = type(module).__name__
+    if family == "model":
+        family = getattr(module, "likelihood", "poisson")
+    if family not in ("poisson", "nb"):
+        raise ValueError(f'{who}.deviance: family must be "poisson", "nb" or "model", got {family!r}')
+    if family == "poisson":
+        if theta is not None:
+            raise ValueError(f'{who}.deviance: theta= belongs to family="nb"')
+        return None
+    D = raw_W.shape[0]
+    if theta is None:
+        raw = getattr(module, "theta", None)
+        if raw is None:
+            raise ValueError(f'{who}.deviance: family="nb" on a model without theta (likelihood="poisson") needs theta=')
+        return torch.nn.functional.softplus(raw.detach())
+    th = torch.as_tensor(theta, dtype=torch.float32) if not isinstance(theta, torch.Tensor) else theta.detach()
+    if th.numel() not in (1, D):
+        raise ValueError(f"{who}.deviance: theta has {th.numel()} values for {D} genes (a scalar or one per gene)")
+    if not th.is_cuda and not bool((th > 0).all()):
+        raise ValueError(f"{who}.deviance: theta must be positive")
+    return th.to(device=raw_W.device, dtype=torch.float32).reshape(-1).expand(D).contiguous()
+
+
+def _deviance_of(qF_list, W_list, Vp, theta_pos, y, lognormal_mean):
+    if theta_pos is None:
+        return poisson_deviance(qF_list, W_list, Vp, y, lognormal_mean=lognormal_mean)
+    return nb_deviance(qF_list, W_list, Vp, theta_pos, y, lognormal_mean=lognormal_mean)
+
+
 def _deviance_size_factors(raw_V, idx, V, n_spots, who):
     """The positive size factors of ``deviance``: the caller's ``V`` or softplus of the model's (indexed by ``idx``)."""
     if V is None:
@@ -593,16 +682,18 @@ class NSF2(PoissonFactorization):
                               with_lgamma, eps)
         return ll, qF, qU, pU
 
-    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, family="poisson", theta=None, **kwargs):
         """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate: a ``PoissonDeviance``.
         ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors.
         The same for ``likelihood="nb"``: the Poisson deviance of the mean rate is what the nsf paper reports for every
-        likelihood."""
+        likelihood.  ``family="nb"`` (or ``"model"`` on an NB model) scores under the negative binomial instead and returns
+        an ``NBDeviance`` with theta = softplus(self.theta), or the positive ``theta=`` (a scalar or (D,))."""
+        theta_pos = _deviance_theta(self, self.W, family, theta)
         with torch.no_grad():
             Xb = X if idx is None else X[idx]
             Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
             qF = self.prior(X=Xb, **kwargs)[0]
-            return poisson_deviance([qF], [torch.nn.functional.softplus(self.W)], Vp, y, lognormal_mean=lognormal_mean)
+            return _deviance_of([qF], [torch.nn.functional.softplus(self.W)], Vp, theta_pos, y, lognormal_mean)
 
 
 class NSF(nn.Module):
@@ -636,16 +727,18 @@ class NSF(nn.Module):
                               with_lgamma, eps)
         return ll, qF, qU, pU
 
-    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, family="poisson", theta=None, **kwargs):
         """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate: a ``PoissonDeviance``.
         ``V=None`` uses softplus(self.V) (indexed by ``idx``); held-out spots need explicit positive size factors.
         The same for ``likelihood="nb"``: the Poisson deviance of the mean rate is what the nsf paper reports for every
-        likelihood."""
+        likelihood.  ``family="nb"`` (or ``"model"`` on an NB model) scores under the negative binomial instead and returns
+        an ``NBDeviance`` with theta = softplus(self.theta), or the positive ``theta=`` (a scalar or (D,))."""
+        theta_pos = _deviance_theta(self, self.W, family, theta)
         with torch.no_grad():
             Xb = X if idx is None else X[idx]
             Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
             qF = self.gp(X=Xb, **kwargs)[0]
-            return poisson_deviance([qF], [torch.nn.functional.softplus(self.W)], Vp, y, lognormal_mean=lognormal_mean)
+            return _deviance_of([qF], [torch.nn.functional.softplus(self.W)], Vp, theta_pos, y, lognormal_mean)
 
 
 class MGGP_NSF(NSF):
@@ -676,15 +769,16 @@ class MGGP_NSF(NSF):
                               with_lgamma, eps)
         return ll, qF, qU, pU
 
-    def deviance(self, X, y, groupsX=None, idx=None, V=None, lognormal_mean=True, **kwargs):
+    def deviance(self, X, y, groupsX=None, idx=None, V=None, lognormal_mean=True, family="poisson", theta=None, **kwargs):
         """``NSF.deviance`` with the group ids of the spots being scored (``groupsX[idx]`` with ``idx``)."""
         if groupsX is None:
             raise TypeError("MGGP_NSF.deviance needs groupsX")
+        theta_pos = _deviance_theta(self, self.W, family, theta)
         with torch.no_grad():
             Xb, gb = (X, groupsX) if idx is None else (X[idx], groupsX[idx])
             Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
             qF = self._gp(Xb, gb, False)[0]
-            return poisson_deviance([qF], [torch.nn.functional.softplus(self.W)], Vp, y, lognormal_mean=lognormal_mean)
+            return _deviance_of([qF], [torch.nn.functional.softplus(self.W)], Vp, theta_pos, y, lognormal_mean)
 
 
 class Hybrid_NSF2(nn.Module):
@@ -726,9 +820,11 @@ class Hybrid_NSF2(nn.Module):
         ll = _expected_loglik(self, [qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], sp(V), y, E, with_lgamma, eps)
         return ll, qF1, qU, pU, qF2, pF2
 
-    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, family="poisson", theta=None, **kwargs):
         """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate of both factor sets: a
-        ``PoissonDeviance``.  The non-spatial factors exist only for the fitted spots: other spots raise ValueError."""
+        ``PoissonDeviance``.  The non-spatial factors exist only for the fitted spots: other spots raise ValueError.
+        ``family`` and ``theta`` as in ``NSF.deviance``."""
+        theta_pos = _deviance_theta(self, self.sf.W, family, theta)
         with torch.no_grad():
             Xb = X if idx is None else X[idx]
             _hybrid_spots(self.V.shape[0], Xb.shape[0], idx, V, type(self).__name__)
@@ -736,7 +832,7 @@ class Hybrid_NSF2(nn.Module):
             qF1 = self.sf.prior(X=Xb, **kwargs)[0]
             qF2 = (self.cf.prior() if idx is None else self.cf.prior.forward_batched(idx))[0]
             sp = torch.nn.functional.softplus
-            return poisson_deviance([qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], Vp, y, lognormal_mean=lognormal_mean)
+            return _deviance_of([qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], Vp, theta_pos, y, lognormal_mean)
 
 
 class Hybrid_NSF_Exact(Hybrid_NSF2):
@@ -812,10 +908,11 @@ class Hybrid_NSF(NSF):
         ll = _expected_loglik(self, [qF, qF2], [self.W, self.W2], V if idx is None else V[idx], y, E, with_lgamma, eps)
         return ll, qF, qU, pU, qF2, pF2
 
-    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, **kwargs):
+    def deviance(self, X, y, idx=None, V=None, lognormal_mean=True, family="poisson", theta=None, **kwargs):
         """Poisson deviance of ``y`` (D, B) at ``X`` (or ``X[idx]``) under the predictive mean rate of both factor sets (raw
         loadings W, W2 as in ``_hybrid``).  The non-spatial factors exist only for the fitted spots: other spots raise
-        ValueError."""
+        ValueError.  ``family`` and ``theta`` as in ``NSF.deviance``."""
+        theta_pos = _deviance_theta(self, self.W, family, theta)
         with torch.no_grad():
             Xb = X if idx is None else X[idx]
             _hybrid_spots(self.V.shape[0], Xb.shape[0], idx, V, type(self).__name__)
@@ -823,4 +920,4 @@ class Hybrid_NSF(NSF):
             mF, rs = (self.mF, self.scale_qF) if idx is None else (self.mF[:, idx], self.scale_qF[:, idx])
             qF = self.gp(X=Xb, **kwargs)[0]
             qF2 = distributions.Normal(mF, torch.nn.functional.softplus(rs), validate_args=False)
-            return poisson_deviance([qF, qF2], [self.W, self.W2], Vp, y, lognormal_mean=lognormal_mean)
+            return _deviance_of([qF, qF2], [self.W, self.W2], Vp, theta_pos, y, lognormal_mean)

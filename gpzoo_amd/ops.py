@@ -1636,6 +1636,124 @@ def poisson_deviance_sparse(mean, scale, W_pos, V_pos, counts, idx=None, lognorm
     return _deviance_result(per_gene, per_spot, null_per_gene, scalars)
 
 
+def _nb_deviance_result(per_gene, per_spot, null_per_gene, ll_gene, ll_spot, pll_gene, scalars):
+    return dict(per_gene=per_gene, per_spot=per_spot, null_per_gene=null_per_gene, loglik_per_gene=ll_gene,
+                loglik_per_spot=ll_spot, poisson_loglik_per_gene=pll_gene, total=scalars[0], sum_y=scalars[1],
+                sum_mu=scalars[2], null_total=scalars[3], loglik=scalars[4], poisson_loglik=scalars[5])
+
+
+def nb_deviance_plan(N: int, D: int, Lt: int) -> dict:
+    """How ``nb_deviance`` covers a shape (gpz_nb_deviance_plan, a host-only query: no device needed); the keys of
+    ``poisson_deviance_plan``."""
+    lib = _lib.load()
+    v = [C.c_int32() for _ in range(5)]
+    tper, fp = C.c_int64(), C.c_int32()
+    rc = lib.gpz_nb_deviance_plan(int(N), int(D), int(Lt), *(C.byref(x) for x in v), C.byref(tper), C.byref(fp))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(spots_per_tile=v[0].value, genes_per_tile=v[1].value, genes_per_block=v[2].value, gene_slices=v[3].value,
+                spot_slices=v[4].value, tiles_per_spot_slice=tper.value, factors_padded=fp.value,
+                workspace_bytes=int(lib.gpz_nb_deviance_workspace_bytes(int(N), int(D), int(Lt))))
+
+
+def nb_deviance_sparse_plan(N: int, B: int, D: int, Lt: int, nnz: int) -> dict:
+    """The same for ``nb_deviance_sparse`` (gpz_nb_deviance_sparse_plan); the keys of ``poisson_deviance_sparse_plan``."""
+    lib = _lib.load()
+    gc, sc, fp, nch = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = lib.gpz_nb_deviance_sparse_plan(int(N), int(B), int(D), int(Lt), int(nnz), C.byref(gc), C.byref(sc), C.byref(nch),
+                                         C.byref(fp))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, spot_chunk=sc.value, n_gene_chunks=nch.value, factors_padded=fp.value,
+                workspace_bytes=int(lib.gpz_nb_deviance_sparse_workspace_bytes(int(N), int(B), int(D), int(nnz), int(Lt))))
+
+
+def _nb_deviance_outputs(D, B, dev):
+    f64 = torch.float64
+    return [torch.empty(n, dtype=f64, device=dev) for n in (D, B, D, D, B, D, 6)]
+
+
+@_on_device
+def nb_deviance(mean, scale, W_pos, V_pos, theta_pos, y, lognormal_mean: bool = True):
+    """Negative-binomial scoring of the counts under the predictive mean rate (gpz_nb_deviance): mu as in
+    ``poisson_deviance``, one inverse dispersion ``theta_pos`` (D,) > 0 per gene;
+    dev = 2 [y log(y / mu) - (y + theta) log1p((y - mu) / (mu + theta))], ll = log NB(y | mu, theta), pll = log Poisson(y | mu).
+
+    Returns a dict of fp64 tensors without a graph: ``per_gene``, ``null_per_gene``, ``loglik_per_gene``,
+    ``poisson_loglik_per_gene`` (D,), ``per_spot``, ``loglik_per_spot`` (N,) and the 0-d ``total``, ``sum_y``, ``sum_mu``,
+    ``null_total``, ``loglik``, ``poisson_loglik``.  The null model has the Poisson null's rate per gene and the gene's own
+    theta.  y is read twice; the (D,N) rate is never materialised.  Nothing here waits for the device."""
+    _need_cuda(mean, scale, W_pos, V_pos, theta_pos, y)
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale = mean.detach().to(f32).contiguous(), scale.detach().to(f32).contiguous()
+    W_pos, V_pos, y = W_pos.detach().to(f32).contiguous(), V_pos.detach().to(f32).contiguous(), y.detach().to(f32).contiguous()
+    theta_pos = theta_pos.detach().to(f32).contiguous()
+    if W_pos.data_ptr() % 16:
+        W_pos = W_pos.clone()            # the entry wants W 16-byte aligned (include/gpzoo_hip.h)
+    Lt, N = mean.shape
+    D = y.shape[0]
+    if (y.shape != (D, N) or scale.shape != (Lt, N) or W_pos.shape != (D, Lt) or V_pos.shape != (N,)
+            or theta_pos.shape != (D,)):
+        raise ValueError(f"nb_deviance: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, "
+                         f"W {tuple(W_pos.shape)}, V {tuple(V_pos.shape)}, theta {tuple(theta_pos.shape)} do not fit together")
+    dev = mean.device
+    outs = _nb_deviance_outputs(D, N, dev)
+    nbytes = lib.gpz_nb_deviance_workspace_bytes(N, D, Lt)
+    if nbytes == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ws = _workspace(dev, nbytes)
+    rc = lib.gpz_nb_deviance(_ptr(mean), _ptr(scale), _ptr(W_pos), _ptr(V_pos), _ptr(theta_pos), _ptr(y), N, D, Lt,
+                             int(bool(lognormal_mean)), *(_ptr(o) for o in outs), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_nb_deviance")
+    return _nb_deviance_result(*outs)
+
+
+@_on_device
+def nb_deviance_sparse(mean, scale, W_pos, V_pos, theta_pos, counts, idx=None, lognormal_mean: bool = True):
+    """``nb_deviance`` for counts held as their non-zeros (gpz_nb_deviance_sparse): the same dict, as one dense pass over the
+    batch that reads no counts plus sums over the stored values.
+
+    counts: a ``likelihoods.SparseCounts`` (D, N), or the view ``counts[:, idx]`` of one.  mean, scale (Lt,B); W_pos (D,Lt);
+    V_pos (B,); theta_pos (D,); the per-spot outputs follow the view's order.  ``idx``: shorthand for ``counts[:, idx]``.
+    Nothing here waits for the device."""
+    from .likelihoods import SparseCounts
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"nb_deviance_sparse: counts must be a SparseCounts, got {type(counts).__name__}")
+    if idx is not None:
+        counts = counts[:, idx]
+    _need_cuda(mean, scale, W_pos, V_pos, theta_pos)
+    dev = mean.device
+    if counts.device != dev:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {counts.device}, the model on {dev}: move them with counts.to(device)")
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale = mean.detach().to(f32).contiguous(), scale.detach().to(f32).contiguous()
+    W_pos, V_pos = W_pos.detach().to(f32).contiguous(), V_pos.detach().to(f32).contiguous()
+    theta_pos = theta_pos.detach().to(f32).contiguous()
+    if W_pos.data_ptr() % 16:
+        W_pos = W_pos.clone()
+    base = counts.base
+    D, N = base.shape
+    Lt, B = mean.shape
+    if (counts.shape != (W_pos.shape[0], B) or scale.shape != (Lt, B) or W_pos.shape != (D, Lt) or V_pos.shape != (B,)
+            or theta_pos.shape != (D,)):
+        raise ValueError(f"nb_deviance_sparse: counts {tuple(counts.shape)}, mean {tuple(mean.shape)}, "
+                         f"scale {tuple(scale.shape)}, W {tuple(W_pos.shape)}, V {tuple(V_pos.shape)}, "
+                         f"theta {tuple(theta_pos.shape)} do not fit together")
+    outs = _nb_deviance_outputs(D, B, dev)
+    nbytes = lib.gpz_nb_deviance_sparse_workspace_bytes(N, B, D, base.nnz, Lt)
+    if nbytes == 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ws = _workspace(dev, nbytes)
+    rc = lib.gpz_nb_deviance_sparse(_ptr(mean), _ptr(scale), _ptr(W_pos), _ptr(V_pos), _ptr(theta_pos), _ptr(base.col_ptr),
+                                    _ptr(base.col_gene), _ptr(base.col_val), _ptr(base.row_ptr), _ptr(base.row_spot),
+                                    _ptr(base.row_perm), _ptr(counts.idx), _ptr(counts.pos), N, B, D, base.nnz, Lt,
+                                    int(bool(lognormal_mean)), *(_ptr(o) for o in outs), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_nb_deviance_sparse")
+    return _nb_deviance_result(*outs)
+
+
 def profile_enable(on: bool = True):
     _lib.check(_lib.load().gpz_profile_enable(int(on)), "gpz_profile_enable")
 

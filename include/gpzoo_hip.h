@@ -45,7 +45,9 @@
  * gpz_nb_nsf, gpz_nb_nsf_workspace_bytes and the host-only gpz_nb_nsf_plan -- the training step of gpz_poisson_nsf under a
  * negative-binomial likelihood with one inverse dispersion per gene (the nsf paper's lik="nb");
  * gpz_nb_nsf_sparse, gpz_nb_nsf_sparse_workspace_bytes and the host-only gpz_nb_nsf_sparse_plan -- gpz_nb_nsf for counts
- * stored as their non-zeros: a dense pass over the batch that reads no counts plus sums over the non-zeros.
+ * stored as their non-zeros: a dense pass over the batch that reads no counts plus sums over the non-zeros;
+ * gpz_nb_deviance and gpz_nb_deviance_sparse, each with its *_workspace_bytes and host-only *_plan query -- the NB deviance,
+ * the NB log density and the Poisson log density of held-out counts under the predictive mean rate and a per-gene theta.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -434,6 +436,47 @@ int gpz_poisson_deviance_sparse(const float* mean, const float* scale, const flo
                                 int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t lognormal_mean,
                                 double* per_gene, double* per_spot, double* null_per_gene, double* scalars, void* ws,
                                 size_t ws_bytes, void* stream);
+
+/* Held-out scoring under a negative-binomial likelihood with one inverse dispersion theta[d] > 0 per gene (torch's
+ * NegativeBinomial(total_count = theta, logits = log mu - log theta)) and the predictive mean rate of gpz_poisson_deviance,
+ * mu[d,n] = V[n] sum_l W[d,l] m[l,n]: the interface of gpz_poisson_deviance plus theta (D,).
+ *   dev = 2 [ y log(y / mu) - (y + theta) log1p((y - mu) / (mu + theta)) ]        (the first term exactly 0 at y = 0)
+ *   ll  = lgamma(y + theta) - lgamma(theta) - lgamma(y + 1) + y log(mu / (mu + theta)) - theta log1p(mu / theta)
+ *   pll = y log mu - mu - lgamma(y + 1)                                            (the Poisson log density of the same mu)
+ * per_gene, null_per_gene, loglik_per_gene, poisson_loglik_per_gene (D,), per_spot, loglik_per_spot (N,) and
+ * scalars[6] = {total, sum y, sum mu, null total, loglik, poisson loglik}, all fp64.  The null model is mu0[d,n] = V[n] r_d
+ * with the Poisson null's rate r_d = sum_n y / sum_n V and the gene's own theta (the maximum-likelihood rate when V is
+ * constant, a convention otherwise); null_per_gene is exactly 0 for a gene without counts.
+ * fp32 element-wise work (a compensated log1p), the lgamma terms and every sum in fp64 in a fixed order, no atomics: two calls
+ * agree bit for bit.  y is read twice (sum_n y must be known before the null deviance can be evaluated); the (D, N) rate never
+ * exists in memory and the workspace holds nothing of D x N elements.  Limits, alignment and the error contract are those of
+ * gpz_poisson_deviance; a null theta is rejected with a message of its own.  gpz_nb_deviance_plan answers like
+ * gpz_poisson_deviance_plan. */
+int gpz_nb_deviance_plan(int64_t N, int64_t D, int32_t Lt, int32_t* spots_per_tile, int32_t* genes_per_tile,
+                         int32_t* genes_per_block, int32_t* gene_slices, int32_t* spot_slices, int64_t* tiles_per_spot_slice,
+                         int32_t* factors_padded);
+size_t gpz_nb_deviance_workspace_bytes(int64_t N, int64_t D, int32_t Lt);
+int gpz_nb_deviance(const float* mean, const float* scale, const float* W, const float* V, const float* theta, const float* y,
+                    int64_t N, int64_t D, int32_t Lt, int32_t lognormal_mean, double* per_gene, double* per_spot,
+                    double* null_per_gene, double* loglik_per_gene, double* loglik_per_spot, double* poisson_loglik_per_gene,
+                    double* scalars, void* ws, size_t ws_bytes, void* stream);
+
+/* gpz_nb_deviance for counts stored as their non-zeros; the argument layout of gpz_poisson_deviance_sparse plus theta.  With
+ * z(mu) = theta log1p(mu / theta) every output is a zero part over ALL (d, n) of the batch -- 2 z for the deviance, -z for the
+ * log density, -mu for the Poisson log density, from one dense pass that reads no counts -- plus a sum over the stored values:
+ *   dev: 2 [ y log(y (mu + theta) / (mu (y + theta))) - theta log1p(y / theta) ]
+ *   ll:  y log(mu / (mu + theta)) + lgamma(y + theta) - lgamma(theta) - lgamma(y + 1);      pll: y log mu - lgamma(y + 1)
+ * The null model's rate comes first from a pass over the gene rows' stored entries.  The workspace holds nothing of D x B or
+ * nnz elements.  Same contract as gpz_poisson_deviance_sparse; gpz_nb_deviance_sparse_plan answers like its plan query. */
+int gpz_nb_deviance_sparse_plan(int64_t N, int64_t B, int64_t D, int32_t Lt, int64_t nnz, int32_t* gene_chunk,
+                                int32_t* spot_chunk, int64_t* n_gene_chunks, int32_t* factors_padded);
+size_t gpz_nb_deviance_sparse_workspace_bytes(int64_t N, int64_t B, int64_t D, int64_t nnz, int32_t Lt);
+int gpz_nb_deviance_sparse(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                           const int64_t* col_ptr, const int32_t* col_gene, const float* col_val, const int64_t* row_ptr,
+                           const int32_t* row_spot, const int32_t* row_perm, const int32_t* idx, const int32_t* pos, int64_t N,
+                           int64_t B, int64_t D, int64_t nnz, int32_t Lt, int32_t lognormal_mean, double* per_gene,
+                           double* per_spot, double* null_per_gene, double* loglik_per_gene, double* loglik_per_spot,
+                           double* poisson_loglik_per_gene, double* scalars, void* ws, size_t ws_bytes, void* stream);
 
 /* K nearest rows of Z for every row of X, ascending by (Euclidean distance, index): the neighbour
  * bookkeeping of VNNGP, argsort(cdist(X, Z))[:, :K] (gp.py:31, 64).  idx (N,K) int64.  K <= 32. */
