@@ -9,6 +9,11 @@
  *  - plain pointers and sizes only; every pointer is DEVICE memory owned by the
  *    caller unless marked "host"; the library never allocates user-visible
  *    memory; scratch comes from a caller workspace sized by *_workspace_bytes.
+ *  - the workspace need not be cleared by the caller and may hold anything (every entry writes, or clears, each part
+ *    of it before reading it); outputs are fully written on success except where stated: the opaque buffers
+ *    wt_cache (the unused columns of a short last chunk's slot stay untouched), factor_cache and the VNNGP state
+ *    (blocks above the diagonal of the inverse factor are neither stored nor loaded) -- DESIGN.md, "Scratch and
+ *    output initialisation".
  *  - all launches are asynchronous on `stream` (a hipStream_t passed as void*).
  *  - return 0 on success, negative on bad arguments / launch errors
  *    (gpz_last_error() holds the message, per thread).
