@@ -49,13 +49,44 @@ typedef float dvf4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ dvf4 dv_mfma(float a, float b, dvf4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
-// The element-wise part.  y log(y / mu) as y ln2 (log2 y - log2 mu): log2 y also serves the null model's y log y.
+// log1p(x), x >= 0, compensated for the rounding of 1 + x (log1p_c of nb_deviance.hip): u = 1 + x, log(u) + (x - (u - 1)) / u;
+// below 2^-12 the series x - x^2 / 2 + x^3 / 3.
+__device__ __forceinline__ float dv_log1p(float x) {
+  const float u = 1.f + x;
+  const float big = __builtin_fmaf(DV_LN2, __builtin_amdgcn_logf(u), (x - (u - 1.f)) * __builtin_amdgcn_rcpf(u));
+  const float small = x * __builtin_fmaf(x, __builtin_fmaf(x, 1.f / 3.f, -0.5f), 1.f);
+  return x < 0x1p-12f ? small : big;
+}
+
+// y log(y / mu), y > 0, as a log1p of a non-negative argument on either side of y = mu:
+//   y >= mu:  y log1p((y - mu) / mu),      y < mu:  -y log1p((mu - y) / y).
+// The difference of two logarithms loses what the deviance is made of where a large count lies next to its rate: at
+// y ~ mu ~ 1e4 the unit deviance is about 1 while y log y ~ 1e5 is rounded to 0.008, and log2 y - log2 mu carries the
+// absolute error of both logarithms.  y - mu is exact there, so this form keeps the relative error of one log1p.
+__device__ __forceinline__ float dv_ylog_ratio(float y, float mu) {
+  const bool up = y >= mu;
+  const float l = dv_log1p(fabsf(y - mu) * __builtin_amdgcn_rcpf(up ? mu : y));
+  return up ? y * l : -y * l;
+}
+
+// The same for a stored count of the sparse entry, with the rate in fp64.  There sum mu over ALL (d, n) enters in fp64
+// through the factorisation and a stored count adds 2 (y log(y / mu) - y), which is -2 mu to first order: the two meet
+// only if the stored term sees the rate the factorisation sums, so the dot product and y - mu are formed in fp64 (an
+// fp32 dot product is off by an ulp of mu, 1e-3 at mu = 1e4, per stored count); the logarithm stays fp32.
+__device__ __forceinline__ float dv_ylog_ratio(float y, double mu) {
+  const bool up = (double)y >= mu;
+  const float l = dv_log1p((float)fabs((double)y - mu) * __builtin_amdgcn_rcpf(up ? (float)mu : y));
+  return up ? y * l : -y * l;
+}
+
+// The element-wise part: 2 (y log(y / mu) - (y - mu)), the difference y - mu formed first (y log(y / mu) is y - mu to first
+// order, and either is small beside y); y ln2 log2 y serves the null model's y log y.
 struct DvTerm { float dev, yly; };
 __device__ __forceinline__ DvTerm dv_term(float y, float mu) {
   const bool pos = y > 0.f;
   const float l2y = __builtin_amdgcn_logf(pos ? y : 1.f), yl = y * DV_LN2;
-  const float t = pos ? yl * (l2y - __builtin_amdgcn_logf(mu)) : 0.f;
-  return DvTerm{2.f * ((t - y) + mu), yl * l2y};
+  const float t = pos ? dv_ylog_ratio(pos ? y : 1.f, mu) : 0.f;
+  return DvTerm{2.f * (t - (y - mu)), yl * l2y};
 }
 
 template <typename T>
@@ -449,11 +480,10 @@ __global__ __launch_bounds__(256) void dv_sp_spot_kernel(DevSpArgs a) {
     if (y == 0.f) continue;                 // an explicit zero: 0 log(.) is never formed
     float w[LT];
     dv_load_w<LT>(a.W, a.col_gene[k], a.Lt, w);
-    float z = 0.f;
+    double z = 0.0;
 #pragma unroll
-    for (int l = 0; l < LT; ++l) z = __builtin_fmaf(w[l], m[l], z);
-    const float t = y * DV_LN2 * (__builtin_amdgcn_logf(y) - __builtin_amdgcn_logf(vn * z));
-    acc += (double)(2.f * (t - y));
+    for (int l = 0; l < LT; ++l) z = __builtin_fma((double)w[l], (double)m[l], z);
+    acc += 2.0 * ((double)dv_ylog_ratio(y, (double)vn * z) - (double)y);
   }
   acc = dv_wave_sum(acc);
   const double cm = dv_wave_sum(lane < LT ? a.cD[lane] * (double)a.mT[j * LT + lane] : 0.0);
@@ -498,27 +528,32 @@ __global__ __launch_bounds__(256) void dv_sp_gene_kernel(DevSpArgs a) {
   float w[LT];
   dv_load_w<LT>(a.W, g, a.Lt, w);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};           // at most 8 entries per lane
+  double ys = 0.0;                               // sum y, exact: it meets sum y log(y / mu) below
   for (int i = lane; i < cnt; i += 64) {
     const int64_t j = lj[wave][i];
     const float y = ly[wave][i];
     const dvf4* mp = reinterpret_cast<const dvf4*>(a.mT + j * LT);
-    float z = 0.f;
+    double z = 0.0;
 #pragma unroll
     for (int l = 0; l < LT; l += 4) {
       const dvf4 v = mp[l / 4];
-      z = __builtin_fmaf(w[l], v[0], z); z = __builtin_fmaf(w[l + 1], v[1], z);
-      z = __builtin_fmaf(w[l + 2], v[2], z); z = __builtin_fmaf(w[l + 3], v[3], z);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) z = __builtin_fma((double)w[l + i], (double)v[i], z);
     }
     const float l2y = __builtin_amdgcn_logf(y), yl = y * DV_LN2;
-    acc[0] += 2.f * (yl * (l2y - __builtin_amdgcn_logf(a.V[j] * z)) - y);
-    acc[1] += y;
+    acc[0] += dv_ylog_ratio(y, (double)a.V[j] * z);
+    ys += (double)y;
     acc[2] += yl * l2y;
     acc[3] += y * a.lV[j];
   }
+  // part[0] = sum 2 (y log(y / mu) - y): the two sums meet in fp64 (y log(y / mu) is small beside y next to y = mu)
+  double t[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double t = dv_wave_sum((double)acc[k]);
-    if (lane == 0) a.part[wi * 4 + k] = t;
+  for (int k = 0; k < 4; ++k) t[k] = dv_wave_sum(k == 1 ? ys : (double)acc[k]);
+  t[0] = 2.0 * (t[0] - t[1]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a.part[wi * 4 + k] = t[k];
   }
 }
 

@@ -7,17 +7,18 @@
 //   mu[d,n]  = V[n] sum_l W[d,l] m[l,n]
 //   dev[d,n] = 2 [ y log(y / mu) - (y + theta) log1p((y - mu) / (mu + theta)) ]      (the first term exactly 0 at y = 0)
 //   ll[d,n]  = lgamma(y + theta) - lgamma(theta) - lgamma(y + 1) + y log(mu / (mu + theta)) - theta log1p(mu / theta)
-//   pll[d,n] = y log mu - mu - lgamma(y + 1)
+//   pll[d,n] = y log mu - mu - lgamma(y + 1)  =  -(y log(y / mu) - y + mu) - [lgamma(y + 1) - (y log y - y)]
 //   null model mu0[d,n] = V[n] r_d, r_d = sum_n y[d,n] / sum_n V[n] (the Poisson null's rate, with the gene's own theta):
 //   the same dev with mu0 in place of mu; exactly 0 for a gene without counts.
 //
-// The second term of the deviance is evaluated with a non-negative argument on either side of y = mu,
-//   y >= mu:  -(y + theta) log1p((y - mu) / (mu + theta)),      y < mu:  +(y + theta) log1p((mu - y) / (y + theta))
-// (the same number: (y + theta) / (mu + theta) is one plus the first argument and the reciprocal of one plus the second), so
-// the argument never approaches -1 and y = 0 gives 2 theta log1p(mu / theta) by the same code.  log1p is the compensated
-// one of nb.hip: u = 1 + x, log1p(x) = log(u) + (x - (u - 1)) / u.
+// The deviance is evaluated as 2 (y A - theta B), A = log(y (mu + theta) / (mu (y + theta))), B = log((y + theta) / (mu + theta)),
+// each a log1p with a non-negative argument on either side of y = mu (unit_dev), so no argument approaches -1, y = 0 gives
+// 2 theta log1p(mu / theta) by the same code, and neither a small theta nor a large count next to its rate costs digits.
+// log1p is the compensated one of nb.hip: u = 1 + x, log1p(x) = log(u) + (x - (u - 1)) / u.  The Poisson log density is
+// formed as minus half the Poisson unit deviance, whose y log(y / mu) = y (A + B) comes with the NB deviance, minus
+// Stirling's remainder of lgamma(y + 1), a term in y alone.
 //
-// The lgamma terms depend on y and theta only.  For integer counts below 16 they come from a per-gene table in fp64
+// The lgamma terms (and Stirling's remainder) depend on y and theta only.  For integer counts below 16 they come from a per-gene table in fp64
 // (lgamma(y + theta) - lgamma(theta) = sum_{k<y} log(theta + k), the recurrence of nb.hip); every other count takes the fp64
 // lgamma.  They are summed in fp64, per gene and per spot, by a pass of their own that also forms sum_n y -- the null
 // model's rate has to be known before the element-wise pass, so y is read twice.
@@ -25,7 +26,8 @@
 // Dense (gpz_nb_deviance), fp32 element-wise work, fp64 sums, no atomics, every sum in a fixed order:
 //   nd_factors_kernel   m (Lt, N); V padded to whole tiles
 //   nd_vsum_kernel      sum_n V[n]
-//   nd_table_kernel     T[d][y], y < 16; lgamma(theta[d]); lgamma(y + 1), y < 16
+//   nd_table_kernel     T[d][y] = lgamma(y + theta) - lgamma(theta) - lgamma(y + 1), y < 16; lgamma(theta[d]); Stirling's
+//                       remainder lgamma(y + 1) - (y log y - y), y < 16
 //   nd_const_kernel     grid (ceil(D / 64), spot slices): sum y and the lgamma sums per gene and slice, per spot and gene block
 //   nd_rate_kernel      per gene: the slices in order, r_d
 //   nd_tile_kernel      the tile scheme of dv_tile_kernel (16 genes x 64 spots per wave on v_mfma_f32_16x16x4_f32, spots as
@@ -37,7 +39,7 @@
 // Sparse (gpz_nb_deviance_sparse).  With z(mu) = theta log1p(mu / theta):
 //   dev = 2 z(mu) over ALL (d, n) + sum_stored 2 [ y log(y (mu + theta) / (mu (y + theta))) - theta log1p(y / theta) ]
 //   ll  = - z(mu) over ALL (d, n) + sum_stored [ y log(mu / (mu + theta)) + lgamma terms ]
-//   pll = - mu    over ALL (d, n) + sum_stored [ y log mu - lgamma(y + 1) ]
+//   pll = - mu    over ALL (d, n) + sum_stored [ y - y log(y / mu) - Stirling's remainder ]
 // One dense zero pass (nd_tile_kernel without counts) gives sum z, sum mu and the null's sum z(V r_d) per gene and sum z
 // per spot; r_d comes first from a pass over the gene rows' stored entries (nds_const_kernel, O(nnz)).  The corrections
 // use the work split of deviance.hip's sparse half: one wave per batch spot, one wave per chunk of at most 512
@@ -55,7 +57,7 @@ constexpr int BG = 64;            // genes per workgroup (4 waves): one per-spot
 constexpr int CHUNK = 512;        // sparse: non-zeros of one gene row per wave
 constexpr int TAB = 16;           // integer counts below this take the lgamma terms from the table
 constexpr int TROW = TAB + 2;     // a gene's table row: T[0 .. 15], lgamma(theta), theta
-constexpr int CQ = 3;             // per-gene sums of the const pass: y, lgamma(y + theta) - lgamma(theta), lgamma(y + 1)
+constexpr int CQ = 3;             // per-gene sums of the const pass: y and const_terms' cl and st
 constexpr int GQ = 5;             // per-gene sums of the tile pass: deviance, mu, null deviance, ll and pll rate parts
 constexpr int ZQ = 3;             // per-gene sums of the zero pass: z(mu), mu, z(mu0)
 constexpr int NSCAL = 6;          // total, sum y, sum mu, null total, loglik, poisson loglik
@@ -81,36 +83,54 @@ __device__ __forceinline__ float log1p_c(float x) {
   return x < 0x1p-12f ? small : big;
 }
 
-// the unit NB deviance; l2y = log2(y) (0 at y = 0), l2mu = log2(mu)
-__device__ __forceinline__ float unit_dev(float y, float l2y, float mu, float l2mu, float th) {
-  const bool up = y >= mu;
-  const float x = fabsf(y - mu) * __builtin_amdgcn_rcpf((up ? mu : y) + th);
-  const float s = (y + th) * log1p_c(x);
-  const float t = y > 0.f ? y * LN2 * (l2y - l2mu) : 0.f;
-  return 2.f * (up ? t - s : t + s);
+// The unit NB deviance and y log(y / mu).  With lo = min(y, mu), hi = max(y, mu), d = hi - lo:
+//   A = log1p(theta d / (lo (hi + theta)))  = |log(y (mu + theta) / (mu (y + theta)))|      (not formed at y = 0)
+//   B = log1p(d / (lo + theta))             = |log((y + theta) / (mu + theta))|
+//   dev = 2 (y A - theta B) for y >= mu, 2 (theta B - y A) for y < mu;   y log(y / mu) = +- y (A + B).
+// This is dev = 2 [y log(y / mu) - (y + theta) log((y + theta) / (mu + theta))] with the two terms in y taken together: apart,
+// they agree to theta / y of their size where theta << mu (theta = 1e-2 at counts of 1e4: six digits lost), and
+// y log(y / mu) from two logarithms loses a large count next to its rate (see dv_ylog_ratio of deviance.hip).  Every log1p
+// has a non-negative argument; what is left to cancel, y A against theta B, is the deviance being of second order in d / mu.
+struct Unit { float dev, yl; };
+__device__ __forceinline__ Unit unit_dev(float y, float mu, float th) {
+  const bool up = y >= mu, pos = y > 0.f;
+  const float d = fabsf(y - mu), lo = up ? mu : y, hi = up ? y : mu;
+  const float b = log1p_c(d * __builtin_amdgcn_rcpf(lo + th));
+  const float a = log1p_c(th * d * __builtin_amdgcn_rcpf((pos ? lo : 1.f) * (hi + th)));
+  const float ya = pos ? y * a : 0.f, tb = th * b;
+  return Unit{2.f * (up ? ya - tb : tb - ya), pos ? (up ? y * (a + b) : -y * (a + b)) : 0.f};
 }
 
-// a stored count's corrections to the zero parts: the deviance's, the log density's and the Poisson log density's (the
-// lgamma terms apart)
+// a stored count's corrections to the zero parts 2 z(mu), -z(mu), -mu: the deviance's, 2 (+- y A - theta log1p(y / theta)) with
+// the A of unit_dev; the log density's (the lgamma terms apart); and the Poisson log density's, y - y log(y / mu) -- with
+// the zero part -(y log(y / mu) - y + mu), half the Poisson unit deviance; the terms in y alone are const_terms' st
 struct Corr { float dev, ll, pl; };
 __device__ __forceinline__ Corr stored_corr(float y, float mu, float th, float ith, float l2th) {
-  const float l2y = __builtin_amdgcn_logf(y), l2mu = __builtin_amdgcn_logf(mu);
+  const float l2mu = __builtin_amdgcn_logf(mu);
   const float lm = log1p_c(mu * ith), ly = log1p_c(y * ith);
+  const bool up = y >= mu;
+  const float d = fabsf(y - mu), lo = up ? mu : y, hi = up ? y : mu;
+  const float ya = y * log1p_c(th * d * __builtin_amdgcn_rcpf(lo * (hi + th)));
+  const float yl = y * log1p_c(d * __builtin_amdgcn_rcpf(lo));
   Corr c;
-  c.dev = 2.f * (y * (LN2 * (l2y - l2mu) + (lm - ly)) - th * ly);
+  c.dev = 2.f * ((up ? ya : -ya) - th * ly);
   c.ll = y * (LN2 * (l2mu - l2th) - lm);
-  c.pl = y * LN2 * l2mu;
+  c.pl = y - (up ? yl : -yl);
   return c;
 }
 
-// lgamma(y + theta) - lgamma(theta) and lgamma(y + 1) of a count y != 0: the gene's table row and the factorial table for
-// an integer below TAB, the fp64 lgamma otherwise
-struct Const { double cth, lg; };
+// The terms of a count y != 0 that depend on y and theta only, in fp64:
+//   cl = lgamma(y + theta) - lgamma(theta) - lgamma(y + 1)      the NB log density's
+//   st = lgamma(y + 1) - (y log y - y)                          the Poisson log density's: pll = -(y log(y / mu) - y + mu) - st,
+// Stirling's remainder (log(2 pi y) / 2 + ...), so that the rate part of pll is minus half a unit deviance and nothing of
+// the size y log y is rounded to fp32.  The gene's table row and the table of st for an integer below TAB, the fp64
+// lgamma and log otherwise.
+struct Const { double cl, st; };
 __device__ __forceinline__ Const const_terms(float y1, const double* row, const double* lf) {
   const int yi = (int)y1;
   if (y1 == (float)yi && yi > 0 && yi < TAB) return Const{row[yi], lf[yi]};
-  const double yd = (double)y1;
-  return Const{lgamma(yd + row[TAB + 1]) - row[TAB], lgamma(yd + 1.0)};
+  const double yd = (double)y1, lg = lgamma(yd + 1.0);
+  return Const{lgamma(yd + row[TAB + 1]) - row[TAB] - lg, lg - yd * (log(yd) - 1.0)};
 }
 
 __global__ __launch_bounds__(256) void nd_vsum_kernel(const float* V, int64_t n, double* out) {
@@ -121,10 +141,10 @@ __global__ __launch_bounds__(256) void nd_vsum_kernel(const float* V, int64_t n,
   if (threadIdx.x == 0) out[0] = t;
 }
 
-// T [D][TROW] and lf [TAB]
+// T [D][TROW]: const_terms' cl for y < TAB, lgamma(theta), theta; lf [TAB]: const_terms' st for y < TAB
 __global__ __launch_bounds__(256) void nd_table_kernel(const float* theta, int64_t D, double* T, double* lf) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < TAB) lf[i] = lgamma((double)i + 1.0);
+  if (i < TAB) lf[i] = i > 0 ? lgamma((double)i + 1.0) - (double)i * (log((double)i) - 1.0) : 0.0;
   if (i >= D * TROW) return;
   const int64_t d = i / TROW;
   const int j = (int)(i - d * TROW);
@@ -135,8 +155,8 @@ __global__ __launch_bounds__(256) void nd_table_kernel(const float* theta, int64
   else if (th > 1e-20 && th < 1e8) {
     double p = 1.0;
     for (int k = 0; k < j; ++k) p *= th + k;      // <= 1e8^15
-    v = log(p);
-  } else v = lgamma(th + j) - lgamma(th);
+    v = log(p) - lgamma((double)j + 1.0);
+  } else v = lgamma(th + j) - lgamma(th) - lgamma((double)j + 1.0);
   T[i] = v;
 }
 
@@ -147,7 +167,7 @@ __global__ __launch_bounds__(256) void nd_table_kernel(const float* theta, int64
 struct ConstArgs {
   const float* y; const double *T, *lf;
   double* gcs;                    // [SN][CQ][D]
-  float* cslab;                   // [GB][N]: per spot, sum over the block's genes of lgamma(y+theta) - lgamma(theta) - lgamma(y+1)
+  float* cslab;                   // [GB][N]: per spot, sum over the block's genes of const_terms' cl
   int64_t N, D;
   int SN;
 };
@@ -184,8 +204,8 @@ __global__ __launch_bounds__(256) void nd_const_kernel(ConstArgs a) {
     for (int g = 0; g < TG; ++g)
       if (yy[g] != 0.f) {
         const Const c = const_terms(yy[g], sT[wave][g], slf);
-        acc[g][0] += (double)yy[g]; acc[g][1] += c.cth; acc[g][2] += c.lg;
-        sc += c.cth - c.lg;
+        acc[g][0] += (double)yy[g]; acc[g][1] += c.cl; acc[g][2] += c.st;
+        sc += c.cl;
       }
     sp[par][wave][lane] = sc;
     // One barrier per tile: the buffer written two tiles ago was read before its readers reached this one.
@@ -225,30 +245,38 @@ struct TileArgs {
   const float *W, *theta, *y;     // y: null in the zero pass
   const float *mF, *Vw, *rD;      // (Lt, N); [Np], V = 1 beyond N; (D,)
   double* gslab;                  // [SN][GQ or ZQ][D]
-  float *s0, *s1;                 // [GB][N]: per spot the deviance and the log density's rate part; or z(mu) and unused
+  float *s0, *s1;                 // [GB][N]: per spot the deviance and the log density's rate part (unused in the zero pass)
+  double* zs;                     // [GB][N], the zero pass: per spot z(mu).  fp64, and summed in fp64 over the genes: a stored
+                                  // count's correction takes 2 z(mu) back, so at large rates the output is what is left of
+                                  // sums a million times its size
   int64_t N, D;
   int Lt, SN;
 };
 
 // The sums over the wave's 16 genes of 16 per-lane values: a halving exchange across the gene lanes r (see dv_tile_kernel)
 // leaves lane r with the sum over all 16 genes of value r, i.e. of spot 16q + r = the lane's own number in the wave.
-__device__ __forceinline__ float gene_lanes_sum(float (&v)[16], int r) {
+template <typename T>
+__device__ __forceinline__ T gene_lanes_sum(T (&v)[16], int r) {
   const bool b8 = (r & 8) != 0, b4 = (r & 4) != 0, b2 = (r & 2) != 0, b1 = (r & 1) != 0;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { const float keep = b8 ? v[i + 8] : v[i], send = b8 ? v[i] : v[i + 8]; v[i] = keep + __shfl_xor(send, 8); }
+  for (int i = 0; i < 8; ++i) { const T keep = b8 ? v[i + 8] : v[i], send = b8 ? v[i] : v[i + 8]; v[i] = keep + __shfl_xor(send, 8); }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { const float keep = b4 ? v[i + 4] : v[i], send = b4 ? v[i] : v[i + 4]; v[i] = keep + __shfl_xor(send, 4); }
+  for (int i = 0; i < 4; ++i) { const T keep = b4 ? v[i + 4] : v[i], send = b4 ? v[i] : v[i + 4]; v[i] = keep + __shfl_xor(send, 4); }
 #pragma unroll
-  for (int i = 0; i < 2; ++i) { const float keep = b2 ? v[i + 2] : v[i], send = b2 ? v[i] : v[i + 2]; v[i] = keep + __shfl_xor(send, 2); }
-  const float keep = b1 ? v[1] : v[0], send = b1 ? v[0] : v[1];
+  for (int i = 0; i < 2; ++i) { const T keep = b2 ? v[i + 2] : v[i], send = b2 ? v[i] : v[i + 2]; v[i] = keep + __shfl_xor(send, 2); }
+  const T keep = b1 ? v[1] : v[0], send = b1 ? v[0] : v[1];
   return keep + __shfl_xor(send, 1);
 }
+
+template <bool ZERO> struct SpotSum { typedef float type; };
+template <> struct SpotSum<true> { typedef double type; };
 
 template <int KS, bool ZERO>
 __global__ __launch_bounds__(256) void nd_tile_kernel(TileArgs a) {
   constexpr bool PFA = KS <= 8;                 // the A operand of the next tile fits in registers beside the current one
   constexpr int NQ = ZERO ? ZQ : GQ, NS = ZERO ? 1 : 2;
-  __shared__ float sp[2][NS][4][TS];
+  typedef typename SpotSum<ZERO>::type spt;     // the per-spot sums: fp64 in the zero pass (see TileArgs::zs)
+  __shared__ spt sp[2][NS][4][TS];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, q = lane >> 4;
   const int64_t d0 = ((int64_t)blockIdx.x * 4 + wave) * TG;
@@ -321,7 +349,8 @@ __global__ __launch_bounds__(256) void nd_tile_kernel(TileArgs a) {
     float f[NQ];
 #pragma unroll
     for (int k = 0; k < NQ; ++k) f[k] = 0.f;
-    float v[16], w[16];                         // [4c + g]: the element at spot 16q + 4c + g of gene d0 + r
+    spt v[16];                                  // [4c + g]: the element at spot 16q + 4c + g of gene d0 + r
+    float w[16];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -336,13 +365,15 @@ __global__ __launch_bounds__(256) void nd_tile_kernel(TileArgs a) {
           v[4 * c + g] = zz;
         } else {
           const float y1 = cur.yv[c][g];        // 0 where the element does not exist
-          const float l2y = __builtin_amdgcn_logf(y1 > 0.f ? y1 : 1.f), l2mu = __builtin_amdgcn_logf(mu);
-          const float dev = ok ? unit_dev(y1, l2y, mu, l2mu, th) : 0.f;
+          const float l2mu = __builtin_amdgcn_logf(mu);
+          const Unit un = unit_dev(y1, mu, th);
+          const float dev = ok ? un.dev : 0.f;
           const float ylm = y1 * LN2 * l2mu;    // y log mu
           const float ll = ok ? __builtin_fmaf(-(y1 + th), lm, __builtin_fmaf(-y1 * LN2, l2th, ylm)) : 0.f;
           const float mu0 = (ok && rpos) ? vn * rd : 1.f;
-          const float dev0 = (ok && rpos) ? unit_dev(y1, l2y, mu0, __builtin_amdgcn_logf(mu0), th) : 0.f;
-          f[0] += dev; f[1] += ok ? mu : 0.f; f[2] += dev0; f[3] += ll; f[4] += ok ? ylm - mu : 0.f;
+          const float dev0 = (ok && rpos) ? unit_dev(y1, mu0, th).dev : 0.f;
+          // the Poisson log density's rate part: -(y log(y / mu) - (y - mu)), the rest is const_terms' st
+          f[0] += dev; f[1] += ok ? mu : 0.f; f[2] += dev0; f[3] += ll; f[4] += ok ? (y1 - mu) - un.yl : 0.f;
           v[4 * c + g] = dev;
           w[4 * c + g] = ll;
         }
@@ -355,9 +386,11 @@ __global__ __launch_bounds__(256) void nd_tile_kernel(TileArgs a) {
     __syncthreads();
     if (threadIdx.x < NS * TS) {
       const int k = threadIdx.x >> 6, t = threadIdx.x & 63;      // k is uniform over the wave
-      if (n0 + t < a.N)
-        (k == 0 ? a.s0 : a.s1)[(int64_t)blockIdx.x * a.N + n0 + t] =
-            (sp[par][k][0][t] + sp[par][k][1][t]) + (sp[par][k][2][t] + sp[par][k][3][t]);
+      if (n0 + t < a.N) {
+        const spt sum = (sp[par][k][0][t] + sp[par][k][1][t]) + (sp[par][k][2][t] + sp[par][k][3][t]);
+        if constexpr (ZERO) a.zs[(int64_t)blockIdx.x * a.N + n0 + t] = sum;
+        else (k == 0 ? a.s0 : a.s1)[(int64_t)blockIdx.x * a.N + n0 + t] = sum;
+      }
     }
     cur = nxt;
   }
@@ -382,10 +415,9 @@ __global__ __launch_bounds__(256) void nd_finish_kernel(const double* gslab, int
 #pragma unroll
       for (int k = 0; k < GQ; ++k) g[k] += gslab[((int64_t)s * GQ + k) * D + d];
     sy = gc[d];
-    const double cth = gc[D + d], lg = gc[2 * D + d];
     nul = sy > 0.0 ? g[2] : 0.0;
-    ll = g[3] + (cth - lg);
-    pl = g[4] - lg;
+    ll = g[3] + gc[D + d];                      // const_terms' cl and st
+    pl = g[4] - gc[2 * D + d];
     per_gene[d] = g[0];
     null_per_gene[d] = nul;
     ll_per_gene[d] = ll;
@@ -415,7 +447,8 @@ __global__ __launch_bounds__(256) void nd_total_kernel(const double* partial, in
 
 // per spot: the gene blocks' slabs in order.  per_spot = fa sum s0 + (ca ? ca[n] : 0);
 // ll_per_spot = fb sum sb + sum sc + (cb ? cb[n] : 0)   (sc nullable)
-__global__ __launch_bounds__(256) void nd_spot_sum_kernel(const float* s0, const float* sb, const float* sc, int GB, int64_t N,
+template <typename T>
+__global__ __launch_bounds__(256) void nd_spot_sum_kernel(const T* s0, const T* sb, const float* sc, int GB, int64_t N,
                                                           double fa, double fb, const double* ca, const double* cb,
                                                           double* per_spot, double* ll_per_spot) {
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -608,7 +641,7 @@ __global__ __launch_bounds__(256) void nds_const_kernel(SpArgs a) {
       const float y = a.col_val[a.row_perm[p]];
       if (y == 0.f) continue;
       const Const c = const_terms(y, row, a.lf);
-      s[0] += (double)y; s[1] += c.cth; s[2] += c.lg;
+      s[0] += (double)y; s[1] += c.cl; s[2] += c.st;
     }
   }
 #pragma unroll
@@ -677,7 +710,7 @@ __global__ __launch_bounds__(256) void nds_spot_kernel(SpArgs a) {
     const Corr c = stored_corr(y, vn * z, th, 1.f / th, __builtin_amdgcn_logf(th));
     const Const t = const_terms(y, a.T + (int64_t)g * TROW, a.lf);
     ad += (double)c.dev;
-    al += (double)c.ll + (t.cth - t.lg);
+    al += (double)c.ll + t.cl;
   }
   ad = wave_sum(ad);
   al = wave_sum(al);
@@ -765,8 +798,8 @@ __global__ __launch_bounds__(256) void nds_gene_finish_kernel(SpArgs a) {
 
 struct SpPlan {
   Slices sl; int LT; int64_t nchunks; size_t bytes;
-  float *mF, *Vw, *mT, *rD, *zslab;
-  double *vsum, *T, *lf, *part0, *part, *spc, *gc, *zgs, *gslab, *partial;
+  float *mF, *Vw, *mT, *rD;
+  double *zslab, *vsum, *T, *lf, *part0, *part, *spc, *gc, *zgs, *gslab, *partial;
   int32_t *cstart, *chunk_gene;
 };
 
@@ -790,7 +823,7 @@ static SpPlan sp_plan(int64_t B, int64_t D, int Lt, int64_t nnz, void* ws) {
   p.gc = c.take<double>((size_t)CQ * D);
   p.rD = c.take<float>((size_t)D);
   p.zgs = c.take<double>((size_t)p.sl.SN * ZQ * D);
-  p.zslab = c.take<float>((size_t)p.sl.GB * B);
+  p.zslab = c.take<double>((size_t)p.sl.GB * B);
   p.gslab = c.take<double>((size_t)GQ * D);
   p.partial = c.take<double>((size_t)p.sl.nbD * NSCAL);
   p.bytes = c.used();
@@ -873,13 +906,14 @@ extern "C" int gpz_nb_deviance(const float* mean, const float* scale, const floa
   GPZ_LAUNCH_OK();
   TileArgs ta;
   ta.W = W; ta.theta = theta; ta.y = y; ta.mF = p.mF; ta.Vw = p.Vw; ta.rD = p.rD; ta.gslab = p.gslab; ta.s0 = p.s0; ta.s1 = p.s1;
-  ta.N = N; ta.D = D; ta.Lt = Lt; ta.SN = sl.SN;
+  ta.zs = nullptr; ta.N = N; ta.D = D; ta.Lt = Lt; ta.SN = sl.SN;
   launch_tiles<false>(sl.KS, ta, sl.GB, s);
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(nd_finish_kernel, dim3((unsigned)sl.nbD), dim3(256), 0, s, p.gslab, sl.SN, p.gc, D, per_gene, null_per_gene,
                      loglik_per_gene, poisson_loglik_per_gene, p.partial);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(nd_spot_sum_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, p.s0, p.s1, p.cslab, sl.GB, N, 1.0,
+  hipLaunchKernelGGL(nd_spot_sum_kernel<float>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const float*)p.s0,
+                     (const float*)p.s1, (const float*)p.cslab, sl.GB, N, 1.0,
                      1.0, (const double*)nullptr, (const double*)nullptr, per_spot, loglik_per_spot);
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(nd_total_kernel, dim3(1), dim3(256), 0, s, p.partial, sl.nbD, scalars);
@@ -947,8 +981,8 @@ extern "C" int gpz_nb_deviance_sparse(const float* mean, const float* scale, con
   hipLaunchKernelGGL(nds_rate_kernel, dim3((unsigned)sl.nbD), dim3(256), 0, s, a, p.rD);
   GPZ_LAUNCH_OK();
   TileArgs ta;
-  ta.W = W; ta.theta = theta; ta.y = nullptr; ta.mF = p.mF; ta.Vw = p.Vw; ta.rD = p.rD; ta.gslab = p.zgs; ta.s0 = p.zslab;
-  ta.s1 = nullptr; ta.N = B; ta.D = D; ta.Lt = Lt; ta.SN = sl.SN;
+  ta.W = W; ta.theta = theta; ta.y = nullptr; ta.mF = p.mF; ta.Vw = p.Vw; ta.rD = p.rD; ta.gslab = p.zgs; ta.s0 = nullptr;
+  ta.s1 = nullptr; ta.zs = p.zslab; ta.N = B; ta.D = D; ta.Lt = Lt; ta.SN = sl.SN;
   launch_tiles<true>(sl.KS, ta, sl.GB, s);
   GPZ_LAUNCH_OK();
   int rc;
@@ -970,7 +1004,8 @@ extern "C" int gpz_nb_deviance_sparse(const float* mean, const float* scale, con
   hipLaunchKernelGGL(nd_finish_kernel, dim3((unsigned)sl.nbD), dim3(256), 0, s, p.gslab, 1, p.gc, D, per_gene, null_per_gene,
                      loglik_per_gene, poisson_loglik_per_gene, p.partial);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(nd_spot_sum_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, p.zslab, p.zslab, (const float*)nullptr,
+  hipLaunchKernelGGL(nd_spot_sum_kernel<double>, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, (const double*)p.zslab,
+                     (const double*)p.zslab, (const float*)nullptr,
                      sl.GB, B, 2.0, -1.0, (const double*)p.spc, (const double*)(p.spc + B), per_spot, loglik_per_spot);
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(nd_total_kernel, dim3(1), dim3(256), 0, s, p.partial, sl.nbD, scalars);
