@@ -83,6 +83,9 @@ _SIGNATURES = {
     "gpz_nb_nsf_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "gpz_nb_nsf": (C.c_int, [C.c_void_p] * 7 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32] +
                    [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_fa_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32] + [C.POINTER(C.c_int32)] * 4 + [C.POINTER(C.c_int64)]),
+    "gpz_gaussian_fa": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 8 +
+                        [C.c_size_t, C.c_void_p]),
     "gpz_nb_nsf_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6),
     "gpz_nb_nsf_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),

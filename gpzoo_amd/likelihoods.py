@@ -9,6 +9,8 @@ as the reference, plus ``expected_loglik`` -- the fused fp32 training-step form
 ``likelihood="nb"`` on any of the count models swaps the Poisson noise for a negative binomial with one inverse
 dispersion per gene (the nsf paper's ``lik="nb"``): ``pY`` is a torch NegativeBinomial and ``expected_loglik`` runs
 the fused ``gpz_nb_nsf`` step.
+``RSF`` and ``FA`` at the end are the Gaussian factor models for normalised, real-valued expression: real loadings, an
+intercept and a noise level per gene, and an exact ``expected_loglik`` through the fused ``gpz_gaussian_fa`` step.
 """
 from __future__ import annotations
 
@@ -921,3 +923,201 @@ class Hybrid_NSF(NSF):
             qF = self.gp(X=Xb, **kwargs)[0]
             qF2 = distributions.Normal(mF, torch.nn.functional.softplus(rs), validate_args=False)
             return _deviance_of([qF, qF2], [self.W, self.W2], Vp, theta_pos, y, lognormal_mean)
+
+
+# --------------------------------------------------------------------------------------------
+# Gaussian factor models on normalised, real-valued expression: RSF (a GP prior on the factors; the nsf paper's
+# real-valued spatial factorisation, which it shows to be MEFISTO's model) and FA (an i.i.d. prior).  W is real and
+# there is no link, so E_q[log p(y | F)] is a closed form: `expected_loglik` is exact, takes no samples and runs the
+# fused gpz_gaussian_fa step.
+# --------------------------------------------------------------------------------------------
+
+class _GaussianFALogLik(torch.autograd.Function):
+    """E_q[sum_dn log Normal(y | b + W F, noise_sd)] through gpz_gaussian_fa (value and gradients in one fused step;
+    backward only scales them)."""
+
+    @staticmethod
+    def forward(ctx, mean, scale, W, b, noise_sd, y):
+        from . import ops
+        ll, _, dmean, dscale, dW, db, dsd = ops.gaussian_fa(mean, scale, W, b, noise_sd, y)
+        ctx.save_for_backward(dmean.to(mean.dtype), dscale.to(scale.dtype), dW.to(W.dtype), db.to(b.dtype),
+                              dsd.to(noise_sd.dtype))
+        return ll.to(mean.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        dmean, dscale, dW, db, dsd = ctx.saved_tensors
+        return g * dmean, g * dscale, g * dW, g * db, g * dsd, None
+
+
+def gaussian_expected_loglik(qF_list, W_list, b, noise_sd, y):
+    """Exact E_q[log p(y | F)] for y ~ Normal(b[:, None] + sum_k W_k F_k, noise_sd[:, None]), F_k ~ qF_k independent.
+
+    qF_list: Normal distributions over (L_k, N) factors; W_list: real (D, L_k) loadings; b (D,); noise_sd (D,) positive
+    standard deviations; y: the dense (D, N) data.  Differentiable in every argument but y (gpz_gaussian_fa)."""
+    mean = torch.cat([q.mean for q in qF_list], dim=0)
+    scale = torch.cat([q.scale for q in qF_list], dim=0)
+    W = torch.cat(list(W_list), dim=1)
+    return _GaussianFALogLik.apply(mean, scale, W, b, noise_sd, y)
+
+
+class GaussianScore(NamedTuple):
+    """What ``RSF.score`` / ``FA.score`` return; every tensor is fp64 and carries no graph.  ``sse_per_gene`` is the squared
+    error of the predictive mean b + W E_q[F] and ``mse_per_gene`` = sse / B, ``mse`` = sum sse / (D B);
+    ``r2_per_gene`` = 1 - sse / sum_n (y - mean_n y)^2 (NaN where that sum is 0) and ``r2`` the same over all genes.
+    ``loglik`` is the EXPECTED log density under q(F): next to the squared error it carries sum_l W[d,l]^2 sum_n scale^2,
+    the variance of q(F), so it is not a function of ``sse`` alone."""
+    loglik: torch.Tensor
+    sse_per_gene: torch.Tensor
+    mse_per_gene: torch.Tensor
+    mse: torch.Tensor
+    r2_per_gene: torch.Tensor
+    r2: torch.Tensor
+
+
+def gaussian_score(qF_list, W_list, b, noise_sd, y):
+    """``GaussianScore`` of the dense (D, B) data ``y`` from the value-only form of gpz_gaussian_fa (one pass over y); the
+    null sums of squares come from a plain torch reduction of y in fp64."""
+    from . import ops
+    with torch.no_grad():
+        mean = torch.cat([q.mean for q in qF_list], dim=0)
+        scale = torch.cat([q.scale for q in qF_list], dim=0)
+        W = torch.cat(list(W_list), dim=1)
+        ll, sse = ops.gaussian_fa(mean, scale, W, b, noise_sd, y, grads=False)
+        D, B = y.shape
+        yd = y.detach().double()
+        null = ((yd - yd.mean(dim=1, keepdim=True)) ** 2).sum(dim=1)
+        return GaussianScore(loglik=ll.clone(), sse_per_gene=sse, mse_per_gene=sse / B, mse=sse.sum() / (D * B),
+                             r2_per_gene=_explained(sse, null), r2=_explained(sse.sum(), null.sum()))
+
+
+def _call_gp(gp, X, groupsX=None):
+    """q(F), q(U), p(U) of a GP at X; the multi-group GPs take the group ids as ``MGGP_NSF`` passes them."""
+    if groupsX is None:
+        return gp(X)
+    if getattr(gp, "_whitened", False):
+        return gp(X, groupsX=groupsX)          # MGGP_WSVGP takes groupsX as a keyword
+    return gp(X, groupsX)
+
+
+NOISE_SD_RANGE = (1e-18, 1e18)     # what gpz_gaussian_fa supports (include/gpzoo_hip.h): 1 / sd^2 must be a finite fp32
+
+
+def _noise_sd(raw):
+    """softplus(raw) kept inside the range the fused step supports: training may push the raw parameter anywhere, and a
+    softplus that underflows would make 1 / sd^2 infinite in fp32."""
+    return torch.nn.functional.softplus(raw).clamp(*NOISE_SD_RANGE)
+
+
+def _known_kwargs(who, kwargs, known):
+    """Keyword arguments are forwarded by the training loops (``groupsX=``); anything else is a mistake, not ignored."""
+    extra = sorted(set(kwargs) - set(known))
+    if extra:
+        raise TypeError(f"{who}: unexpected keyword argument(s) {extra} (known: {sorted(known)})")
+
+
+def _init_gaussian(module, y, L, noise0):
+    """Parameters of the Gaussian factor models: W (D, L) real = randn / sqrt(L), b (D,) = the row means of y, noise (D,)
+    raw with softplus(noise) = the row standard deviations of y floored at 1e-3, or the positive scalar ``noise0``."""
+    import numpy as np
+    from .utilities import init_softplus
+    D, N = y.shape
+    dt = torch.get_default_dtype()
+    yd = torch.as_tensor(y).detach().double()
+    module.W = nn.Parameter(torch.randn((D, L)) / float(L) ** 0.5)
+    module.b = nn.Parameter(yd.mean(dim=1).to(dtype=dt, device="cpu"))
+    if noise0 is None:
+        sd = yd.std(dim=1, unbiased=False).clamp_min(1e-3).cpu().numpy()
+    else:
+        if not float(noise0) > 0:
+            raise ValueError(f"{type(module).__name__}: noise0 must be positive, got {noise0}")
+        sd = np.full((D,), float(noise0), dtype=np.float64)
+    module.noise = nn.Parameter(torch.as_tensor(init_softplus(sd), dtype=dt))
+
+
+class RSF(nn.Module):
+    """Real-valued spatial factorisation: y ~ Normal(b[:, None] + W F, softplus(noise)[:, None]) with a GP prior on the
+    rows of F (``gp``: SVGP, WSVGP, VNNGP or, with ``groupsX=``, a multi-group GP) -- the nsf paper's RSF, i.e. MEFISTO.
+    ``W`` (D, L) is real (``signed_loadings``: the training loops do not clamp it), ``b`` (D,) the intercept, ``noise`` (D,)
+    raw: softplus(noise) is the per-gene noise standard deviation, as in ``GaussianLikelihood`` (kept inside
+    ``NOISE_SD_RANGE``).  ``groupsX=`` is the only extra keyword the methods take; any other raises TypeError."""
+    signed_loadings = True
+
+    def __init__(self, gp, y, L=10, noise0=None):
+        super().__init__()
+        self.gp = gp
+        _init_gaussian(self, y, L, noise0)
+
+    def _pY(self, qF, E):
+        sd = _noise_sd(self.noise)
+        return _dist(distributions.Normal, self.b[:, None] + torch.matmul(self.W, qF.rsample((E,))), sd[:, None])
+
+    def _qF(self, X, idx, kwargs):
+        _known_kwargs("RSF", kwargs, ("groupsX",))
+        gX = kwargs.get("groupsX")
+        if idx is not None:
+            X, gX = X[idx], (None if gX is None else gX[idx])
+        return _call_gp(self.gp, X, gX)
+
+    def forward(self, X, E=10, verbose=False, **kwargs):
+        qF, qU, pU = self._qF(X, None, kwargs)
+        return self._pY(qF, E), qF, qU, pU
+
+    def forward_batched(self, X, idx, E=10, verbose=False, **kwargs):
+        qF, qU, pU = self._qF(X, idx, kwargs)
+        return self._pY(qF, E), qF, qU, pU
+
+    def expected_loglik(self, X, y, idx=None, E=None, **kwargs):
+        """Fused training-step form: (E_q[log p(y | F)] as a scalar, qF, qU, pU).  The value is exact -- what
+        ``forward``'s ``pY.log_prob(y).mean(0).sum()`` estimates -- so ``E`` is accepted and unused.  For a batch pass
+        ``y[:, idx]`` together with ``idx``; group ids (``groupsX=``) follow the sampled spots."""
+        qF, qU, pU = self._qF(X, idx, kwargs)
+        ll = gaussian_expected_loglik([qF], [self.W], self.b, _noise_sd(self.noise), y)
+        return ll, qF, qU, pU
+
+    def score(self, X, y, idx=None, **kwargs):
+        """``GaussianScore`` of ``y`` (D, B) at ``X`` (or ``X[idx]``), held-out spots included: the squared error and R^2 of
+        the predictive mean, and the expected log density (which also carries the variance of q(F))."""
+        with torch.no_grad():
+            qF = self._qF(X, idx, kwargs)[0]
+            return gaussian_score([qF], [self.W], self.b, _noise_sd(self.noise), y)
+
+
+class FA(nn.Module):
+    """Factor analysis: ``RSF``'s likelihood over a ``GaussianPrior`` (i.i.d. factors per spot), with ``PNMF``'s return
+    tuples ``(..., qF, pF)``."""
+    signed_loadings = True
+
+    def __init__(self, prior, y, L=10, noise0=None):
+        super().__init__()
+        self.prior = prior
+        _init_gaussian(self, y, L, noise0)
+
+    _pY = RSF._pY
+
+    def forward(self, E=10, **kwargs):
+        _known_kwargs("FA", kwargs, ("X", "verbose"))       # the loops call model(X=X, E=E); the factors are per spot
+        qF, pF = self.prior()
+        return self._pY(qF, E), qF, pF
+
+    def forward_batched(self, idx, E=10, **kwargs):
+        _known_kwargs("FA", kwargs, ("X", "verbose"))
+        qF, pF = self.prior.forward_batched(idx)
+        return self._pY(qF, E), qF, pF
+
+    def expected_loglik(self, X, y, idx=None, E=None, **kwargs):
+        """Fused form of ``forward``'s ``pY.log_prob(y).mean(0).sum()``, exact: (value, qF, pF).  ``X`` is accepted for the
+        signature of the spatial models and unused, ``E`` likewise.  The 3-tuple is ``PNMF``'s: ``train`` and
+        ``train_batched`` unpack four values and therefore do not run an ``FA`` (nor a ``PNMF``); write the loop by hand."""
+        _known_kwargs("FA", kwargs, ())
+        qF, pF = self.prior() if idx is None else self.prior.forward_batched(idx)
+        ll = gaussian_expected_loglik([qF], [self.W], self.b, _noise_sd(self.noise), y)
+        return ll, qF, pF
+
+    def score(self, X, y, idx=None, **kwargs):
+        """``GaussianScore`` of ``y`` (D, B) for the fitted spots (or those of ``idx``); see ``RSF.score``.  The factors
+        exist only for the fitted spots."""
+        _known_kwargs("FA", kwargs, ())
+        with torch.no_grad():
+            qF = (self.prior() if idx is None else self.prior.forward_batched(idx))[0]
+            return gaussian_score([qF], [self.W], self.b, _noise_sd(self.noise), y)

@@ -1367,6 +1367,67 @@ def nb_nsf(mean, scale, eps, W_pos, V_pos, theta_pos, y, with_lgamma: bool = Tru
     return (total, *acc)
 
 
+def gaussian_fa_plan(N: int, D: int, Lt: int) -> dict:
+    """How ``gaussian_fa`` covers a shape (gpz_gaussian_fa_plan, a host-only query: no device needed): ``factors_padded``
+    (Lt rounded up to the kernel instance), ``aligned_rows`` (N % 4 == 0: rows of y move 16 bytes at a time),
+    ``gene_slices`` and ``spot_slices`` (partial slabs of the spot pass and of the gene pass), ``partials_bytes``."""
+    lib = _lib.load()
+    fp, al, gsl, ssl, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    rc = lib.gpz_gaussian_fa_plan(int(N), int(D), int(Lt), C.byref(fp), C.byref(al), C.byref(gsl), C.byref(ssl), C.byref(nb))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(factors_padded=fp.value, aligned_rows=bool(al.value), gene_slices=gsl.value, spot_slices=ssl.value,
+                partials_bytes=int(nb.value))
+
+
+def gaussian_fa(mean, scale, W, b, noise_sd, y, grads: bool = True):
+    """Fused exact expected Gaussian log-likelihood of the real-valued factor models and its gradients (gpz_gaussian_fa):
+    E_q[sum log Normal(y | b[:, None] + W F, noise_sd[:, None])] under q(F) = Normal(mean, scale), in closed form -- no
+    samples.
+
+    mean, scale (Lt,N); W (D,Lt) real; b (D,); noise_sd (D,) positive standard deviations; y (D,N) dense.  Returns
+    (loglik fp64 scalar, sse_per_gene fp64 (D,), dmean, dscale, dW, db, dnoise_sd), or the first two with
+    ``grads=False`` (one pass over y instead of two).  ``sse_per_gene`` is the squared error of the predictive mean
+    b + W mean; ``loglik`` also carries the variance of q(F).  Nothing here waits for the device: the call can be captured
+    in a graph.  A ``SparseCounts`` raises TypeError: normalised data is dense."""
+    from .likelihoods import SparseCounts
+    if isinstance(y, SparseCounts):
+        raise TypeError("gaussian_fa: the Gaussian step takes dense real-valued data (normalised expression is dense): "
+                        "a SparseCounts holds counts, pass the normalised array")
+    return _gaussian_fa(mean, scale, W, b, noise_sd, y, grads)
+
+
+@_on_device
+def _gaussian_fa(mean, scale, W, b, noise_sd, y, grads):
+    _need_cuda(mean, scale, W, b, noise_sd, y)
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale, W, b, noise_sd, y = (t.detach().to(f32).contiguous() for t in (mean, scale, W, b, noise_sd, y))
+    # the entry wants 16-byte aligned arrays (include/gpzoo_hip.h); a contiguous view keeps its storage offset
+    mean, scale, W, b, noise_sd, y = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (mean, scale, W, b, noise_sd, y))
+    if mean.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"gaussian_fa: mean {tuple(mean.shape)} must be (Lt, N) and y {tuple(y.shape)} (D, N)")
+    Lt, N = mean.shape
+    D = y.shape[0]
+    if scale.shape != (Lt, N) or W.shape != (D, Lt) or b.shape != (D,) or noise_sd.shape != (D,) or y.shape != (D, N):
+        raise ValueError(f"gaussian_fa: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, W "
+                         f"{tuple(W.shape)}, b {tuple(b.shape)}, noise_sd {tuple(noise_sd.shape)} do not fit together")
+    dev = mean.device
+    nb = C.c_int64()
+    if lib.gpz_gaussian_fa_plan(N, D, Lt, None, None, None, None, C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ll = torch.empty(1, dtype=torch.float64, device=dev)
+    sse = torch.empty(D, dtype=torch.float64, device=dev)
+    out = [torch.empty((Lt, N), dtype=f32, device=dev), torch.empty((Lt, N), dtype=f32, device=dev),
+           torch.empty((D, Lt), dtype=f32, device=dev), torch.empty((D,), dtype=f32, device=dev),
+           torch.empty((D,), dtype=f32, device=dev)] if grads else [None] * 5
+    ws = _workspace(dev, nb.value)
+    rc = lib.gpz_gaussian_fa(_ptr(mean), _ptr(scale), _ptr(W), _ptr(b), _ptr(noise_sd), _ptr(y), N, D, Lt, _ptr(ll), _ptr(sse),
+                             *(_ptr(t) for t in out), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_gaussian_fa")
+    return (ll[0], sse, *out) if grads else (ll[0], sse)
+
+
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
     """How ``poisson_nsf_sparse`` covers a shape (gpz_poisson_nsf_sparse_plan, a host-only query: no device needed):
     ``gene_chunk`` (non-zeros of a gene row per wave of the gene pass), ``spot_chunk`` (the same for a spot's column; 0:

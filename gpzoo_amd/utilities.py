@@ -88,7 +88,10 @@ def _elbo_terms(model, X, y, E, **kwargs):
 
 
 def _clamp_loadings(model, names=("W", "W2")):
-    """keep raw loadings non-negative after an update (utilities.py:522-523, 551-552, 628)"""
+    """keep raw loadings non-negative after an update (utilities.py:522-523, 551-552, 628); a model with real loadings
+    (``signed_loadings``: RSF, FA) is left alone"""
+    if getattr(model, "signed_loadings", False):
+        return
     for n in names:
         w = getattr(model, n, None)
         if isinstance(w, torch.Tensor):

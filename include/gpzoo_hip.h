@@ -52,7 +52,10 @@
  * gpz_nb_nsf_sparse, gpz_nb_nsf_sparse_workspace_bytes and the host-only gpz_nb_nsf_sparse_plan -- gpz_nb_nsf for counts
  * stored as their non-zeros: a dense pass over the batch that reads no counts plus sums over the non-zeros;
  * gpz_nb_deviance and gpz_nb_deviance_sparse, each with its *_workspace_bytes and host-only *_plan query -- the NB deviance,
- * the NB log density and the Poisson log density of held-out counts under the predictive mean rate and a per-gene theta.
+ * the NB log density and the Poisson log density of held-out counts under the predictive mean rate and a per-gene theta;
+ * gpz_gaussian_fa and the host-only gpz_gaussian_fa_plan -- the exact expected Gaussian log-likelihood of the real-valued
+ * factor models (RSF over a GP prior, FA over an i.i.d. one) and its gradients; its scratch is the explicit argument
+ * `partials`, sized by the plan query.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -326,6 +329,39 @@ int gpz_nb_nsf(const float* mean, const float* scale, const float* eps, const fl
                const float* theta, const float* y, int64_t N, int64_t D, int32_t Lt, int32_t E, int32_t with_lgamma,
                double* loglik, float* dmean, float* dscale, float* dW, float* dV, float* dtheta, void* ws,
                size_t ws_bytes, void* stream);
+
+/* The Gaussian member of the family (csrc/gaussian.hip): real-valued y (D,N), real loadings W (D,Lt), intercept b (D,) and
+ * one noise standard deviation per gene, noise_sd (D,) > 0 (a scale, not a variance), under q(F) = N(mean, scale^2)
+ * independent with mean and scale (Lt,N).  This is the likelihood of RSF (a GP prior on F; the nsf paper's
+ * real-valued spatial factorisation, MEFISTO's model) and of FA (an i.i.d. prior).  There is no link function, so the
+ * expectation under q(F) has a closed form -- no samples, no eps, an exact value:
+ *   r = y - b - W mean,  R[d] = sum_n r^2,  S[l] = sum_n scale^2,  Q[d] = sum_l W[d,l]^2 S[l]
+ *   loglik[0]       = sum_d [ -N (log(2 pi) / 2 + log noise_sd[d]) - (R[d] + Q[d]) / (2 noise_sd[d]^2) ]
+ *   sse_per_gene[d] = R[d]  (fp64; the squared error of the predictive mean; may be NULL)
+ *   dmean = W^T g with g = r / noise_sd^2,  dscale[l,n] = -scale[l,n] sum_d W[d,l]^2 / noise_sd[d]^2,
+ *   dW = g mean^T - W S / noise_sd^2,  db = sum_n g,  dnoise_sd = -N / noise_sd + (R + Q) / noise_sd^3
+ * Several factor sets concatenate along Lt as in the count steps.  fp32 operands, the dense products on
+ * v_mfma_f32_16x16x4_f32, every sum across tiles fp64 in a fixed order, no floating-point atomics: two calls agree bit
+ * for bit.  y is read twice by a gradient call and once by a value-only call: the five gradient pointers are either
+ * all set or all NULL, and with all NULL only loglik and sse_per_gene are computed (held-out scoring).
+ * The scratch memory is the explicit argument `partials` (partial sums per gene slice and spot slice; nothing of D x N
+ * elements); it need not be cleared and may hold anything.  Its size comes from the host-only plan query, which also
+ * reports factors_padded (Lt rounded up to the kernel instance), aligned_rows (1 when N % 4 == 0: rows of y and of the
+ * slabs move 16 bytes at a time), gene_slices and spot_slices (any out pointer may be NULL).
+ * Supported range of noise_sd: 1e-18 <= noise_sd[d] <= 1e18 (finite).  The spot pass forms 1 / noise_sd^2 in fp32, which
+ * overflows to inf below about 5e-20 and flushes towards 0 above about 2e19: dmean then holds inf / NaN or zeros while the
+ * outputs the finish kernel forms in fp64 (loglik, sse_per_gene, dW, db, dnoise_sd) stay finite.  The values are not checked
+ * (that would need a pass over device memory); a caller that trains noise_sd keeps it inside the range.
+ * 1 <= Lt <= 64, 1 <= N, D < 2^31; N need not be a multiple of 4.  Every array argument and partials must be 16-byte
+ * aligned.  Argument errors (a null among the inputs, loglik or partials, gradient pointers partly set, extents, Lt, a
+ * small partials_bytes, alignment) return -1 before any launch; the plan query then returns a negative value and leaves
+ * the reason in gpz_last_error. */
+int gpz_gaussian_fa_plan(int64_t N, int64_t D, int32_t Lt, int32_t* factors_padded, int32_t* aligned_rows,
+                         int32_t* gene_slices, int32_t* spot_slices, int64_t* partials_bytes);
+int gpz_gaussian_fa(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                    const float* y, int64_t N, int64_t D, int32_t Lt, double* loglik, double* sse_per_gene,
+                    float* dmean, float* dscale, float* dW, float* db, float* dnoise_sd,
+                    void* partials, size_t partials_bytes, void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
