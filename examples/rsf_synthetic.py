@@ -4,9 +4,16 @@ expression: smooth signed factors on a 2-D tissue, real loadings, an intercept a
 whitened SVGP prior, fitted with ``train_batched`` through the fused exact step (``gpz_gaussian_fa``: no samples), then
 ``model.score`` on held-out spots.
 
+With ``--sparse-expression DENSITY`` the data are counts instead, held as their non-zeros from start to end: synthetic
+Poisson counts with about DENSITY of the entries non-zero -> ``SparseCounts`` -> ``train_val_split`` -> ``log_normalize``
+(log1p of size-normalised counts, centred per gene; the held-out split is centred with the training split's offset) ->
+the same fit through ``gpz_gaussian_fa_sparse`` -> held-out ``score``.  No (genes, spots) array exists on the device.
+
     PYTHONPATH=. python examples/rsf_synthetic.py [--spots 20000 --genes 1000 --factors 6 --inducing 500 --steps 300]
+                                                  [--sparse-expression 0.05]
 """
 import argparse
+import math
 import time
 
 import torch
@@ -14,8 +21,8 @@ import torch.nn as nn
 
 from gpzoo.gp import WSVGP
 from gpzoo.kernels import NSF_RBF
-from gpzoo.likelihoods import RSF
-from gpzoo.utilities import train_batched
+from gpzoo.likelihoods import RSF, SparseCounts
+from gpzoo.utilities import log_normalize, train_batched, train_val_split
 
 
 def synthetic_expression(N, D, L, gen):
@@ -31,6 +38,28 @@ def synthetic_expression(N, D, L, gen):
     return X, Y, sd
 
 
+def synthetic_counts(N, D, L, density, gen):
+    """Poisson counts over smooth non-negative factors, their mean rate set so that about ``density`` of the entries are
+    non-zero; the spots come in random order, as ``train_val_split`` assumes."""
+    X = (torch.rand(N, 2, generator=gen) - 0.5) * 200.0
+    c = (torch.rand(L, 2, generator=gen) - 0.5) * 160.0
+    F = torch.exp(-((X[None] - c[:, None]) ** 2).sum(-1) / (2 * 35.0 ** 2))                   # (L,N)
+    rate = torch.rand(D, L, generator=gen) ** 2 @ F + 0.02
+    rate *= -math.log1p(-density) / float(rate.mean())
+    return X, torch.poisson(rate, generator=gen)
+
+
+def sparse_expression_data(a, gen, dev):
+    """(X, expr) of the training split and of the held-out split, both on the device."""
+    X, counts = synthetic_counts(a.spots, a.genes, a.factors, a.sparse_expression, gen)
+    counts = SparseCounts(counts)
+    print(f"{counts.nnz} non-zeros, density {counts.nnz / (a.spots * a.genes):.3f}")
+    tr, val = train_val_split(X, counts, train_frac=1.0 - a.holdout, sz="scanpy")
+    fit = log_normalize(tr["y"], size_factors=tr["sz"])
+    held = log_normalize(val["y"], size_factors=val["sz"], offset=fit.offset)      # centred with the training means
+    return tr["X"].to(dev), fit.to(dev), val["X"].to(dev), held.to(dev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--spots", type=int, default=20000)
@@ -41,20 +70,26 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--holdout", type=float, default=0.1, help="fraction of the spots held out for the score")
     ap.add_argument("--lr", type=float, default=2e-2, help="Adam's learning rate")
+    ap.add_argument("--sparse-expression", type=float, default=None, metavar="DENSITY",
+                    help="fit log-normalised synthetic counts of this density, held as their non-zeros (SparseExpression)")
     a = ap.parse_args()
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
-    X, Y, sd_true = synthetic_expression(a.spots, a.genes, a.factors, gen)
-    n_val = max(int(a.holdout * a.spots), 1)
-    perm = torch.randperm(a.spots, generator=gen)
-    held, fit = perm[:n_val], perm[n_val:]
-    Xv, Yv, X, Y = X[held], Y[:, held], X[fit], Y[:, fit]
+    sd_true = None
+    if a.sparse_expression is not None:
+        X, Y, Xv, Yv = sparse_expression_data(a, gen, dev)
+    else:
+        X, Y, sd_true = synthetic_expression(a.spots, a.genes, a.factors, gen)
+        n_val = max(int(a.holdout * a.spots), 1)
+        perm = torch.randperm(a.spots, generator=gen)
+        held, fit = perm[:n_val], perm[n_val:]
+        Xv, Yv, X, Y = X[held], Y[:, held], X[fit], Y[:, fit]
     print(f"{Y.shape[1]} spots to fit, {Yv.shape[1]} held out")
 
     L, M = a.factors, a.inducing
     kernel = NSF_RBF(sigma=1.0, lengthscale=30.0, L=L)
     gp = WSVGP(kernel, dim=2, M=M, jitter=1e-2)
-    gp.Z = nn.Parameter(X[torch.randperm(X.shape[0], generator=gen)[:M]].clone(), requires_grad=False)
+    gp.Z = nn.Parameter(X[torch.randperm(X.shape[0], generator=gen)[:M]].clone().cpu(), requires_grad=False)
     gp.mu = nn.Parameter(1e-2 * torch.randn(L, M, generator=gen))
     gp.Lu = nn.Parameter(1e-2 * torch.randn(L, M, M, generator=gen) - 1.0 * torch.eye(M))
     kernel.sigma.requires_grad_(False); kernel.lengthscale.requires_grad_(False)
@@ -78,8 +113,9 @@ def main():
     fit_sd = torch.nn.functional.softplus(model.noise.detach()).cpu()
     print("held-out spots:  R^2 %.3f -> %.3f, mse %.4f -> %.4f, expected loglik %.4g -> %.4g"
           % (float(before.r2), float(after.r2), float(before.mse), float(after.mse), float(before.loglik), float(after.loglik)))
-    print("noise sd, median fitted %.3f (true %.3f); %d of %d loadings negative"
-          % (float(fit_sd.median()), float(sd_true.median()), int((model.W < 0).sum()), model.W.numel()))
+    print("noise sd, median fitted %.3f%s; %d of %d loadings negative"
+          % (float(fit_sd.median()), "" if sd_true is None else " (true %.3f)" % float(sd_true.median()),
+             int((model.W < 0).sum()), model.W.numel()))
     assert sum(losses[-k:]) < sum(losses[:k]) and float(after.r2) > float(before.r2)
 
 

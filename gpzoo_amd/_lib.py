@@ -86,6 +86,10 @@ _SIGNATURES = {
     "gpz_gaussian_fa_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32] + [C.POINTER(C.c_int32)] * 4 + [C.POINTER(C.c_int64)]),
     "gpz_gaussian_fa": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 8 +
                         [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_fa_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "gpz_gaussian_fa_sparse": (C.c_int, [C.c_void_p] * 14 + [C.c_int64] * 4 + [C.c_int32] + [C.c_void_p] * 9 +
+                               [C.c_size_t, C.c_void_p]),
     "gpz_nb_nsf_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6),
     "gpz_nb_nsf_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),

@@ -14,7 +14,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpzoo_hip.so")
-SOURCES = ["runtime.hip", "kfill.hip", "gemm.hip", "gemmw.hip", "gemmp.hip", "diag128.hip", "coop.hip", "factor.hip", "kgrad.hip", "mmops.hip", "poisson.hip", "svgp.hip", "vnngp.hip", "collective.hip", "spatial.hip", "nmf.hip", "smooth.hip", "kmeans.hip", "gram.hip", "poisson_sparse.hip", "nmf_sparse.hip", "deviance.hip", "nb.hip", "nb_sparse.hip", "nb_deviance.hip", "gaussian.hip"]
+SOURCES = ["runtime.hip", "kfill.hip", "gemm.hip", "gemmw.hip", "gemmp.hip", "diag128.hip", "coop.hip", "factor.hip", "kgrad.hip", "mmops.hip", "poisson.hip", "svgp.hip", "vnngp.hip", "collective.hip", "spatial.hip", "nmf.hip", "smooth.hip", "kmeans.hip", "gram.hip", "poisson_sparse.hip", "nmf_sparse.hip", "deviance.hip", "nb.hip", "nb_sparse.hip", "nb_deviance.hip", "gaussian.hip", "gaussian_sparse.hip"]
 HEADERS = ["common.h", "gemm.h", "cov.h", "gemmw.h", "gemmp.h", "diag128.h", "factor.h", "kgrad.h", "mmops.h", os.path.join("..", "..", "include", "gpzoo_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # per source, after FLAGS: the kNN distances of spatial.hip and smooth.hip, and the k-means distances of kmeans.hip, are

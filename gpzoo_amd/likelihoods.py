@@ -10,7 +10,9 @@ as the reference, plus ``expected_loglik`` -- the fused fp32 training-step form
 dispersion per gene (the nsf paper's ``lik="nb"``): ``pY`` is a torch NegativeBinomial and ``expected_loglik`` runs
 the fused ``gpz_nb_nsf`` step.
 ``RSF`` and ``FA`` at the end are the Gaussian factor models for normalised, real-valued expression: real loadings, an
-intercept and a noise level per gene, and an exact ``expected_loglik`` through the fused ``gpz_gaussian_fa`` step.
+intercept and a noise level per gene, and an exact ``expected_loglik`` through the fused ``gpz_gaussian_fa`` step -- or,
+for a ``SparseExpression`` (centred log-normalised counts held as the stored entries minus a per-gene offset,
+``utilities.log_normalize``), through ``gpz_gaussian_fa_sparse``.
 """
 from __future__ import annotations
 
@@ -287,6 +289,86 @@ class TransposedCounts:
         return f"TransposedCounts(shape={self.shape}, dtype={self.dtype}, device={self.device})"
 
 
+class SparseExpression:
+    """The (D genes, N spots) real matrix ``values - offset[:, None]`` held as the stored entries of ``values`` (a
+    ``SparseCounts``-structured object: the same six index / value arrays, so the by-spot and by-gene orders are reused)
+    and a (D,) fp64 ``offset``.  Centred log-normalised counts are of this form (``utilities.log_normalize``): the values
+    have exactly the sparsity of the counts, and nothing of D x N elements is held.
+
+    It is what the Gaussian factor models (``RSF``, ``FA``) take in place of a dense array: ``expected_loglik``, ``score``
+    and the training loops evaluate it through gpz_gaussian_fa_sparse.  ``y[:, idx]`` with a 1-D integer tensor of distinct
+    spots is a no-copy view (``SparseCounts.__getitem__``, its deferred check included); a view of a view raises TypeError.
+    It holds no counts: the Poisson / NB steps, the deviances, ``regularized_nmf`` and ``scanpy_sizefactors`` refuse it."""
+
+    def __init__(self, values, offset):
+        if not isinstance(values, SparseCounts):
+            raise TypeError(f"SparseExpression: values must be a SparseCounts-structured object, got {type(values).__name__}")
+        offset = torch.as_tensor(offset).detach().to(device=values.device, dtype=torch.float64).reshape(-1).contiguous()
+        if offset.numel() != values.shape[0]:
+            raise ValueError(f"SparseExpression: offset has {offset.numel()} values for {values.shape[0]} genes")
+        self.values, self.offset = values, offset
+
+    @property
+    def shape(self):
+        return self.values.shape
+
+    @property
+    def device(self):
+        return self.values.device
+
+    @property
+    def nnz(self) -> int:
+        return self.values.nnz
+
+    @property
+    def is_view(self) -> bool:
+        return self.values.base is not self.values
+
+    def to(self, device):
+        moved = self.values.to(device)
+        return self if moved is self.values else SparseExpression(moved, self.offset.to(moved.device))
+
+    def cuda(self, device=None):
+        return self.to(torch.device("cuda") if device is None else device)
+
+    def cpu(self):
+        return self.to("cpu")
+
+    def to_dense(self):
+        """The (D, N) array in fp32 (of a view: its B columns): ``values.to_dense() - offset[:, None]``, formed in fp64."""
+        return (self.values.to_dense().double() - self.offset[:, None]).to(torch.float32)
+
+    def __getitem__(self, key):
+        if self.is_view:
+            raise TypeError("SparseExpression: y[:, idx] of a view; index the SparseExpression itself")
+        return SparseExpression(self.values[key], self.offset)
+
+    def __repr__(self):
+        return f"SparseExpression(shape={tuple(self.shape)}, device={self.device}{', view' if self.is_view else ''})"
+
+
+def _counts_expected(y, who):
+    """A ``SparseExpression`` holds real-valued expression, not counts: the count likelihoods refuse it."""
+    if isinstance(y, SparseExpression):
+        raise TypeError(f"{who}: a SparseExpression holds real-valued expression (values - offset), not counts; the count "
+                        "likelihoods take a SparseCounts or a dense count array, the Gaussian models (RSF, FA) take this")
+
+
+def _segment_sums(v, ptr):
+    """fp64 sums of the runs ``v[ptr[i]:ptr[i + 1]]`` in a fixed order (0 for an empty run)."""
+    v = v.to(torch.float64)
+    if v.numel() == 0:
+        return torch.zeros(ptr.numel() - 1, dtype=torch.float64, device=ptr.device)
+    return torch.segment_reduce(v, "sum", lengths=torch.diff(ptr), unsafe=True)
+
+
+def _gene_moments(expr):
+    """(sum_n z, sum_n z^2) per gene over all spots of a whole ``SparseExpression``, fp64."""
+    v = expr.values
+    z = v.col_val[v.row_perm.long()].to(torch.float64)
+    return _segment_sums(z, v.row_ptr), _segment_sums(z * z, v.row_ptr)
+
+
 def _offsets(sorted_ids, n):
     """(n + 1,) int64 start offsets of the runs of an ascending id array."""
     out = torch.zeros(n + 1, dtype=torch.int64, device=sorted_ids.device)
@@ -352,6 +434,7 @@ class _SparsePoissonLogLik(torch.autograd.Function):
 
 def _loglik_function(y):
     """The autograd function of the fused Poisson step for this form of the counts: the caller chooses by what they pass."""
+    _counts_expected(y, "poisson_expected_loglik")
     return _SparsePoissonLogLik if isinstance(y, SparseCounts) else _PoissonLogLik
 
 
@@ -407,6 +490,7 @@ class _SparseNBLogLik(torch.autograd.Function):
 
 def _nb_loglik_function(y):
     """The autograd function of the fused negative-binomial step for this form of the counts (``_loglik_function``'s sibling)."""
+    _counts_expected(y, "nb_expected_loglik")
     return _SparseNBLogLik if isinstance(y, SparseCounts) else _NBLogLik
 
 
@@ -489,6 +573,7 @@ def poisson_deviance(qF_list, W_list, V_pos, y, *, lognormal_mean=True):
     V_pos (B,) positive size factors; y: the (D, B) counts, dense (gpz_poisson_deviance) or a ``SparseCounts`` / its view
     ``y[:, idx]`` (gpz_poisson_deviance_sparse).  The (D, B) rate is never materialised.  Returns a ``PoissonDeviance``."""
     from . import ops
+    _counts_expected(y, "poisson_deviance")
     with torch.no_grad():
         mean = torch.cat([q.mean for q in qF_list], dim=0)
         scale = torch.cat([q.scale for q in qF_list], dim=0)
@@ -541,6 +626,7 @@ def nb_deviance(qF_list, W_list, V_pos, theta_pos, y, *, lognormal_mean=True):
     Arguments as for ``poisson_deviance``; y dense (gpz_nb_deviance) or a ``SparseCounts`` / its view ``y[:, idx]``
     (gpz_nb_deviance_sparse).  Returns an ``NBDeviance``."""
     from . import ops
+    _counts_expected(y, "nb_deviance")
     with torch.no_grad():
         mean = torch.cat([q.mean for q in qF_list], dim=0)
         scale = torch.cat([q.scale for q in qF_list], dim=0)
@@ -950,15 +1036,38 @@ class _GaussianFALogLik(torch.autograd.Function):
         return g * dmean, g * dscale, g * dW, g * db, g * dsd, None
 
 
+class _SparseGaussianFALogLik(torch.autograd.Function):
+    """_GaussianFALogLik for a SparseExpression (or its view y[:, idx]) through gpz_gaussian_fa_sparse."""
+
+    @staticmethod
+    def forward(ctx, mean, scale, W, b, noise_sd, y):
+        from . import ops
+        ll, _, _, dmean, dscale, dW, db, dsd = ops.gaussian_fa_sparse(mean, scale, W, b, noise_sd, y)
+        ctx.save_for_backward(dmean.to(mean.dtype), dscale.to(scale.dtype), dW.to(W.dtype), db.to(b.dtype),
+                              dsd.to(noise_sd.dtype))
+        return ll.to(mean.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        dmean, dscale, dW, db, dsd = ctx.saved_tensors
+        return g * dmean, g * dscale, g * dW, g * db, g * dsd, None
+
+
+def _gaussian_loglik_function(y):
+    """The autograd function of the fused Gaussian step for this form of the data (``_loglik_function``'s sibling)."""
+    return _SparseGaussianFALogLik if isinstance(y, SparseExpression) else _GaussianFALogLik
+
+
 def gaussian_expected_loglik(qF_list, W_list, b, noise_sd, y):
     """Exact E_q[log p(y | F)] for y ~ Normal(b[:, None] + sum_k W_k F_k, noise_sd[:, None]), F_k ~ qF_k independent.
 
     qF_list: Normal distributions over (L_k, N) factors; W_list: real (D, L_k) loadings; b (D,); noise_sd (D,) positive
-    standard deviations; y: the dense (D, N) data.  Differentiable in every argument but y (gpz_gaussian_fa)."""
+    standard deviations; y: the (D, N) data, dense (gpz_gaussian_fa) or a ``SparseExpression`` / its view ``y[:, idx]``
+    (gpz_gaussian_fa_sparse).  Differentiable in every argument but y."""
     mean = torch.cat([q.mean for q in qF_list], dim=0)
     scale = torch.cat([q.scale for q in qF_list], dim=0)
     W = torch.cat(list(W_list), dim=1)
-    return _GaussianFALogLik.apply(mean, scale, W, b, noise_sd, y)
+    return _gaussian_loglik_function(y).apply(mean, scale, W, b, noise_sd, y)
 
 
 class GaussianScore(NamedTuple):
@@ -977,16 +1086,20 @@ class GaussianScore(NamedTuple):
 
 def gaussian_score(qF_list, W_list, b, noise_sd, y):
     """``GaussianScore`` of the dense (D, B) data ``y`` from the value-only form of gpz_gaussian_fa (one pass over y); the
-    null sums of squares come from a plain torch reduction of y in fp64."""
+    null sums of squares come from a plain torch reduction of y in fp64.  Of a ``SparseExpression`` (or its view): the
+    value-only form of gpz_gaussian_fa_sparse, which returns the null sums of squares itself (``ss_per_gene``)."""
     from . import ops
     with torch.no_grad():
         mean = torch.cat([q.mean for q in qF_list], dim=0)
         scale = torch.cat([q.scale for q in qF_list], dim=0)
         W = torch.cat(list(W_list), dim=1)
-        ll, sse = ops.gaussian_fa(mean, scale, W, b, noise_sd, y, grads=False)
         D, B = y.shape
-        yd = y.detach().double()
-        null = ((yd - yd.mean(dim=1, keepdim=True)) ** 2).sum(dim=1)
+        if isinstance(y, SparseExpression):
+            ll, sse, null = ops.gaussian_fa_sparse(mean, scale, W, b, noise_sd, y, grads=False)
+        else:
+            ll, sse = ops.gaussian_fa(mean, scale, W, b, noise_sd, y, grads=False)
+            yd = y.detach().double()
+            null = ((yd - yd.mean(dim=1, keepdim=True)) ** 2).sum(dim=1)
         return GaussianScore(loglik=ll.clone(), sse_per_gene=sse, mse_per_gene=sse / B, mse=sse.sum() / (D * B),
                              r2_per_gene=_explained(sse, null), r2=_explained(sse.sum(), null.sum()))
 
@@ -1018,21 +1131,43 @@ def _known_kwargs(who, kwargs, known):
 
 def _init_gaussian(module, y, L, noise0):
     """Parameters of the Gaussian factor models: W (D, L) real = randn / sqrt(L), b (D,) = the row means of y, noise (D,)
-    raw with softplus(noise) = the row standard deviations of y floored at 1e-3, or the positive scalar ``noise0``."""
+    raw with softplus(noise) = the row standard deviations of y floored at 1e-3, or the positive scalar ``noise0``.
+    Of a whole ``SparseExpression`` the means and standard deviations come from fp64 segment sums over the stored
+    entries (the offset shifts the mean and cancels in the deviation); nothing is densified."""
     import numpy as np
     from .utilities import init_softplus
     D, N = y.shape
     dt = torch.get_default_dtype()
-    yd = torch.as_tensor(y).detach().double()
+    if isinstance(y, SparseExpression):
+        if y.is_view:
+            raise TypeError(f"{type(module).__name__}: built from a view y[:, idx]; pass the whole SparseExpression")
+        s1, s2 = _gene_moments(y)
+        row_mean = s1 / N - y.offset
+        row_sd = (s2 / N - (s1 / N) ** 2).clamp_min(0.0).sqrt()
+    else:
+        yd = torch.as_tensor(y).detach().double()
+        row_mean = yd.mean(dim=1)
+        row_sd = None
     module.W = nn.Parameter(torch.randn((D, L)) / float(L) ** 0.5)
-    module.b = nn.Parameter(yd.mean(dim=1).to(dtype=dt, device="cpu"))
+    module.b = nn.Parameter(row_mean.to(dtype=dt, device="cpu"))
     if noise0 is None:
-        sd = yd.std(dim=1, unbiased=False).clamp_min(1e-3).cpu().numpy()
+        sd = (yd.std(dim=1, unbiased=False) if row_sd is None else row_sd).clamp_min(1e-3).cpu().numpy()
     else:
         if not float(noise0) > 0:
             raise ValueError(f"{type(module).__name__}: noise0 must be positive, got {noise0}")
         sd = np.full((D,), float(noise0), dtype=np.float64)
     module.noise = nn.Parameter(torch.as_tensor(init_softplus(sd), dtype=dt))
+
+
+class _DenseNormal(distributions.Normal):
+    """torch's Normal as ``RSF`` / ``FA`` return it from ``forward``: the sampled (E, D, N) form has no sparse evaluation, so
+    ``log_prob`` of a ``SparseExpression`` raises TypeError instead of torch's message about a non-tensor value."""
+
+    def log_prob(self, value):
+        if isinstance(value, (SparseExpression, SparseCounts)):
+            raise TypeError(f"pY.log_prob: a {type(value).__name__} goes through the fused step only "
+                            "(model.expected_loglik / model.score); the sampled form needs the dense array, y.to_dense()")
+        return super().log_prob(value)
 
 
 class RSF(nn.Module):
@@ -1050,7 +1185,7 @@ class RSF(nn.Module):
 
     def _pY(self, qF, E):
         sd = _noise_sd(self.noise)
-        return _dist(distributions.Normal, self.b[:, None] + torch.matmul(self.W, qF.rsample((E,))), sd[:, None])
+        return _dist(_DenseNormal, self.b[:, None] + torch.matmul(self.W, qF.rsample((E,))), sd[:, None])
 
     def _qF(self, X, idx, kwargs):
         _known_kwargs("RSF", kwargs, ("groupsX",))

@@ -1389,8 +1389,11 @@ def gaussian_fa(mean, scale, W, b, noise_sd, y, grads: bool = True):
     (loglik fp64 scalar, sse_per_gene fp64 (D,), dmean, dscale, dW, db, dnoise_sd), or the first two with
     ``grads=False`` (one pass over y instead of two).  ``sse_per_gene`` is the squared error of the predictive mean
     b + W mean; ``loglik`` also carries the variance of q(F).  Nothing here waits for the device: the call can be captured
-    in a graph.  A ``SparseCounts`` raises TypeError: normalised data is dense."""
-    from .likelihoods import SparseCounts
+    in a graph.  A ``SparseCounts`` raises TypeError: normalised data is dense.  So does a ``SparseExpression`` (centred
+    log-normalised counts held as their non-zeros): that form goes through ``gaussian_fa_sparse``."""
+    from .likelihoods import SparseCounts, SparseExpression
+    if isinstance(y, SparseExpression):
+        raise TypeError("gaussian_fa: takes a dense array; a SparseExpression goes through gaussian_fa_sparse")
     if isinstance(y, SparseCounts):
         raise TypeError("gaussian_fa: the Gaussian step takes dense real-valued data (normalised expression is dense): "
                         "a SparseCounts holds counts, pass the normalised array")
@@ -1426,6 +1429,72 @@ def _gaussian_fa(mean, scale, W, b, noise_sd, y, grads):
                              *(_ptr(t) for t in out), _ptr(ws), ws.numel(), _stream(dev))
     _lib.check(rc, "gpz_gaussian_fa")
     return (ll[0], sse, *out) if grads else (ll[0], sse)
+
+
+def gaussian_fa_sparse_plan(N: int, B: int, D: int, Lt: int, nnz: int) -> dict:
+    """How ``gaussian_fa_sparse`` covers a shape (gpz_gaussian_fa_sparse_plan, a host-only query: no device needed):
+    ``gene_chunk`` (stored entries of a gene row per wave of the gene pass), ``n_gene_chunks`` (the bound on the length of its
+    work list), ``factors_padded`` (Lt rounded up to the kernel instance), ``workspace_bytes``."""
+    lib = _lib.load()
+    gc, fp, nch, nb = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+    rc = lib.gpz_gaussian_fa_sparse_plan(int(N), int(B), int(D), int(Lt), int(nnz), C.byref(gc), C.byref(nch), C.byref(fp),
+                                         C.byref(nb))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, n_gene_chunks=nch.value, factors_padded=fp.value, workspace_bytes=int(nb.value))
+
+
+def gaussian_fa_sparse(mean, scale, W, b, noise_sd, expr, idx=None, grads: bool = True):
+    """``gaussian_fa`` for expression held as its stored entries minus a per-gene offset (gpz_gaussian_fa_sparse): exact sums
+    over the non-zeros plus Lt x Lt Gram matrices -- O(nnz_B Lt + (B + D) Lt^2) work, nothing of D x B elements.
+
+    expr: a ``likelihoods.SparseExpression`` (D, N), or the view ``expr[:, idx]`` of one.  mean, scale (Lt,B) with B = N, or
+    B = len(idx) for a view; W (D,Lt) real; b, noise_sd (D,).  ``idx``: shorthand for ``expr[:, idx]``.  Returns
+    (loglik fp64 scalar, sse_per_gene fp64 (D,), ss_per_gene fp64 (D,), dmean, dscale, dW, db, dnoise_sd), or the first three
+    with ``grads=False`` (the same bits).  ``ss_per_gene`` is the null sum of squares sum_n (y - mean_n y)^2 of the batch.
+    Nothing here waits for the device: the call can be captured in a graph."""
+    from .likelihoods import SparseExpression
+    if not isinstance(expr, SparseExpression):
+        raise TypeError(f"gaussian_fa_sparse: expr must be a SparseExpression, got {type(expr).__name__}")
+    if idx is not None:
+        expr = expr[:, idx]
+    return _gaussian_fa_sparse(mean, scale, W, b, noise_sd, expr, grads)
+
+
+@_on_device
+def _gaussian_fa_sparse(mean, scale, W, b, noise_sd, expr, grads):
+    _need_cuda(mean, scale, W, b, noise_sd)
+    dev = mean.device
+    if expr.device != dev:
+        raise RuntimeError(f"gpzoo_amd: the expression lives on {expr.device}, the model on {dev}: move it with expr.to(device)")
+    lib = _lib.load()
+    f32 = torch.float32
+    mean, scale, W, b, noise_sd = (t.detach().to(f32).contiguous() for t in (mean, scale, W, b, noise_sd))
+    if mean.dim() != 2:
+        raise ValueError(f"gaussian_fa_sparse: mean {tuple(mean.shape)} must be (Lt, B)")
+    view, base = expr.values, expr.values.base
+    D, N = base.shape
+    Lt, B = mean.shape
+    if tuple(expr.shape) != (D, B) or scale.shape != (Lt, B) or W.shape != (D, Lt) or b.shape != (D,) or noise_sd.shape != (D,):
+        raise ValueError(f"gaussian_fa_sparse: expr {tuple(expr.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, W "
+                         f"{tuple(W.shape)}, b {tuple(b.shape)}, noise_sd {tuple(noise_sd.shape)} do not fit together")
+    nnz = int(base.col_val.numel())
+    nb = C.c_int64()
+    if lib.gpz_gaussian_fa_sparse_plan(N, B, D, Lt, nnz, None, None, None, C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    ll = torch.empty(1, dtype=torch.float64, device=dev)
+    sse = torch.empty(D, dtype=torch.float64, device=dev)
+    ss = torch.empty(D, dtype=torch.float64, device=dev)
+    out = [torch.empty((Lt, B), dtype=f32, device=dev), torch.empty((Lt, B), dtype=f32, device=dev),
+           torch.empty((D, Lt), dtype=f32, device=dev), torch.empty((D,), dtype=f32, device=dev),
+           torch.empty((D,), dtype=f32, device=dev)] if grads else [None] * 5
+    ws = _workspace(dev, nb.value)
+    rc = lib.gpz_gaussian_fa_sparse(_ptr(mean), _ptr(scale), _ptr(W), _ptr(b), _ptr(noise_sd), _ptr(expr.offset),
+                                    _ptr(base.col_ptr), _ptr(base.col_gene), _ptr(base.col_val), _ptr(base.row_ptr),
+                                    _ptr(base.row_spot), _ptr(base.row_perm), _ptr(view.idx), _ptr(view.pos), N, B, D, nnz, Lt,
+                                    _ptr(ll), _ptr(sse), _ptr(ss), *(_ptr(t) for t in out), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_gaussian_fa_sparse")
+    return (ll[0], sse, ss, *out) if grads else (ll[0], sse, ss)
 
 
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:

@@ -103,10 +103,10 @@ def _spots(X, batch_size):
 
 
 def _fused_counts_only(model, y, fused):
-    """A SparseCounts has no (E,D,N) form: only the fused step takes it."""
-    from .likelihoods import SparseCounts
-    if isinstance(y, SparseCounts) and not (fused and hasattr(model, "expected_loglik")):
-        raise TypeError("SparseCounts go through the fused step only: pass fused=True to a model with "
+    """A SparseCounts has no (E,D,N) form: only the fused step takes it.  The same for a SparseExpression."""
+    from .likelihoods import SparseCounts, SparseExpression
+    if isinstance(y, (SparseCounts, SparseExpression)) and not (fused and hasattr(model, "expected_loglik")):
+        raise TypeError(f"{type(y).__name__} goes through the fused step only: pass fused=True to a model with "
                         "expected_loglik (pY.log_prob(y) needs the dense array, y.to_dense())")
 
 
@@ -518,7 +518,8 @@ def init_softplus(mat, minval=1e-5):
 
 def _transposed_counts(Y, who):
     """True for ``counts.T`` of a ``SparseCounts``; the ``SparseCounts`` itself (genes x spots) is refused, not transposed."""
-    from .likelihoods import SparseCounts, TransposedCounts
+    from .likelihoods import SparseCounts, TransposedCounts, _counts_expected
+    _counts_expected(Y, who)
     if isinstance(Y, SparseCounts):
         raise TypeError(f"{who}: Y is a SparseCounts (genes x spots); pass its .T (obs x feat)")
     return isinstance(Y, TransposedCounts)
@@ -540,6 +541,43 @@ def scanpy_sizefactors(Y):
     import numpy as np
     totals = _spot_totals(Y, "scanpy_sizefactors")
     return totals / np.median(totals)
+
+
+def log_normalize(counts, size_factors=None, center=True, offset=None):
+    """The normalisation the nsf paper feeds to RSF / MEFISTO / FA -- log1p of size-normalised counts, centred per gene --
+    of a whole ``SparseCounts``, as a ``SparseExpression``: ``z = log1p(y / sz[n])`` on the stored entries only (a zero
+    count stays zero, so z has exactly the sparsity of the counts) and the centring as the (D,) fp64 ``offset``.  O(nnz):
+    the index arrays are shared with ``counts``, only the values are new (formed in fp64, stored in fp32).
+
+    ``size_factors``: (N,) positive; default ``scanpy_sizefactors(counts.T)`` (a spot without counts has no stored entry,
+    so nothing divides by zero).  ``center=True``: ``offset`` = the per-gene mean of z over all N spots (fp64 segment sums);
+    ``center=False``: zeros.  ``offset=``: a given (D,) tensor instead, e.g. the training split's means for a held-out
+    split.  Views, dense tensors and a ``SparseExpression`` raise TypeError."""
+    from .likelihoods import SparseCounts, SparseExpression, _gene_moments
+    if not isinstance(counts, SparseCounts) or counts.base is not counts:
+        what = "a view y[:, idx]" if isinstance(counts, SparseCounts) else type(counts).__name__
+        raise TypeError(f"log_normalize: a whole SparseCounts expected, got {what} (build one with SparseCounts(y))")
+    D, N = counts.shape
+    dev = counts.device
+    if size_factors is None:
+        size_factors = scanpy_sizefactors(counts.T)
+    sz = torch.as_tensor(size_factors).detach().reshape(-1).to(device=dev, dtype=torch.float64)
+    if sz.numel() != N:
+        raise ValueError(f"log_normalize: {sz.numel()} size factors for {N} spots")
+    values = object.__new__(SparseCounts)
+    values.base, values.idx, values.pos, values.shape = values, None, None, counts.shape
+    for k in SparseCounts._PARTS:
+        setattr(values, k, getattr(counts, k))
+    values.col_val = torch.log1p(counts.col_val.to(torch.float64) / sz[counts._spots()]).to(torch.float32)
+    if offset is not None:
+        off = torch.as_tensor(offset).detach().reshape(-1).to(device=dev, dtype=torch.float64)
+        if off.numel() != D:
+            raise ValueError(f"log_normalize: offset has {off.numel()} values for {D} genes")
+    elif center:
+        off = _gene_moments(SparseExpression(values, torch.zeros(D, dtype=torch.float64, device=dev)))[0] / N
+    else:
+        off = torch.zeros(D, dtype=torch.float64, device=dev)
+    return SparseExpression(values, off)
 
 
 def train_val_split(X, y, train_frac=0.95, sz="constant"):

@@ -55,7 +55,10 @@
  * the NB log density and the Poisson log density of held-out counts under the predictive mean rate and a per-gene theta;
  * gpz_gaussian_fa and the host-only gpz_gaussian_fa_plan -- the exact expected Gaussian log-likelihood of the real-valued
  * factor models (RSF over a GP prior, FA over an i.i.d. one) and its gradients; its scratch is the explicit argument
- * `partials`, sized by the plan query.
+ * `partials`, sized by the plan query;
+ * gpz_gaussian_fa_sparse and the host-only gpz_gaussian_fa_sparse_plan -- gpz_gaussian_fa for expression stored as its
+ * non-zeros minus a per-gene offset (centred log-normalised counts): the same outputs as exact sums over the non-zeros
+ * plus Lt x Lt Gram matrices; its scratch is `partials` again, sized by the plan query's workspace_bytes.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -362,6 +365,41 @@ int gpz_gaussian_fa(const float* mean, const float* scale, const float* W, const
                     const float* y, int64_t N, int64_t D, int32_t Lt, double* loglik, double* sse_per_gene,
                     float* dmean, float* dscale, float* dW, float* db, float* dnoise_sd,
                     void* partials, size_t partials_bytes, void* stream);
+
+/* gpz_gaussian_fa for expression stored as its non-zeros minus a per-gene offset (csrc/gaussian_sparse.hip):
+ *   y[d,n] = z[d,n] - offset[d],
+ * where z is held in the two orders of gpz_poisson_nsf_sparse below (col_ptr, col_gene, col_val by spot; row_ptr, row_spot,
+ * row_perm by gene; the same trust in the arrays) -- log1p of size-normalised counts, centred per gene, is of this form
+ * and z then has exactly the sparsity of the counts.  The expected log-likelihood is quadratic in y, so the offset folds
+ * into the intercept: with a = b + offset, iv = 1 / noise_sd^2, p[d,n] = a[d] + W[d,:] . mean[:,n], M1 = sum_n mean[:,n],
+ * G = sum_n mean[:,n] mean[:,n]^T, S2[l] = sum_n scale[l,n]^2, u = sum_d iv a W[d,:], H = sum_d iv W[d,:] W[d,:]^T,
+ *   sse_per_gene[d] = sum_nz(d) z (z - 2 p) + B a^2 + 2 a W[d,:] . M1 + W[d,:] G W[d,:]^T      R[d] = sse + sum_l W[d,l]^2 S2[l]
+ *   loglik[0]       = sum_d [ -B (log(2 pi) / 2 + log noise_sd[d]) - iv R[d] / 2 ]
+ *   ss_per_gene[d]  = sum_nz(d) z^2 - (sum_nz(d) z)^2 / B    (fp64; the null sum of squares of R^2, the offset cancels)
+ *   dmean[:,n] = sum_nz(n) iv z W[d,:] - u - H mean[:,n],  dscale[l,n] = -scale[l,n] H[l,l],
+ *   dW[d,:] = iv [ sum_nz(d) z mean[:,n] - a M1 - G W[d,:] - S2 * W[d,:] ],  db[d] = iv [ sum_nz(d) z - B a - W[d,:] . M1 ],
+ *   dnoise_sd[d] = -B / noise_sd + R[d] / noise_sd^3
+ * -- the numbers of gpz_gaussian_fa on the dense (D,B) array, for O(nnz_B Lt + (B + D) Lt^2) work; nothing of D x B or nnz
+ * elements is read, written or allocated beyond the stored entries themselves.  mean, scale (Lt,B), W (D,Lt), b, noise_sd
+ * (D,) fp32; offset (D,) fp64.  idx (B) lists the batch's distinct spots and pos (N) is its inverse (-1 outside the batch);
+ * both NULL: the whole data set, B = N.  sse_per_gene and ss_per_gene may be NULL.  The five gradient pointers are either
+ * all set or all NULL (value-only: loglik, sse_per_gene and ss_per_gene, the same bits as in a gradient call).
+ * Every accumulation and the quadratic terms are fp64 in a fixed order, no atomics: two calls agree bit for bit.  The
+ * scratch memory is the explicit argument `partials` as for gpz_gaussian_fa; it need not be cleared and may hold anything.
+ * Its size is the plan query's workspace_bytes; the plan (host only, any out pointer may be NULL) also reports gene_chunk
+ * (stored entries of a gene row per wave of the gene pass), n_gene_chunks (the bound D + nnz / gene_chunk on the length of
+ * its work list) and factors_padded (Lt rounded up to the kernel instance).
+ * 1 <= Lt <= 64, 1 <= B <= N, N, D, nnz < 2^31; noise_sd as for gpz_gaussian_fa.  The inputs need only their natural alignment,
+ * partials 16 bytes.  Argument errors return -1 before any launch with the reason in gpz_last_error. */
+int gpz_gaussian_fa_sparse_plan(int64_t N, int64_t B, int64_t D, int32_t Lt, int64_t nnz, int32_t* gene_chunk,
+                                int64_t* n_gene_chunks, int32_t* factors_padded, int64_t* workspace_bytes);
+int gpz_gaussian_fa_sparse(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                           const double* offset, const int64_t* col_ptr, const int32_t* col_gene, const float* col_val,
+                           const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
+                           const int32_t* idx, const int32_t* pos, int64_t N, int64_t B, int64_t D, int64_t nnz,
+                           int32_t Lt, double* loglik, double* sse_per_gene, double* ss_per_gene, float* dmean,
+                           float* dscale, float* dW, float* db, float* dnoise_sd, void* partials,
+                           size_t partials_bytes, void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
