@@ -7,11 +7,14 @@ on synthetic counts, against the same model started from mu = 0 and random loadi
 
     PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30
                                                    --inducing-from {subset,kmeans} --mu-from {smooth,projection}
-                                                   --sparse-counts DENSITY]
+                                                   --sparse-counts DENSITY [--select-genes NFEAT --rank-by {deviance,moran}]]
 
 ``--sparse-counts DENSITY`` thins the counts to about that fraction of non-zeros and runs the whole chain on them as a
 ``SparseCounts``: the size factors and the NMF start from ``counts.T``, the fit from ``counts``.  The dense count array
-then never reaches the device.
+then never reaches the device.  ``--select-genes NFEAT`` ranks the genes of those counts first (``rank_genes``: Poisson deviance
+against a constant-rate null, or Moran's I of the log-normalised counts over the spots' 6-neighbour graph) and runs the chain
+on the NFEAT best (``counts.select_genes``) -- the reference's ``ad[:, :nfeat]`` of genes sorted by importance.  The size
+factors stay those of the whole data set.
 """
 import argparse
 
@@ -23,7 +26,7 @@ from gpzoo.gp import SVGP
 from gpzoo.kernels import NSF_RBF
 from gpzoo.likelihoods import NSF2, SparseCounts
 from gpzoo.utilities import (init_softplus, kmeans_inducing_points, project_factors_to_inducing, regularized_nmf,
-                             rescale_spatial_coords, scanpy_sizefactors, smooth_spatial_factors, train)
+                             rank_genes, rescale_spatial_coords, scanpy_sizefactors, smooth_spatial_factors, train)
 
 
 def synthetic_counts(N, D, L, rng):
@@ -61,7 +64,13 @@ def main():
                          "projection onto Z (project_factors_to_inducing, the notebooks' Kzx @ Kxz composition)")
     ap.add_argument("--sparse-counts", type=float, default=None, metavar="DENSITY",
                     help="keep about this fraction of the counts as non-zeros and run the chain through SparseCounts")
+    ap.add_argument("--select-genes", "--select_genes", type=int, default=None, metavar="NFEAT",
+                    help="with --sparse-counts: rank the genes and keep the NFEAT best before the NMF start")
+    ap.add_argument("--rank-by", "--rank_by", choices=("deviance", "moran"), default="deviance",
+                    help="the score --select-genes ranks by (rank_genes)")
     a = ap.parse_args()
+    if a.select_genes is not None and a.sparse_counts is None:
+        raise SystemExit("--select-genes ranks the stored non-zeros of a SparseCounts: pass --sparse-counts DENSITY with it")
     dev = torch.device("cuda")
     rng = np.random.default_rng(0)
     X, Y = synthetic_counts(a.spots, a.genes, a.factors, rng)
@@ -75,6 +84,11 @@ def main():
         print(f"sparse counts: {Y.nnz} non-zeros, {Y.nnz / (a.spots * a.genes):.1%} of {a.genes} x {a.spots}")
         sz = scanpy_sizefactors(Y.T)
         sz = np.maximum(sz, sz[sz > 0].min())           # a spot thinned to nothing says nothing about its depth; log(sz) stays finite
+        if a.select_genes is not None:
+            order, score = rank_genes(Y, by=a.rank_by, coords=X if a.rank_by == "moran" else None, nfeat=a.select_genes)
+            Y = Y.select_genes(order)
+            print(f"selected {Y.shape[0]} of {a.genes} genes by {a.rank_by}: score {float(score[0]):.4g} ... {float(score[-1]):.4g}, "
+                  f"{Y.nnz} non-zeros kept")
         F, W = regularized_nmf(Y.T, L, sz=sz, **nmf_kw)
     else:
         sz = scanpy_sizefactors(Y)

@@ -1,0 +1,323 @@
+// gene_rank.hip -- two per-gene scores of counts (or log-normalised values) stored as their non-zeros, for ranking and
+// selecting genes ahead of a fit: the deviance against a constant-rate null (scry's devianceFeatureSelection, the nsf
+// paper's ranking) and Moran's I over the spots' K-neighbour graph (squidpy's spatial_autocorr(mode="moran")).  Both are
+// exact sums over the stored entries plus O(N + D) terms; nothing of D x N or nnz elements is allocated.
+//
+// The data set arrives in the by-gene order of gpzoo_amd.likelihoods.SparseCounts: gene d owns [row_ptr[d], row_ptr[d + 1]),
+// its k-th entry sits at spot row_spot[k] and has the value col_val[row_perm[k]].
+//
+// Deviance, S = sum_n size[n], sum = sum_nz y, p = sum / S:
+//   Poisson   2 [ sum_nz y log(y / size_n) - sum log(sum / S) ]
+//   binomial  2 [ sum_nz ( y log(y / size_n) + (size_n - y) log1p(-y / size_n) ) - sum (log p - log1p(-p)) - S log1p(-p) ]
+// Moran's I with weights 1 / K, xbar = S / N, S = sum x, Q = sum x^2, C = sum_{i in nz} x_i sum_{j in nbr(i)} x_j,
+// A = sum_{i in nz} indeg(i) x_i (sum_i sum_{j in nbr(i)} x_j with the two sums exchanged):
+//   I = [ C - xbar (K S + A) + N K xbar^2 ] / ( K (Q - N xbar^2) )
+// -- sum_i z_i sum_j z_j of the dense kernel (spatial.hip) expanded around the zeros, which are never visited.
+//
+// Gene pass (both entries): one workgroup of GR_THREADS threads per gene at a time, genes dealt to a fixed number of
+// workgroups in a fixed order (gene d, d + G, ...).  Thread t adds the entries t, t + GR_THREADS, ... of the row in that
+// order in fp64, the GR_THREADS partial sums are added in a fixed binary tree: the result of a gene depends on neither the
+// grid nor the workgroup that computes it, and two calls agree bit for bit.  A row of N entries is GR_THREADS-wide
+// coalesced sweeps; a row of one entry costs one sweep, and the other workgroups keep the device busy meanwhile.
+//
+// Neighbour lookup of the Moran pass: every workgroup owns one line of N floats in the scratch memory, which it zeroes
+// itself at the start of the launch.  Per gene it scatters the row into the line, gathers the K neighbours of every stored
+// entry from it, and then clears exactly the words it scattered: O(nnz (K + 2)) memory operations, no search, and a
+// scratch of workgroups x N x 4 bytes whatever D is.  The in-degree of the table is counted once per call with integer
+// atomics (a histogram; no atomics on values); that pass also checks every entry of the table and raises info.
+//
+// Built with -ffp-contract=off: every product and sum of the closing formulas is rounded on its own, so the numbers are
+// those of the same expressions written in numpy (the CPU tests evaluate them that way), not of a compiler's choice of fma.
+// The kernels wait for memory, not for the ALUs, so this costs nothing.
+#include "common.h"
+
+namespace gpz {
+namespace grk {
+
+constexpr int GR_THREADS = 256;    // threads of a workgroup = stored entries of a row per sweep (the plan's gene_chunk)
+constexpr int GR_MAX_WG = 256;     // workgroups of the Moran pass (one per CU): its scratch is GR_MAX_WG lines, and more lines
+                                   // in flight bought nothing (measured: DESIGN.md section 5)
+constexpr int GR_DEV_WG = 2048;    // workgroups of the deviance pass (eight per CU, a full CU of waves; it has no lines)
+constexpr int GR_KMAX = 32;
+
+struct GrRows {
+  const int64_t* row_ptr; const int32_t* row_spot; const int32_t* row_perm; const float* col_val;
+  int64_t N, D, nnz;
+};
+
+// red[0] = the sum of red[0 .. GR_THREADS) in a fixed binary tree; every thread of the workgroup calls it
+template <int NV>
+__device__ inline void gr_tree(double (*red)[GR_THREADS]) {
+  __syncthreads();
+  for (int h = GR_THREADS / 2; h >= 1; h >>= 1) {
+    if (int(threadIdx.x) < h)
+      for (int v = 0; v < NV; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
+    __syncthreads();
+  }
+}
+
+// the row of gene d, clamped to the stored entries: an inconsistent row_ptr reads nothing out of bounds
+__device__ inline void gr_row(const GrRows& r, int64_t d, int64_t& lo, int64_t& hi) {
+  lo = r.row_ptr[d];
+  hi = r.row_ptr[d + 1];
+  lo = lo < 0 ? 0 : (lo > r.nnz ? r.nnz : lo);
+  hi = hi < lo ? lo : (hi > r.nnz ? r.nnz : hi);
+}
+
+__device__ inline bool gr_entry(const GrRows& r, int64_t k, int32_t& spot, float& x) {
+  spot = r.row_spot[k];
+  const int32_t p = r.row_perm[k];
+  if (spot < 0 || spot >= r.N || p < 0 || p >= r.nnz) return false;
+  x = r.col_val[p];
+  return true;
+}
+
+// S = sum_n size[n]: one workgroup, strided per thread, then the tree
+__global__ __launch_bounds__(GR_THREADS) void gr_total_kernel(const double* __restrict__ size, int64_t N, double* __restrict__ total) {
+  __shared__ double red[1][GR_THREADS];
+  double a = 0.0;
+  for (int64_t n = threadIdx.x; n < N; n += GR_THREADS) a += size[n];
+  red[0][threadIdx.x] = a;
+  gr_tree<1>(red);
+  if (threadIdx.x == 0) total[0] = red[0][0];
+}
+
+__global__ __launch_bounds__(GR_THREADS) void gr_deviance_kernel(GrRows r, const double* __restrict__ size, int family,
+                                                                 const double* __restrict__ total, double* __restrict__ sum,
+                                                                 double* __restrict__ count, double* __restrict__ deviance) {
+  __shared__ double red[2][GR_THREADS];
+  const double S = total[0];
+  for (int64_t d = blockIdx.x; d < r.D; d += gridDim.x) {
+    int64_t lo, hi;
+    gr_row(r, d, lo, hi);
+    double sy = 0.0, sat = 0.0;
+    for (int64_t k = lo + threadIdx.x; k < hi; k += GR_THREADS) {
+      int32_t spot;
+      float x;
+      if (!gr_entry(r, k, spot, x)) continue;
+      const double y = double(x);
+      sy += y;
+      if (y > 0.0) {
+        const double sz = size[spot], q = y / sz;
+        double t = y * log(q);
+        if (family == 1 && sz > y) t += (sz - y) * log1p(-q);      // y == size_n: y log 1 + 0
+        sat += t;
+      }
+    }
+    red[0][threadIdx.x] = sy;
+    red[1][threadIdx.x] = sat;
+    gr_tree<2>(red);
+    if (threadIdx.x == 0) {
+      const double s = red[0][0];
+      double null = 0.0;
+      if (s > 0.0) {
+        const double p = s / S;
+        if (family == 0) {
+          null = s * log(p);
+        } else if (p < 1.0) {
+          const double l1 = log1p(-p);
+          null = s * (log(p) - l1) + S * l1;
+        }                                                           // p = 1: sum log 1 + 0
+      }
+      sum[d] = s;
+      count[d] = double(hi - lo);
+      deviance[d] = hi > lo ? 2.0 * (red[1][0] - null) : 0.0;
+    }
+    __syncthreads();
+  }
+}
+
+// every entry of the table once: the in-degree histogram (integer atomics) and the check of mi_rows -- an entry outside
+// [0, N) or naming its own row is counted nowhere, read nowhere, and raises info
+__global__ __launch_bounds__(GR_THREADS) void gr_indeg_kernel(const int64_t* __restrict__ nbr, int64_t N, int K,
+                                                              int32_t* __restrict__ indeg, int32_t* __restrict__ info) {
+  const int64_t e = int64_t(blockIdx.x) * GR_THREADS + threadIdx.x;
+  if (e >= N * K) return;
+  const int64_t i = e / K, j = nbr[e];
+  if (j < 0 || j >= N || j == i) {
+    *info = 1;
+    return;
+  }
+  atomicAdd(indeg + j, 1);
+}
+
+__global__ __launch_bounds__(GR_THREADS) void gr_moran_kernel(GrRows r, const int64_t* __restrict__ nbr, int K,
+                                                              const int32_t* __restrict__ indeg, float* __restrict__ lines,
+                                                              double* __restrict__ I) {
+  __shared__ double red[4][GR_THREADS];
+  __shared__ float lohi[2][GR_THREADS];
+  const int64_t N = r.N;
+  float* __restrict__ line = lines + int64_t(blockIdx.x) * N;
+  for (int64_t n = threadIdx.x; n < N; n += GR_THREADS) line[n] = 0.0f;
+  __syncthreads();
+  for (int64_t d = blockIdx.x; d < r.D; d += gridDim.x) {
+    int64_t lo, hi;
+    gr_row(r, d, lo, hi);
+    for (int64_t k = lo + threadIdx.x; k < hi; k += GR_THREADS) {
+      int32_t spot;
+      float x;
+      if (gr_entry(r, k, spot, x)) line[spot] = x;
+    }
+    __syncthreads();
+    double s = 0.0, q = 0.0, c = 0.0, a = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int64_t k = lo + threadIdx.x; k < hi; k += GR_THREADS) {
+      int32_t spot;
+      float xf;
+      if (!gr_entry(r, k, spot, xf)) continue;
+      const double x = double(xf);
+      const int64_t* __restrict__ row = nbr + int64_t(spot) * K;
+      double lag = 0.0;
+      for (int m = 0; m < K; ++m) {
+        const int64_t j = row[m];
+        if (j < 0 || j >= N || j == spot) continue;              // gr_indeg_kernel has told the caller
+        lag += double(line[j]);
+      }
+      s += x;
+      q += x * x;
+      c += x * lag;
+      a += double(indeg[spot]) * x;
+      mn = xf < mn ? xf : mn;
+      mx = xf > mx ? xf : mx;
+    }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = q;
+    red[2][threadIdx.x] = c;
+    red[3][threadIdx.x] = a;
+    lohi[0][threadIdx.x] = mn;
+    lohi[1][threadIdx.x] = mx;
+    __syncthreads();                                              // every gather of the line is done
+    for (int64_t k = lo + threadIdx.x; k < hi; k += GR_THREADS) {
+      const int32_t spot = r.row_spot[k];
+      if (spot >= 0 && spot < N) line[spot] = 0.0f;
+    }
+    for (int h = GR_THREADS / 2; h >= 1; h >>= 1) {
+      if (int(threadIdx.x) < h) {
+        for (int v = 0; v < 4; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
+        const float l2 = lohi[0][threadIdx.x + h], h2 = lohi[1][threadIdx.x + h];
+        if (l2 < lohi[0][threadIdx.x]) lohi[0][threadIdx.x] = l2;
+        if (h2 > lohi[1][threadIdx.x]) lohi[1][threadIdx.x] = h2;
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      const double Nd = double(N), Kd = double(K);
+      const double S = red[0][0], Q = red[1][0], Cs = red[2][0], A = red[3][0];
+      const double xbar = S / Nd;
+      const double den = Kd * (Q - Nd * (xbar * xbar));
+      const double num = Cs - xbar * (Kd * S + A) + Nd * Kd * (xbar * xbar);
+      const bool constant = hi - lo == N && lohi[0][0] == lohi[1][0];     // stored at every spot with one single value
+      I[d] = (hi > lo && !constant && den > 0.0) ? num / den : double(NAN);
+    }
+    __syncthreads();                                              // the line is clear and red is free for the next gene
+  }
+}
+
+struct GrPlan {
+  double* total;      // deviance: S
+  int32_t* indeg;     // Moran: (N,)
+  float* lines;       // Moran: (workgroups, N)
+  int workgroups;
+  size_t bytes;
+};
+
+static GrPlan gr_plan(int64_t N, int64_t D, bool moran, void* scratch) {
+  Carver c(scratch);
+  GrPlan p{};
+  const int cap = moran ? GR_MAX_WG : GR_DEV_WG;
+  p.workgroups = int(D < cap ? D : cap);
+  if (moran) {
+    p.indeg = c.take<int32_t>(size_t(N));
+    p.lines = c.take<float>(size_t(p.workgroups) * size_t(N));
+  } else {
+    p.total = c.take<double>(1);
+  }
+  p.bytes = c.used();
+  return p;
+}
+
+static int gr_check_shape(const char* who, int64_t N, int64_t D, int64_t nnz) {
+  GPZ_REQUIRE(N >= 1 && D >= 1 && nnz >= 0, "%s: bad extents (N = %lld, D = %lld, nnz = %lld)", who, (long long)N, (long long)D,
+              (long long)nnz);
+  GPZ_REQUIRE(N < (1ll << 31) && D < (1ll << 31) && nnz < (1ll << 31), "%s: spots, genes and non-zeros are indexed with 32 bits",
+              who);
+  return 0;
+}
+
+static int gr_check_k(const char* who, int64_t N, int32_t K) {
+  GPZ_REQUIRE(K >= 1 && K <= GR_KMAX && K < N, "%s: K = %d neighbours of N = %lld spots unsupported (1 <= K <= %d, K < N)", who, K,
+              (long long)N, GR_KMAX);
+  return 0;
+}
+
+}  // namespace grk
+}  // namespace gpz
+
+using namespace gpz;
+using namespace gpz::grk;
+
+extern "C" int gpz_gene_deviance_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t* gene_chunk, int32_t* workgroups,
+                                             int64_t* partials_bytes) {
+  if (int rc = gr_check_shape("gpz_gene_deviance_sparse", N, D, nnz)) return rc;
+  const GrPlan p = gr_plan(N, D, false, nullptr);
+  if (gene_chunk) *gene_chunk = GR_THREADS;
+  if (workgroups) *workgroups = p.workgroups;
+  if (partials_bytes) *partials_bytes = int64_t(p.bytes);
+  return 0;
+}
+
+extern "C" int gpz_gene_deviance_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
+                                        const float* col_val, const double* size, int64_t N, int64_t D, int64_t nnz,
+                                        int32_t family, double* sum, double* count, double* deviance, void* partials,
+                                        size_t partials_bytes, void* stream) {
+  GPZ_REQUIRE(row_ptr && size && sum && count && deviance && partials, "gpz_gene_deviance_sparse: null pointer");
+  if (int rc = gr_check_shape("gpz_gene_deviance_sparse", N, D, nnz)) return rc;
+  GPZ_REQUIRE(nnz == 0 || (row_spot && row_perm && col_val), "gpz_gene_deviance_sparse: null pointer (non-zeros)");
+  GPZ_REQUIRE(family == 0 || family == 1, "gpz_gene_deviance_sparse: family %d unknown (0 Poisson, 1 binomial)", family);
+  GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "gpz_gene_deviance_sparse: partials must be 16-byte aligned");
+  const GrPlan p = gr_plan(N, D, false, partials);
+  GPZ_REQUIRE(partials_bytes >= p.bytes, "gpz_gene_deviance_sparse: partials too small (%zu bytes, %zu needed)", partials_bytes,
+              p.bytes);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const GrRows r{row_ptr, row_spot, row_perm, col_val, N, D, nnz};
+  hipLaunchKernelGGL(gr_total_kernel, dim3(1), dim3(GR_THREADS), 0, s, size, N, p.total);
+  GPZ_LAUNCH_OK();
+  hipLaunchKernelGGL(gr_deviance_kernel, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, size, int(family), p.total, sum,
+                     count, deviance);
+  GPZ_LAUNCH_OK();
+  return 0;
+}
+
+extern "C" int gpz_gene_morans_i_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int32_t* gene_chunk,
+                                             int32_t* workgroups, int64_t* partials_bytes) {
+  if (int rc = gr_check_shape("gpz_gene_morans_i_sparse", N, D, nnz)) return rc;
+  if (int rc = gr_check_k("gpz_gene_morans_i_sparse", N, K)) return rc;
+  const GrPlan p = gr_plan(N, D, true, nullptr);
+  if (gene_chunk) *gene_chunk = GR_THREADS;
+  if (workgroups) *workgroups = p.workgroups;
+  if (partials_bytes) *partials_bytes = int64_t(p.bytes);
+  return 0;
+}
+
+extern "C" int gpz_gene_morans_i_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
+                                        const float* col_val, const int64_t* nbr, int64_t N, int64_t D, int64_t nnz, int32_t K,
+                                        double* I, int32_t* info, void* partials, size_t partials_bytes, void* stream) {
+  GPZ_REQUIRE(row_ptr && nbr && I && info && partials, "gpz_gene_morans_i_sparse: null pointer");
+  if (int rc = gr_check_shape("gpz_gene_morans_i_sparse", N, D, nnz)) return rc;
+  if (int rc = gr_check_k("gpz_gene_morans_i_sparse", N, K)) return rc;
+  GPZ_REQUIRE(nnz == 0 || (row_spot && row_perm && col_val), "gpz_gene_morans_i_sparse: null pointer (non-zeros)");
+  GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "gpz_gene_morans_i_sparse: partials must be 16-byte aligned");
+  const GrPlan p = gr_plan(N, D, true, partials);
+  GPZ_REQUIRE(partials_bytes >= p.bytes, "gpz_gene_morans_i_sparse: partials too small (%zu bytes, %zu needed)", partials_bytes,
+              p.bytes);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const GrRows r{row_ptr, row_spot, row_perm, col_val, N, D, nnz};
+  GPZ_HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t), s));
+  GPZ_HIP_OK(hipMemsetAsync(p.indeg, 0, size_t(N) * sizeof(int32_t), s));
+  hipLaunchKernelGGL(gr_indeg_kernel, dim3(unsigned((N * K + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, N, int(K),
+                     p.indeg, info);
+  GPZ_LAUNCH_OK();
+  hipLaunchKernelGGL(gr_moran_kernel, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, nbr, int(K), p.indeg, p.lines, I);
+  GPZ_LAUNCH_OK();
+  return 0;
+}

@@ -224,6 +224,36 @@ class SparseCounts:
         out.base, out.idx, out.pos, out.shape = self, idx.to(torch.int32), pos, (self.shape[0], B)
         return out
 
+    def select_genes(self, genes):
+        """A whole ``SparseCounts`` of the rows ``genes`` in that order -- ``SparseCounts(y.to_dense()[genes])`` without the
+        dense array: the reference's ``ad[:, :nfeat]`` once ``genes`` is a ranking (``utilities.rank_genes``).  ``genes``: a
+        1-D int32 / int64 tensor, or a sequence, of distinct genes in [0, D); a repeated or out-of-range gene raises
+        IndexError.  Torch ops on this object's device, one pass over the stored entries and the constructor's two sorts;
+        the values are carried over as they are.  Of a view ``y[:, idx]``: TypeError."""
+        if self.base is not self:
+            raise TypeError("SparseCounts: select_genes of a view y[:, idx]; select from the SparseCounts itself")
+        D, N = self.shape
+        dev = self.device
+        g = _gene_index(genes, D, dev, "SparseCounts.select_genes")
+        G = int(g.numel())
+        new_id = torch.full((D,), -1, dtype=torch.int64, device=dev)
+        new_id[g] = torch.arange(G, dtype=torch.int64, device=dev)
+        gene = new_id[self.col_gene.long()]
+        keep = gene >= 0
+        gene, spot, val = gene[keep], self._spots()[keep], self.col_val[keep]
+        order = torch.sort(spot * G + gene, stable=True).indices      # by spot, the new ids ascending inside a spot
+        gene, spot = gene[order], spot[order]
+        out = object.__new__(SparseCounts)
+        out.base, out.idx, out.pos, out.shape = out, None, None, (G, N)
+        out.col_val = val[order].contiguous()
+        out.col_gene = gene.to(torch.int32).contiguous()
+        out.col_ptr = _offsets(spot, N)
+        perm = torch.sort(gene, stable=True).indices
+        out.row_perm = perm.to(torch.int32).contiguous()
+        out.row_spot = spot[perm].to(torch.int32).contiguous()
+        out.row_ptr = _offsets(gene, G)
+        return out
+
     @property
     def T(self):
         """The (N spots, D genes) orientation of the same counts, a ``TransposedCounts``: what ``regularized_nmf`` and
@@ -343,6 +373,14 @@ class SparseExpression:
             raise TypeError("SparseExpression: y[:, idx] of a view; index the SparseExpression itself")
         return SparseExpression(self.values[key], self.offset)
 
+    def select_genes(self, genes):
+        """A whole ``SparseExpression`` of the rows ``genes`` in that order (``SparseCounts.select_genes`` of the values,
+        ``offset[genes]`` carried along).  Of a view: TypeError."""
+        if self.is_view:
+            raise TypeError("SparseExpression: select_genes of a view y[:, idx]; select from the SparseExpression itself")
+        g = _gene_index(genes, self.shape[0], self.device, "SparseExpression.select_genes")
+        return SparseExpression(self.values.select_genes(g), self.offset[g])
+
     def __repr__(self):
         return f"SparseExpression(shape={tuple(self.shape)}, device={self.device}{', view' if self.is_view else ''})"
 
@@ -352,6 +390,30 @@ def _counts_expected(y, who):
     if isinstance(y, SparseExpression):
         raise TypeError(f"{who}: a SparseExpression holds real-valued expression (values - offset), not counts; the count "
                         "likelihoods take a SparseCounts or a dense count array, the Gaussian models (RSF, FA) take this")
+
+
+def _gene_index(genes, D, device, who):
+    """``genes`` as a 1-D int64 tensor on ``device``: distinct values in [0, D), or IndexError."""
+    if isinstance(genes, (SparseCounts, SparseExpression, TransposedCounts, str)):
+        raise TypeError(f"{who}: genes must be a 1-D integer tensor or a sequence of gene indices, got {type(genes).__name__}")
+    g = genes.detach() if isinstance(genes, torch.Tensor) else torch.as_tensor(genes)
+    if g.numel() == 0:
+        raise IndexError(f"{who}: no gene selected")
+    if g.dtype not in (torch.int32, torch.int64):
+        if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+            raise TypeError(f"{who}: genes must hold integer indices, got {g.dtype}")
+        g = g.to(torch.int64)
+    if g.dim() != 1:
+        raise ValueError(f"{who}: genes must be 1-D, got shape {tuple(g.shape)}")
+    g = g.to(device=device, dtype=torch.int64)
+    if g.numel() < 1 or g.numel() > D:
+        raise IndexError(f"{who}: {g.numel()} distinct genes out of {D}")
+    seen = torch.zeros(D, dtype=torch.int64, device=device)
+    inside = (g >= 0) & (g < D)
+    seen.scatter_add_(0, g.clamp(0, D - 1), torch.ones_like(g))
+    if not bool(inside.all() & (seen <= 1).all()):
+        raise IndexError(f"{who}: distinct genes in [0, {D}) needed: an index is out of range or repeated")
+    return g
 
 
 def _segment_sums(v, ptr):

@@ -1497,6 +1497,99 @@ def _gaussian_fa_sparse(mean, scale, W, b, noise_sd, expr, grads):
     return (ll[0], sse, ss, *out) if grads else (ll[0], sse, ss)
 
 
+def gene_rank_plan(N: int, D: int, nnz: int, K: Optional[int] = None) -> dict:
+    """How ``gene_deviance_sparse`` (``K=None``) or ``gene_morans_i_sparse`` (``K`` neighbours) covers a shape
+    (gpz_gene_deviance_sparse_plan / gpz_gene_morans_i_sparse_plan, host-only queries: no device needed): ``gene_chunk``
+    (stored entries of a gene row per sweep of its workgroup), ``workgroups`` (genes in flight), ``partials_bytes``."""
+    lib = _lib.load()
+    gc, wg, nb = C.c_int32(), C.c_int32(), C.c_int64()
+    if K is None:
+        rc = lib.gpz_gene_deviance_sparse_plan(int(N), int(D), int(nnz), C.byref(gc), C.byref(wg), C.byref(nb))
+    else:
+        rc = lib.gpz_gene_morans_i_sparse_plan(int(N), int(D), int(nnz), int(K), C.byref(gc), C.byref(wg), C.byref(nb))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, workgroups=wg.value, partials_bytes=int(nb.value))
+
+
+def _whole_values(values, who: str):
+    """The whole ``SparseCounts``-structured object behind ``values`` (itself, or the values of a ``SparseExpression``)."""
+    from .likelihoods import SparseCounts, SparseExpression
+    if isinstance(values, SparseExpression):
+        values = values.values
+    if not isinstance(values, SparseCounts):
+        raise TypeError(f"{who}: a SparseCounts or a SparseExpression expected, got {type(values).__name__}")
+    if values.base is not values:
+        raise TypeError(f"{who}: a view y[:, idx]; the whole data set is needed")
+    return values
+
+
+def gene_deviance_sparse(counts, size, family: int = 0):
+    """Per-gene (sum, count, deviance), fp64 (D,) each, of a whole ``SparseCounts`` against the constant-rate null
+    (gpz_gene_deviance_sparse): ``size`` (N,) fp64 on the counts' device, positive wherever a spot has a stored count;
+    ``family`` 0 Poisson, 1 binomial (``size`` = the spots' totals).  Nothing here waits for the device."""
+    from .likelihoods import SparseCounts, _counts_expected
+    _counts_expected(counts, "gene_deviance_sparse")
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"gene_deviance_sparse: counts must be a SparseCounts, got {type(counts).__name__}")
+    c = _whole_values(counts, "gene_deviance_sparse")
+    _need_cuda(c.col_val)
+    if family not in (0, 1):
+        raise ValueError(f"gene_deviance_sparse: family {family!r} unknown (0 Poisson, 1 binomial)")
+    D, N = c.shape
+    if not isinstance(size, torch.Tensor) or size.dtype != torch.float64 or tuple(size.shape) != (N,):
+        raise ValueError(f"gene_deviance_sparse: size must be an ({N},) float64 tensor")
+    if size.device != c.device:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {c.device}, size on {size.device}")
+    return _gene_deviance_sparse(c, size.detach().contiguous(), int(family))
+
+
+def _gene_deviance_sparse(c, size, family):
+    lib = _lib.load()
+    dev = c.device
+    D, N = c.shape
+    nb = C.c_int64()
+    if lib.gpz_gene_deviance_sparse_plan(N, D, c.nnz, None, None, C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    out = [torch.empty(D, dtype=torch.float64, device=dev) for _ in range(3)]
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nb.value)
+        rc = lib.gpz_gene_deviance_sparse(_ptr(c.row_ptr), _ptr(c.row_spot), _ptr(c.row_perm), _ptr(c.col_val), _ptr(size), N, D,
+                                          c.nnz, family, *(_ptr(t) for t in out), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_gene_deviance_sparse")
+    return tuple(out)
+
+
+def gene_morans_i_sparse(values, nbr) -> torch.Tensor:
+    """(D,) fp64 Moran's I of every gene of a whole ``SparseCounts`` / ``SparseExpression`` (the offset does not change I)
+    over the neighbour table nbr (N,K) int64, 1 <= K <= 32, with row-normalised weights (gpz_gene_morans_i_sparse): what
+    ``morans_i`` gives for the dense transpose, zeros included, from sums over the stored entries.  NaN for a gene without
+    stored entries and for a constant one.  A table entry outside [0, N) or naming its own row raises ValueError (checked
+    on the device; one synchronisation)."""
+    v = _whole_values(values, "gene_morans_i_sparse")
+    _need_cuda(v.col_val)
+    D, N = v.shape
+    dev = v.device
+    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
+        raise ValueError(f"gene_morans_i_sparse: nbr must be an ({N}, K) integer table")
+    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
+    K = int(nbr.shape[1])
+    lib = _lib.load()
+    nb = C.c_int64()
+    if lib.gpz_gene_morans_i_sparse_plan(N, D, v.nnz, K, None, None, C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    out = torch.empty(D, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nb.value)
+        rc = lib.gpz_gene_morans_i_sparse(_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val), _ptr(nbr), N, D,
+                                          v.nnz, K, _ptr(out), _ptr(info), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_gene_morans_i_sparse")
+    if int(info.item()) != 0:
+        raise ValueError("gene_morans_i_sparse: the neighbour table has an entry outside [0, N) or naming its own row")
+    return out
+
+
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
     """How ``poisson_nsf_sparse`` covers a shape (gpz_poisson_nsf_sparse_plan, a host-only query: no device needed):
     ``gene_chunk`` (non-zeros of a gene row per wave of the gene pass), ``spot_chunk`` (the same for a spot's column; 0:

@@ -8,6 +8,8 @@ caller's tensors live on.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 
@@ -525,12 +527,16 @@ def _transposed_counts(Y, who):
     return isinstance(Y, TransposedCounts)
 
 
+def _spot_totals_tensor(c):
+    """(N,) fp64 totals of the spots of a whole ``SparseCounts``, on its device: segment sums of the stored values."""
+    run = torch.cat([c.col_val.new_zeros(1, dtype=torch.float64), torch.cumsum(c.col_val.to(torch.float64), 0)])
+    return torch.diff(run[c.col_ptr])
+
+
 def _spot_totals(Y, who="train_val_split"):
     """(N,1) row totals of Y (obs x feat): numpy's own sum, or of ``counts.T`` the fp64 segment sums of the stored values."""
     if _transposed_counts(Y, who):
-        c = Y.T
-        run = torch.cat([c.col_val.new_zeros(1, dtype=torch.float64), torch.cumsum(c.col_val.to(torch.float64), 0)])
-        return torch.diff(run[c.col_ptr]).cpu().numpy().reshape(-1, 1)
+        return _spot_totals_tensor(Y.T).cpu().numpy().reshape(-1, 1)
     return Y.sum(axis=1, keepdims=True)
 
 
@@ -578,6 +584,166 @@ def log_normalize(counts, size_factors=None, center=True, offset=None):
     else:
         off = torch.zeros(D, dtype=torch.float64, device=dev)
     return SparseExpression(values, off)
+
+
+def _whole_counts_only(counts, who):
+    """A whole ``SparseCounts``, or TypeError: a ``SparseExpression`` holds no counts (``_counts_expected``), ``counts.T``
+    and views are not the (genes, spots) data set."""
+    from .likelihoods import SparseCounts, TransposedCounts, _counts_expected
+    _counts_expected(counts, who)
+    if isinstance(counts, TransposedCounts):
+        raise TypeError(f"{who}: counts is the .T (obs x feat) of a SparseCounts; pass the SparseCounts itself (genes x spots)")
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"{who}: a whole SparseCounts expected, got {type(counts).__name__} (build one with SparseCounts(y))")
+    if counts.base is not counts:
+        raise TypeError(f"{who}: counts is a view y[:, idx]; the whole SparseCounts is needed")
+    return counts
+
+
+_DEVIANCE_FAMILIES = {"poisson": 0, "binomial": 1}
+
+
+def gene_deviance(counts, family="poisson", size_factors=None):
+    """(D,) fp64 deviance of every gene of a whole ``SparseCounts`` against a constant-rate null, on the counts' device
+    (``ops.gene_deviance_sparse``) -- scry's ``devianceFeatureSelection``, the ranking the nsf paper selects genes with and
+    the reference's ``anndata_to_train_val`` expects to have happened ("features sorted in decreasing importance").  Sums
+    over the stored counts only; a gene without counts scores 0.
+
+    ``family``: "poisson", or "binomial" (scry's default; the size of a spot is then its total count).  ``size_factors``:
+    None = the spots' total counts (required for "binomial"), else an (N,) or (N, 1) array of positive values.  A
+    ``SparseExpression``, ``counts.T`` or a view raises TypeError."""
+    from . import ops
+    c = _whole_counts_only(counts, "gene_deviance")
+    if family not in _DEVIANCE_FAMILIES:
+        raise ValueError(f"gene_deviance: family {family!r} unknown ('poisson', 'binomial')")
+    N = c.shape[1]
+    if size_factors is None:
+        size = _spot_totals_tensor(c)
+    else:
+        if family == "binomial":
+            raise ValueError("gene_deviance: the binomial deviance takes the spots' total counts as sizes (size_factors=None)")
+        import numpy as np
+        sf = size_factors.detach() if isinstance(size_factors, torch.Tensor) else torch.as_tensor(np.asarray(size_factors))
+        if tuple(sf.shape) not in ((N,), (N, 1)):
+            raise ValueError(f"gene_deviance: size_factors of shape {tuple(sf.shape)} for {N} spots ((N,) or (N, 1) expected)")
+        size = sf.reshape(-1).to(device=c.device, dtype=torch.float64)
+        if not bool((size > 0).all() & torch.isfinite(size).all()):
+            raise ValueError("gene_deviance: size_factors must be positive and finite")
+    return ops.gene_deviance_sparse(c, size.contiguous(), _DEVIANCE_FAMILIES[family])[2]
+
+
+class GeneAutocorr(NamedTuple):
+    """``gene_autocorr``: Moran's I per gene and the moments squidpy reports beside it under the normality assumption
+    (they depend on the graph alone), all fp64 tensors: ``I`` (D,), ``expected`` = -1 / (N - 1), ``variance`` (scalars) and
+    ``z`` = (I - expected) / sqrt(variance) (D,)."""
+    I: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+
+
+def _moran_moments(nbr):
+    """(expected, variance) of Moran's I under normality for row-normalised weights 1 / K over the table nbr (N, K) of
+    distinct neighbours without self edges, from integer counts: S0 = N, S1 = (N K + 2 m) / K^2 with m mutual pairs,
+    S2 = sum_i (1 + indeg_i / K)^2; fp64 scalars on the table's device."""
+    N, K = nbr.shape
+    rows = torch.arange(N, dtype=torch.int64, device=nbr.device)[:, None]
+    forward, backward = (rows * N + nbr).reshape(-1), (nbr * N + rows).reshape(-1)
+    m2 = int(torch.isin(forward, backward).sum())                 # directed edges whose reverse is an edge too: 2 m
+    indeg = torch.bincount(nbr.reshape(-1), minlength=N).to(torch.float64)
+    S0 = float(N)
+    S1 = (N * K + m2) / float(K * K)
+    S2 = ((1.0 + indeg / K) ** 2).sum()
+    expected = torch.tensor(-1.0 / (N - 1), dtype=torch.float64, device=nbr.device)
+    variance = (N * N * S1 - N * S2 + 3.0 * S0 * S0) / ((N * N - 1.0) * S0 * S0) - expected * expected
+    return expected, variance
+
+
+def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None):
+    """Moran's I of every gene over the spots' directed ``n_neighs``-nearest-neighbour graph -- squidpy's
+    ``spatial_autocorr(mode="moran")`` with one gene per column, the other standard ranking of spatial data.  ``values``: a
+    whole ``SparseCounts`` or ``SparseExpression`` (the offset does not change I), scored from its stored entries
+    (``ops.gene_morans_i_sparse``; nothing of D x N elements is formed), or a dense (D, N) tensor, scored by
+    ``ops.morans_i``.  The graph is ``ops.spatial_knn(coords, n_neighs)`` (``coords`` (N, d), d <= 4), or ``graph=``, an
+    (N, K) int64 table of distinct neighbours, K <= 32.  Returns a ``GeneAutocorr``.  A gene without stored entries and a
+    constant gene give NaN; I of a nearly constant gene loses digits in proportion to mean^2 / variance."""
+    import numpy as np
+    from . import ops
+    from .likelihoods import SparseCounts, SparseExpression, TransposedCounts
+    who = "gene_autocorr"
+    if isinstance(values, TransposedCounts):
+        raise TypeError(f"{who}: values is the .T (obs x feat) of a SparseCounts; pass the SparseCounts itself (genes x spots)")
+    sparse = isinstance(values, (SparseCounts, SparseExpression))
+    if sparse:
+        ops._whole_values(values, who)
+    elif not isinstance(values, torch.Tensor):
+        raise TypeError(f"{who}: a SparseCounts, a SparseExpression or a dense (D, N) tensor expected, got {type(values).__name__}")
+    elif values.dim() != 2 or not values.is_floating_point():
+        raise ValueError(f"{who}: a dense (D, N) floating-point tensor expected, got {tuple(values.shape)} of {values.dtype}")
+    D, N = values.shape
+    dev = values.device
+    if graph is not None:
+        nbr = graph.detach() if isinstance(graph, torch.Tensor) else torch.as_tensor(np.asarray(graph))
+        if nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
+            raise ValueError(f"{who}: graph must be an ({N}, K) integer table")
+        nbr = nbr.to(device=dev, dtype=torch.int64)
+    else:
+        if coords is None:
+            raise ValueError(f"{who}: coords (N, d) or graph= (N, K) needed")
+        X = coords.detach() if isinstance(coords, torch.Tensor) else torch.as_tensor(np.asarray(coords))
+        if X.dim() != 2 or X.shape[0] != N:
+            raise ValueError(f"{who}: coords {tuple(X.shape)} for {N} spots ((N, d) expected)")
+        if X.dtype not in (torch.float32, torch.float64):
+            X = X.double()
+        X = X.to(dev)
+        if not bool(torch.isfinite(X).all()):
+            raise ValueError(f"{who}: coords hold a non-finite value")
+        nbr = ops.spatial_knn(X, int(n_neighs))
+    K = int(nbr.shape[1])
+    if not 1 <= K <= 32 or K >= N:
+        raise ValueError(f"{who}: {K} neighbours of {N} spots unsupported (1 <= K <= 32, K < N)")
+    if sparse:
+        I = ops.gene_morans_i_sparse(values, nbr)
+    else:
+        V = values.detach()
+        I = ops.morans_i((V if V.dtype in (torch.float32, torch.float64) else V.float()).T.contiguous(), nbr)
+    expected, variance = _moran_moments(nbr)
+    return GeneAutocorr(I, expected, variance, (I - expected) / torch.sqrt(variance))
+
+
+def _rank_order(score, nfeat=None):
+    """Indices of ``score`` in decreasing order, NaN last, equal values in index order (the rules of
+    ``dims_autocorr(sort=True)``), cut to the first ``nfeat``."""
+    nan = torch.isnan(score)
+    order = torch.argsort(torch.where(nan, torch.full_like(score, float("inf")), -score), stable=True)
+    last = nan[order]                                  # NaN after everything else, -inf included, whatever the device's
+    order = torch.cat([order[~last], order[last]])     # sort makes of a NaN key
+    if nfeat is not None:
+        if not 1 <= int(nfeat) <= score.numel():
+            raise ValueError(f"rank_genes: nfeat={nfeat} out of {score.numel()} genes")
+        order = order[:int(nfeat)]
+    return order
+
+
+def rank_genes(counts, by="deviance", *, coords=None, nfeat=None, **kw):
+    """``(order, score)`` of the genes of a whole ``SparseCounts``: ``order`` int64 (D,), or (nfeat,), in decreasing score
+    (NaN last, ties in gene order), ``score`` fp64 aligned with it; ``counts.select_genes(order)`` is then the reference's
+    ``ad[:, :nfeat]`` of a data set sorted by importance.  ``by``: "deviance" (``gene_deviance``, Poisson),
+    "binomial_deviance", or "moran" (``gene_autocorr`` of ``log_normalize(counts, center=False)`` over ``coords``).  Extra
+    keywords go to the scorer."""
+    if by == "deviance":
+        score = gene_deviance(counts, "poisson", **kw)
+    elif by == "binomial_deviance":
+        score = gene_deviance(counts, "binomial", **kw)
+    elif by == "moran":
+        _whole_counts_only(counts, "rank_genes")
+        if coords is None and kw.get("graph") is None:
+            raise ValueError("rank_genes: by='moran' needs coords (or graph=)")
+        score = gene_autocorr(log_normalize(counts, center=False), coords, **kw).I
+    else:
+        raise ValueError(f"rank_genes: by={by!r} unknown ('deviance', 'binomial_deviance', 'moran')")
+    order = _rank_order(score, nfeat)
+    return order, score[order]
 
 
 def train_val_split(X, y, train_frac=0.95, sz="constant"):

@@ -58,7 +58,11 @@
  * `partials`, sized by the plan query;
  * gpz_gaussian_fa_sparse and the host-only gpz_gaussian_fa_sparse_plan -- gpz_gaussian_fa for expression stored as its
  * non-zeros minus a per-gene offset (centred log-normalised counts): the same outputs as exact sums over the non-zeros
- * plus Lt x Lt Gram matrices; its scratch is `partials` again, sized by the plan query's workspace_bytes.
+ * plus Lt x Lt Gram matrices; its scratch is `partials` again, sized by the plan query's workspace_bytes;
+ * gpz_gene_deviance_sparse and gpz_gene_morans_i_sparse, each with its host-only *_plan query -- two per-gene scores of
+ * counts stored as their non-zeros, for ranking and selecting genes ahead of a fit: the Poisson / binomial deviance against a
+ * constant-rate null (scry's devianceFeatureSelection) and Moran's I over the spots' K-neighbour graph (squidpy's
+ * spatial_autocorr, one gene per column); their scratch is `partials`, sized by the plan query's partials_bytes.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -400,6 +404,48 @@ int gpz_gaussian_fa_sparse(const float* mean, const float* scale, const float* W
                            int32_t Lt, double* loglik, double* sse_per_gene, double* ss_per_gene, float* dmean,
                            float* dscale, float* dW, float* db, float* dnoise_sd, void* partials,
                            size_t partials_bytes, void* stream);
+
+/* Per-gene scores of a whole data set stored as its non-zeros (csrc/gene_rank.hip), read in the by-gene order of
+ * gpz_poisson_nsf_sparse below: row_ptr int64 (D + 1), row_spot int32 (nnz), row_perm int32 (nnz), the value of entry k being
+ * col_val[row_perm[k]], fp32 (the same trust in the arrays; an index outside its range is skipped, never dereferenced).  The
+ * reference's anndata_to_train_val takes genes "sorted in decreasing importance (eg with deviance)" as a precondition
+ * (utilities.py:192-230) and computes neither score.  All outputs are fp64 arrays of D values, fully written.
+ *
+ * gpz_gene_deviance_sparse: size (N,) fp64, > 0 wherever a spot has a stored entry; S = sum_n size[n] is formed inside.
+ *   sum[d] = sum_nz y,  count[d] = the stored entries of gene d,  p = sum / S,
+ *   family 0 (Poisson):   deviance[d] = 2 [ sum_nz y log(y / size_n) - sum log(sum / S) ]
+ *   family 1 (binomial):  deviance[d] = 2 [ sum_nz ( y log(y / size_n) + (size_n - y) log1p(-y / size_n) )
+ *                                           - sum (log p - log1p(-p)) - S log1p(-p) ]        (size = the spot's total, y <= size)
+ * A term with y == size_n is y log 1 + 0 = 0 (scry's na.rm=TRUE), as is the null term at p == 1; a gene with no stored
+ * entry has deviance 0.  All logs are fp64.
+ *
+ * gpz_gene_morans_i_sparse: nbr (N,K) int64, 1 <= K <= 32, K < N.  I[d] = gpz_morans_i of column d of the dense transpose
+ * (zeros included, row-normalised weights 1 / K), from the expanded form: S = sum x, Q = sum x^2, xbar = S / N,
+ *   C = sum_{i in nz} x_i sum_{j in nbr(i)} x_j,   A = sum_{i in nz} indeg(i) x_i,
+ *   I = [ C - xbar (K S + A) + N K xbar^2 ] / ( K (Q - N xbar^2) ).
+ * NaN for a gene with no stored entry, for a gene stored at every spot with one single value (found from count, min and
+ * max, not from the cancelled denominator) and wherever the denominator is <= 0.  A nearly constant gene loses digits in
+ * proportion to mean^2 / variance.  The in-degree of the table is counted once per call, in the scratch memory.  Each
+ * entry of nbr is checked on the device as by gpz_morans_i: one outside [0, N) or equal to its row is not read, not counted,
+ * and info[0] (device int32) is set to 1.
+ *
+ * Every accumulation is fp64 in a fixed order with no atomics on values (the in-degree histogram uses integer atomics): two
+ * calls agree bit for bit.  The scratch memory is the explicit argument `partials` as for gpz_gaussian_fa_sparse; it need not
+ * be cleared and may hold anything.  Its size is the plan query's partials_bytes; the plan (host only, any out pointer may
+ * be NULL) also reports gene_chunk (stored entries of a gene row per sweep of its workgroup) and workgroups (genes in
+ * flight; the Moran scratch is workgroups x N x 4 bytes plus N x 4, independent of D beyond that).  Nothing of D x N or nnz
+ * elements is allocated.  N, D, nnz < 2^31; partials 16-byte aligned.  Argument errors return -1 before any launch with the
+ * reason in gpz_last_error. */
+int gpz_gene_deviance_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t* gene_chunk, int32_t* workgroups,
+                                  int64_t* partials_bytes);
+int gpz_gene_deviance_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                             const double* size, int64_t N, int64_t D, int64_t nnz, int32_t family, double* sum,
+                             double* count, double* deviance, void* partials, size_t partials_bytes, void* stream);
+int gpz_gene_morans_i_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int32_t* gene_chunk, int32_t* workgroups,
+                                  int64_t* partials_bytes);
+int gpz_gene_morans_i_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                             const int64_t* nbr, int64_t N, int64_t D, int64_t nnz, int32_t K, double* I, int32_t* info,
+                             void* partials, size_t partials_bytes, void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
