@@ -33,6 +33,7 @@
 // nothing of nnz elements (the chunk list has D + nnz / 512 entries).
 #include "common.h"
 #include "mmops.h"
+#include "sparse_rows.h"
 
 namespace gpz {
 
@@ -87,13 +88,6 @@ __device__ __forceinline__ DvTerm dv_term(float y, float mu) {
   const float l2y = __builtin_amdgcn_logf(pos ? y : 1.f), yl = y * DV_LN2;
   const float t = pos ? dv_ylog_ratio(pos ? y : 1.f, mu) : 0.f;
   return DvTerm{2.f * (t - (y - mu)), yl * l2y};
-}
-
-template <typename T>
-__device__ __forceinline__ T dv_wave_sum(T v) {      // every lane ends with the same sum, formed in one fixed tree
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -409,54 +403,6 @@ __global__ __launch_bounds__(64) void dv_colsum_final_kernel(const double* part,
   out[l] = v;
 }
 
-// One workgroup: cstart[d] = number of chunks of the rows before d, chunk_gene[w] = row of chunk w (-1 past the last one).
-__global__ __launch_bounds__(1024) void dv_chunks_kernel(DevSpArgs a) {
-  __shared__ int sh[1024];
-  const int t = threadIdx.x;
-  for (int64_t d = t; d < a.D; d += 1024)
-    a.cstart[d] = (int32_t)((a.row_ptr[d + 1] - a.row_ptr[d] + DV_CHUNK - 1) / DV_CHUNK);
-  __syncthreads();
-  const int64_t per = (a.D + 1023) / 1024;
-  const int64_t d_lo = t * per < a.D ? t * per : a.D, d_hi = d_lo + per < a.D ? d_lo + per : a.D;
-  int mine = 0;
-  for (int64_t d = d_lo; d < d_hi; ++d) mine += a.cstart[d];
-  sh[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {      // inclusive scan
-    const int v = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int64_t at = sh[t] - mine;
-  const int64_t total = sh[1023];
-  __syncthreads();                          // every count has been read before any cstart[d] becomes an offset
-  for (int64_t d = d_lo; d < d_hi; ++d) {
-    const int nc = a.cstart[d];
-    a.cstart[d] = (int32_t)at;
-    for (int c = 0; c < nc; ++c)
-      if (at + c < a.nchunks) a.chunk_gene[at + c] = (int32_t)d;
-    at += nc;
-  }
-  if (t == 0) a.cstart[a.D] = (int32_t)(total < a.nchunks ? total : a.nchunks);
-  for (int64_t w = total + t; w < a.nchunks; w += 1024) a.chunk_gene[w] = -1;
-}
-
-template <int LT>
-__device__ __forceinline__ void dv_load_w(const float* W, int64_t d, int Lt, float (&w)[LT]) {
-  const float* wr = W + d * Lt;
-  if (Lt == LT) {                           // a multiple of 4: rows start 16-byte aligned
-#pragma unroll
-    for (int l = 0; l < LT; l += 4) {
-      const dvf4 v = *reinterpret_cast<const dvf4*>(wr + l);
-      w[l] = v[0]; w[l + 1] = v[1]; w[l + 2] = v[2]; w[l + 3] = v[3];
-    }
-  } else {
-#pragma unroll
-    for (int l = 0; l < LT; ++l) w[l] = l < Lt ? wr[l] : 0.f;
-  }
-}
-
 // Spot pass.  4 waves per workgroup, wave = batch spot j (global spot n = idx[j]); lanes stride over the column's
 // non-zeros.  per_spot[j] = 2 V[j] sum_l c[l] m[l,j] + sum over the column of 2 (y log(y / mu) - y).  No barrier.
 template <int LT>
@@ -479,14 +425,14 @@ __global__ __launch_bounds__(256) void dv_sp_spot_kernel(DevSpArgs a) {
     const float y = a.col_val[k];
     if (y == 0.f) continue;                 // an explicit zero: 0 log(.) is never formed
     float w[LT];
-    dv_load_w<LT>(a.W, a.col_gene[k], a.Lt, w);
+    load_w<LT>(a.W, a.col_gene[k], a.Lt, w);
     double z = 0.0;
 #pragma unroll
     for (int l = 0; l < LT; ++l) z = __builtin_fma((double)w[l], (double)m[l], z);
     acc += 2.0 * ((double)dv_ylog_ratio(y, (double)vn * z) - (double)y);
   }
-  acc = dv_wave_sum(acc);
-  const double cm = dv_wave_sum(lane < LT ? a.cD[lane] * (double)a.mT[j * LT + lane] : 0.0);
+  acc = wave_sum(acc);
+  const double cm = wave_sum(lane < LT ? a.cD[lane] * (double)a.mT[j * LT + lane] : 0.0);
   if (lane == 0) a.per_spot[j] = 2.0 * (double)vn * cm + acc;
 }
 
@@ -526,7 +472,7 @@ __global__ __launch_bounds__(256) void dv_sp_gene_kernel(DevSpArgs a) {
   __syncthreads();                 // every wave, with or without a chunk, arrives here exactly once
   if (g < 0) return;
   float w[LT];
-  dv_load_w<LT>(a.W, g, a.Lt, w);
+  load_w<LT>(a.W, g, a.Lt, w);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};           // at most 8 entries per lane
   double ys = 0.0;                               // sum y, exact: it meets sum y log(y / mu) below
   for (int i = lane; i < cnt; i += 64) {
@@ -549,7 +495,7 @@ __global__ __launch_bounds__(256) void dv_sp_gene_kernel(DevSpArgs a) {
   // part[0] = sum 2 (y log(y / mu) - y): the two sums meet in fp64 (y log(y / mu) is small beside y next to y = mu)
   double t[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) t[k] = dv_wave_sum(k == 1 ? ys : (double)acc[k]);
+  for (int k = 0; k < 4; ++k) t[k] = wave_sum(k == 1 ? ys : (double)acc[k]);
   t[0] = 2.0 * (t[0] - t[1]);
   if (lane == 0) {
 #pragma unroll
@@ -752,7 +698,7 @@ extern "C" int gpz_poisson_deviance_sparse(const float* mean, const float* scale
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(dv_colsum_final_kernel, dim3(1), dim3(64), 0, s, a.apart, a.nbS, a.LT, a.aD);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(dv_chunks_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(chunks_kernel, dim3(1), dim3(1024), 0, s, a.row_ptr, a.D, a.nchunks, DV_CHUNK, false, a.cstart, a.chunk_gene);
   GPZ_LAUNCH_OK();
   int rc;
   switch (a.LT) {

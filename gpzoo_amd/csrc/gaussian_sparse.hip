@@ -27,13 +27,14 @@
 //   gs_s2_kernel      S2, one workgroup per factor
 //   gs_gram_kernel    slabs of 256 rows: partial G and M1 over the spots, partial H and u over the genes (gradient calls only);
 //                     gs_reduce_kernel adds the slabs in ascending order
-//   gs_chunks_kernel  the gene pass's work list: row d is cut into ceil(len_d / 512) chunks of consecutive entries
+//   chunks_kernel     the gene pass's work list: row d is cut into ceil(len_d / 512) chunks of consecutive entries
 //   gs_spot_kernel    one wave per batch spot, lanes stride over the column's entries: dmean, dscale (gradient calls only)
 //   gs_gene_kernel    one wave per (gene, chunk): partials of sum z m, sum z, sum z^2 and sum z (z - 2 p)
 //   gs_finish_kernel  one wave per gene: chunk partials in chunk order, the quadratic forms; dW, db, dsd, sse, ss, loglik per gene
 //   gs_total_kernel   the scalar
 #include "common.h"
 #include "mmops.h"
+#include "sparse_rows.h"
 
 namespace gpz {
 namespace gsp {
@@ -69,13 +70,6 @@ static int gs_instance(int Lt) {
   const int sizes[] = {4, 8, 12, 16, 20, 24, 32, 40, 48, 64};
   for (int s : sizes) if (Lt <= s) return s;
   return 0;
-}
-
-template <typename T>
-__device__ __forceinline__ T gs_wave_sum(T v) {     // every lane ends with the same sum, formed in one fixed tree
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void gs_mt_kernel(GsArgs a) {
@@ -192,38 +186,6 @@ __global__ __launch_bounds__(256) void gs_reduce_kernel(const double* part, int 
   out[e] = v;
 }
 
-// One workgroup: cstart[d] = number of chunks of the rows before d, chunk_gene[w] = row of chunk w (-1 past the last one).
-__global__ __launch_bounds__(1024) void gs_chunks_kernel(GsArgs a) {
-  __shared__ int sh[1024];
-  const int t = threadIdx.x;
-  for (int64_t d = t; d < a.D; d += 1024)
-    a.cstart[d] = (int32_t)((a.row_ptr[d + 1] - a.row_ptr[d] + GS_CHUNK - 1) / GS_CHUNK);
-  __syncthreads();
-  const int64_t per = (a.D + 1023) / 1024;
-  const int64_t d_lo = t * per < a.D ? t * per : a.D, d_hi = d_lo + per < a.D ? d_lo + per : a.D;
-  int mine = 0;
-  for (int64_t d = d_lo; d < d_hi; ++d) mine += a.cstart[d];
-  sh[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {      // inclusive scan
-    const int v = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int64_t at = sh[t] - mine;
-  const int64_t total = sh[1023];
-  for (int64_t d = d_lo; d < d_hi; ++d) {
-    const int nc = a.cstart[d];
-    a.cstart[d] = (int32_t)(at < a.nchunks ? at : a.nchunks);
-    for (int c = 0; c < nc; ++c)
-      if (at + c < a.nchunks) a.chunk_gene[at + c] = (int32_t)d;
-    at += nc;
-  }
-  if (t == 0) a.cstart[a.D] = (int32_t)(total < a.nchunks ? total : a.nchunks);
-  for (int64_t w = total + t; w < a.nchunks; w += 1024) a.chunk_gene[w] = -1;
-}
-
 // Spot pass.  4 waves per workgroup, wave = batch spot j (global spot n = idx[j]).  Each lane takes every 64th entry of the
 // column, reads its gene's pre-scaled row iv W[d,:] and adds z iv W[d,l] to its fp64 partial of factor l.
 template <int LT>
@@ -253,7 +215,7 @@ __global__ __launch_bounds__(256) void gs_spot_kernel(GsArgs a) {
   double mine = 0.0;
 #pragma unroll
   for (int l = 0; l < LT; ++l) {
-    const double t = gs_wave_sum(acc[l]);
+    const double t = wave_sum(acc[l]);
     if (lane == l) mine = t;
   }
   const int ll = lane < LT ? lane : 0;
@@ -343,14 +305,14 @@ __global__ __launch_bounds__(256) void gs_gene_kernel(GsArgs a) {
     double mine = 0.0;
 #pragma unroll
     for (int l = 0; l < LT; ++l) {
-      const double t = gs_wave_sum(acc[l]);
+      const double t = wave_sum(acc[l]);
       if (lane == l) mine = t;
     }
     if (lane < LT) a.partv[wi * LT + lane] = mine;
   }
-  sz = gs_wave_sum(sz);
-  szz = gs_wave_sum(szz);
-  sq = gs_wave_sum(sq);
+  sz = wave_sum(sz);
+  szz = wave_sum(szz);
+  sq = wave_sum(sq);
   if (lane == 0) {
     a.parts[wi * 4] = sz;
     a.parts[wi * 4 + 1] = szz;
@@ -379,9 +341,9 @@ __global__ __launch_bounds__(256) void gs_finish_kernel(GsArgs a) {
     double Gw = 0.0;
     for (int c = 0; c < LT; ++c) Gw = fma(sG[c * LT + ll], (double)__shfl(wf, c), Gw);
     if (lane >= LT) Gw = 0.0;
-    const double wM1 = gs_wave_sum(w * sM1[lane]);
-    const double wGw = gs_wave_sum(w * Gw);
-    const double wS2w = gs_wave_sum(w * w * sS2[lane]);
+    const double wM1 = wave_sum(w * sM1[lane]);
+    const double wGw = wave_sum(w * Gw);
+    const double wS2w = wave_sum(w * w * sS2[lane]);
     double zm = 0.0, sz = 0.0, szz = 0.0, sq = 0.0;
     const int c0 = a.cstart[d], c1 = a.cstart[d + 1];
     for (int c = c0; c < c1; ++c) {
@@ -529,7 +491,7 @@ extern "C" int gpz_gaussian_fa_sparse(const float* mean, const float* scale, con
     hipLaunchKernelGGL(gs_reduce_kernel, dim3((unsigned)((GW + 255) / 256)), dim3(256), 0, s, a.gpart, a.nbG, GW, a.gsum);
     GPZ_LAUNCH_OK();
   }
-  hipLaunchKernelGGL(gs_chunks_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(chunks_kernel, dim3(1), dim3(1024), 0, s, a.row_ptr, a.D, a.nchunks, GS_CHUNK, true, a.cstart, a.chunk_gene);
   GPZ_LAUNCH_OK();
   int rc;
   switch (a.LT) {

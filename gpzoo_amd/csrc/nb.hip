@@ -24,19 +24,20 @@
 //   nb_const_kernel   the bracketed terms above, which depend on y and theta only: one workgroup per gene, fp64
 //   nb_gene_kernel    pass B: the transposed tiles (spots as rows) -> dW = G expF^T and dtheta's sample-dependent sum
 //   nb_finish_kernel  sums the slabs into dmean, dscale, dV, dW, dtheta and the scalar
-// The layout of both passes -- which lane holds which element, how one product's accumulators are the next one's operand
-// without a transpose through LDS, the double-buffered operands -- is poisson.hip's and is described there; this file
-// repeats the kernels with theta as a second per-gene operand because the Poisson object code must not change.
+// Both passes are the templates of nb_passes.h, which nb_sparse.hip's zero part shares; this file supplies the policy with
+// the counts as an operand (NbDense).  Their layout -- which lane holds which element, how one product's accumulators are
+// the next one's operand without a transpose through LDS, the double-buffered operands -- is poisson.hip's and is described
+// there.  poisson.hip does not share them: its pass A runs two waves per SIMD at the 256-VGPR limit, and any textual change
+// re-rolls its register allocation ("Why the Poisson passes keep their own text").
 #include "common.h"
 #include "mmops.h"
+#include "nb_passes.h"
 
 namespace gpz {
 namespace nb {
 
 constexpr int NMAXL = 64;   // factors (PMAXL of poisson.hip)
 constexpr int NMAXE = 32;   // samples per call (PMAXE)
-constexpr int NEG = 4;      // samples pass B holds in LDS at a time (PEG)
-constexpr float LN2 = 0.69314718055994530942f;
 
 struct NbArgs {
   const float* mean; const float* scale; const float* eps;   // (Lt,N), (Lt,N), (E,Lt,N)
@@ -60,219 +61,97 @@ __global__ void nb_prep_kernel(NbArgs a) {
   a.expF[i] = __expf(a.mean[ln] + a.scale[ln] * a.eps[i]);
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x2 pkfma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-
 // The element-wise part of both passes.  In: the rate factor zz = Z, the count, V of the spot, theta and 1 / theta of the
 // gene.  With mu = V Z, x = mu / theta, u = 1 + x and t = (y + theta) / (mu + theta) = (y / theta + 1) / u:
 //   lu = log2(u), c = (x - (u - 1)) / u       log1p(x) = ln2 lu + c   (the compensation, see the head of the file)
 //   w  = y - mu t                             = theta (y - mu) / (mu + theta): dV = sum w / V, dtheta's term is -w / theta
 //   g  = w / Z                                = y / Z - V t = E G
 // Four transcendentals per element in pass A (two reciprocals, log2 u and log2 x for the value), three in pass B.
+// u and c's numerator are each formed in one rounding, fma(mu, 1 / theta, 1) and fma(mu, 1 / theta, -(u - 1)), everywhere but
+// in pass A's interior tiles (FUSED = false), which use the rounded x in both.  The forms are written out because the
+// results are held bit for bit and the compiler's own choice between them changes with the text around the element.
 struct NbElem { float x, lu, c, w, g; };
+template <bool FUSED>
 __device__ __forceinline__ NbElem nb_elem(float zz, float y1, float v, float ith) {
   NbElem o;
   const float mu = v * zz;
   o.x = mu * ith;
-  const float u = 1.f + o.x;
+  float u, num;
+  if constexpr (FUSED) {
+    u = __builtin_fmaf(mu, ith, 1.f);
+    num = __builtin_fmaf(mu, ith, -(u - 1.f));
+  } else {
+    asm("" : "+v"(o.x));                        // the rounded product: keeps what follows from being fused with it
+    u = 1.f + o.x;
+    num = o.x - (u - 1.f);
+  }
   const float ru = __builtin_amdgcn_rcpf(u);
   o.lu = __builtin_amdgcn_logf(u);
-  o.c = (o.x - (u - 1.f)) * ru;
+  o.c = num * ru;
   const float t = __builtin_fmaf(y1, ith, 1.f) * ru;
   o.w = __builtin_fmaf(-mu, t, y1);
   o.g = o.w * __builtin_amdgcn_rcpf(zz);
   return o;
 }
 
-// Pass A  grid (E * ceil(N/64), S), 4 waves; see spot_mfma_kernel of poisson.hip.
+// What nb_passes.h asks of a step: the counts are an operand.
+struct NbDense {
+  static constexpr bool HAS_Y = true;
+  static __device__ __forceinline__ int64_t spots(const NbArgs& a) { return a.N; }
+  static __device__ __forceinline__ const float* y(const NbArgs& a) { return a.y; }
+  // pass A, value: ln2 (y log2 x - (y + theta) log2 u) - (y + theta) c, the two parts summed apart and combined per group
+  struct SumsA { float lla = 0.f, llb = 0.f; };
+  template <bool MASKED>
+  static __device__ __forceinline__ float elem_a(SumsA& s, int, float z, float y1, float v, float th, float ith, float& dv, bool ok) {
+    const float yt = y1 + th;
+    if constexpr (!MASKED) {
+      const NbElem o = nb_elem<false>(z, y1, v, ith);
+      s.lla = __builtin_fmaf(y1, __builtin_amdgcn_logf(o.x), s.lla);
+      s.lla = __builtin_fmaf(-yt, o.lu, s.lla);
+      s.llb = __builtin_fmaf(yt, o.c, s.llb);
+      dv += o.w;
+      return o.g;
+    } else {
+      const float zz = ok ? z : 1.f;
+      const NbElem o = nb_elem<true>(zz, y1, v, ith);
+      s.lla += ok ? __builtin_fmaf(y1, __builtin_amdgcn_logf(o.x), -yt * o.lu) : 0.f;
+      s.llb += ok ? yt * o.c : 0.f;
+      dv += ok ? o.w : 0.f;
+      return ok ? o.g : 0.f;
+    }
+  }
+  static __device__ __forceinline__ double fold_a(const SumsA& s, const float (&)[4]) { return (double)__builtin_fmaf(LN2, s.lla, -s.llb); }
+  // dv holds sum_d w = V sum_d (y / V - Z t)
+  static __device__ __forceinline__ float close_dv(float dv, float v, float inv_e) { return dv * __builtin_amdgcn_rcpf(v) * inv_e; }
+  // pass B, dtheta's term: -log1p(x) - w / theta = -(ln2 lu + c) - w / theta, the three sums apart and combined per tile
+  struct SumsB { float tpa = 0.f, tpb = 0.f, tpc = 0.f; };
+  template <bool MASKED>
+  static __device__ __forceinline__ float elem_b(SumsB& s, float z, float y1, float v, float ith, bool ok) {
+    if constexpr (!MASKED) {
+      const NbElem o = nb_elem<true>(z, y1, v, ith);
+      s.tpa += o.lu;
+      s.tpb += o.c;
+      s.tpc += o.w;
+      return o.g;
+    } else {
+      const float zz = ok ? z : 1.f, v1 = ok ? v : 1.f;
+      const NbElem o = nb_elem<true>(zz, y1, v1, ith);
+      s.tpa += ok ? o.lu : 0.f;
+      s.tpb += ok ? o.c : 0.f;
+      s.tpc += ok ? o.w : 0.f;
+      return ok ? o.g : 0.f;
+    }
+  }
+  static __device__ __forceinline__ double fold_b(const SumsB& s, float ith) { return -(double)(__builtin_fmaf(LN2, s.tpa, s.tpb) + ith * s.tpc); }
+};
+
+// Pass A  grid (E * ceil(N/64), S), 4 waves: nb_pass_a of nb_passes.h.
 #ifndef GPZ_NB_SPOT_WAVES
 #define GPZ_NB_SPOT_WAVES 1     // waves per SIMD the register allocation of pass A is made for
 #endif
 template <int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPZ_NB_SPOT_WAVES, GPZ_NB_SPOT_WAVES))) void nb_spot_kernel(NbArgs a, int GS) {
-  constexpr int LT16 = (KS + 3) / 4;
-  __shared__ double sh[8];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, q = lane >> 4;
-  const int e = blockIdx.x % a.E, gs = wave;
-  const int s = blockIdx.y;
-  const int64_t n0 = (int64_t)(blockIdx.x / a.E) * 64;
-  const int64_t per = (int64_t)a.Lt * a.N;
-  const int64_t dper = (a.D + a.S - 1) / a.S;
-  const int64_t d_lo = s * dper, d_hi = (d_lo + dper < a.D) ? d_lo + dper : a.D;
-  const float inv_e = 1.f / (float)a.E;
-  const bool vec = (a.N & 3) == 0;
-  const bool tile_full = n0 + 64 <= a.N;
-  float vn[4], invv[4], bz[KS][4];
-  bool nok[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int64_t n = n0 + 4 * r + c;
-    nok[c] = n < a.N;
-    vn[c] = nok[c] ? a.V[n] : 1.f;
-    invv[c] = __builtin_amdgcn_rcpf(vn[c]);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int l = 4 * ks + q;
-      bz[ks][c] = (nok[c] && l < a.Lt) ? a.expF[e * per + (int64_t)l * a.N + n] : 0.f;
-    }
-  }
-  f32x4 dacc[LT16][4];
-#pragma unroll
-  for (int lt = 0; lt < LT16; ++lt)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dacc[lt][c] = f32x4{0, 0, 0, 0};
-  float dv[4] = {0.f, 0.f, 0.f, 0.f};
-  double ll = 0.0;
-  // one 16-gene group's operands; th / ith are theta and 1 / theta of the genes 4q + g on this lane's register axis
-  // (1 for a gene that does not exist: its elements are masked, but the arithmetic must stay finite)
-  struct Group { float wa[KS]; f32x4 yv[4]; float wt[4][LT16]; float th[4], ith[4]; };
-  auto load_group = [&](int64_t d0, Group& G) __attribute__((always_inline)) {
-    if (d0 + 16 <= d_hi && tile_full && vec) {
-      const float* wr = a.W + (d0 + r) * a.Lt;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const int l = 4 * ks + q;
-        const float v = wr[l < a.Lt ? l : a.Lt - 1];
-        G.wa[ks] = l < a.Lt ? v : 0.f;
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int64_t dg = d0 + 4 * q + g;
-        G.yv[g] = *reinterpret_cast<const f32x4*>(a.y + dg * a.N + n0 + 4 * r);
-        G.th[g] = a.theta[dg];
-        G.ith[g] = a.ith[dg];
-        const float* wg = a.W + dg * a.Lt;
-#pragma unroll
-        for (int lt = 0; lt < LT16; ++lt) {
-          const int l = 16 * lt + r;
-          const float v = wg[l < a.Lt ? l : a.Lt - 1];
-          G.wt[g][lt] = l < a.Lt ? v : 0.f;
-        }
-      }
-      return;
-    }
-    const int64_t d = d0 + r;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int l = 4 * ks + q;
-      G.wa[ks] = (d < d_hi && l < a.Lt) ? a.W[d * a.Lt + l] : 0.f;
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int64_t dg = d0 + 4 * q + g;
-      G.yv[g] = f32x4{0, 0, 0, 0};
-      G.th[g] = 1.f;
-      G.ith[g] = 1.f;
-      if (dg < d_hi) {
-        G.th[g] = a.theta[dg];
-        G.ith[g] = a.ith[dg];
-        const float* yp = a.y + dg * a.N + n0 + 4 * r;
-        if (vec && nok[3]) G.yv[g] = *reinterpret_cast<const f32x4*>(yp);
-        else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) if (nok[c]) G.yv[g][c] = yp[c];
-        }
-      }
-#pragma unroll
-      for (int lt = 0; lt < LT16; ++lt) {
-        const int l = 16 * lt + r;
-        G.wt[g][lt] = (dg < d_hi && l < a.Lt) ? a.W[dg * a.Lt + l] : 0.f;
-      }
-    }
-  };
-  Group cur, nxt;
-  const int64_t dstep = 16 * GS;
-  int64_t d0 = d_lo + 16 * gs;
-  if (d0 < d_hi) load_group(d0, cur);
-  for (; d0 < d_hi; d0 += dstep) {
-    if (d0 + dstep < d_hi) load_group(d0 + dstep, nxt);
-    f32x4 z[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      z[c] = f32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) z[c] = mfma4(cur.wa[ks], bz[ks][c], z[c]);
-    }
-    // element-wise: the sample-dependent terms of the log-density, dV, and G in place of Z (1 / E applied at the end)
-    // value: ln2 (y log2 x - (y + theta) log2 u) - (y + theta) c, the two parts summed apart and combined per group
-    float lla = 0.f, llb = 0.f;
-    if (d0 + 16 <= d_hi && tile_full) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float y1 = cur.yv[g][c], yt = y1 + cur.th[g];
-          const NbElem o = nb_elem(z[c][g], y1, vn[c], cur.ith[g]);
-          lla = __builtin_fmaf(y1, __builtin_amdgcn_logf(o.x), lla);
-          lla = __builtin_fmaf(-yt, o.lu, lla);
-          llb = __builtin_fmaf(yt, o.c, llb);
-          dv[c] += o.w;
-          z[c][g] = o.g;
-        }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const bool dok = d0 + 4 * q + g < d_hi;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const bool ok = dok && nok[c];
-          const float zz = ok ? z[c][g] : 1.f, y1 = cur.yv[g][c], yt = y1 + cur.th[g];
-          const NbElem o = nb_elem(zz, y1, vn[c], cur.ith[g]);
-          lla += ok ? __builtin_fmaf(y1, __builtin_amdgcn_logf(o.x), -yt * o.lu) : 0.f;
-          llb += ok ? yt * o.c : 0.f;
-          dv[c] += ok ? o.w : 0.f;
-          z[c][g] = ok ? o.g : 0.f;
-        }
-      }
-    }
-    ll += (double)__builtin_fmaf(LN2, lla, -llb);
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int lt = 0; lt < LT16; ++lt)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) dacc[lt][c] = mfma4(cur.wt[g][lt], z[c][g], dacc[lt][c]);
-    cur = nxt;
-  }
-  const int64_t slab = (int64_t)s * GS + gs;
-#pragma unroll
-  for (int lt = 0; lt < LT16; ++lt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int l = 16 * lt + 4 * q + g;
-      if (l < a.Lt) {
-        float* dp = a.dexp_slab + ((slab * a.E + e) * a.Lt + l) * a.N + n0 + 4 * r;
-        if (vec && nok[3])
-          *reinterpret_cast<f32x4*>(dp) = f32x4{dacc[lt][0][g] * inv_e, dacc[lt][1][g] * inv_e, dacc[lt][2][g] * inv_e, dacc[lt][3][g] * inv_e};
-        else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) if (nok[c]) dp[c] = dacc[lt][c][g] * inv_e;
-        }
-      }
-    }
-  const int nw = a.E * GS;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    float v = dv[c] * invv[c] * inv_e;           // dv holds sum_d w = V sum_d (y / V - Z t)
-    v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-    if (q == 0 && nok[c]) a.dV_slab[((int64_t)s * nw + e * GS + gs) * a.N + n0 + 4 * r + c] = v;
-  }
-  const double t = block_sum(ll * (double)inv_e, sh);
-  if (threadIdx.x == 0) a.ll_slab[(int64_t)s * gridDim.x + blockIdx.x] = t;
-}
-
-// psi(x), x > 0, fp64: the argument shifted above 6 by psi(x) = psi(x + 1) - 1 / x, then the asymptotic series (its first
-// omitted term is below 1e-12 there)
-__device__ __forceinline__ double digamma_pos(double x) {
-  double r = 0.0;
-  while (x < 6.0) { r -= 1.0 / x; x += 1.0; }
-  const double i = 1.0 / x, i2 = i * i;
-  const double ser = i2 * (1.0 / 12 - i2 * (1.0 / 120 - i2 * (1.0 / 252 - i2 * (1.0 / 240 - i2 * (1.0 / 132 - i2 * (691.0 / 32760 - i2 / 12))))));
-  return r + log(x) - 0.5 * i - ser;
+  nb_pass_a<KS, NbDense>(a, GS);
 }
 
 // The terms that depend on y and theta only: per gene, sums over its spots of lgamma(y + theta) - lgamma(theta) (-> cl),
@@ -330,7 +209,7 @@ __global__ __launch_bounds__(256) void nb_const_kernel(NbArgs a) {
       const unsigned long long m = __ballot(aside);
       if (aside) lst[cnt + __popcll(m & ((1ull << lane) - 1ull))] = y1;
       cnt += __popcll(m);
-      if (a.with_lgamma && y1 != 0.f) lg += (double)((whole && yi < 256) ? lfact[yi] : lgammaf(y1 + 1.f));
+      if (a.with_lgamma && y1 != 0.f) lg += (double)lgamma1p_term(lfact, y1, yi, whole);
       }
     }
     __syncthreads();
@@ -354,180 +233,10 @@ __global__ __launch_bounds__(256) void nb_const_kernel(NbArgs a) {
   if (threadIdx.x == 0) { a.cl[d] = tcl; a.cpsi[d] = tcp; a.lg[d] = tlg; }
 }
 
-// Pass B  grid (ceil(D/64), SN), 4 waves; see gene_mfma_kernel of poisson.hip.  This lane's gene is column r of the
-// transposed tile, so theta is one register, and dtheta's sample-dependent sum reduces over the same axes as dW: one more
-// output column per gene.
+// Pass B  grid (ceil(D/64), SN), 4 waves: nb_pass_b of nb_passes.h.
 template <int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void nb_gene_kernel(NbArgs a, int SN) {
-  constexpr bool TAIL = (KS % 4) == 1;
-  constexpr int LTM = TAIL ? KS / 4 : (KS + 3) / 4, LTA = LTM > 0 ? LTM : 1, L0 = 16 * LTM;
-  constexpr int LT16 = (KS + 3) / 4, LP = 16 * LT16, PF = 68;
-  extern __shared__ float smem_nb[];
-  const int EG = a.E < NEG ? a.E : NEG, NG = (a.E + EG - 1) / EG;
-  const int FB = EG * LP * PF;
-  float* sF = smem_nb;                          // [2][EG][LP][PF]
-  float* sV = smem_nb + 2 * FB;                 // [2][64]
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, q = lane >> 4;
-  const int64_t d0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
-  const int64_t dcol = d0 + r;
-  const bool dok = dcol < a.D;
-  const bool d_full = d0 + 16 <= a.D;
-  const int64_t per = (int64_t)a.Lt * a.N;
-  const int64_t ntiles = (a.N + 63) / 64, tper = (ntiles + SN - 1) / SN;
-  const int64_t t_lo = blockIdx.y * tper, t_hi = (t_lo + tper < ntiles) ? t_lo + tper : ntiles;
-  const float inv_e = 1.f / (float)a.E;
-  const bool vec = (a.N & 3) == 0;
-  const float ith = dok ? a.ith[dcol] : 1.f;
-  float wb[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const int l = 4 * ks + q;
-    wb[ks] = (dok && l < a.Lt) ? a.W[dcol * a.Lt + l] : 0.f;
-  }
-  f32x4 dwt[LTA];
-#pragma unroll
-  for (int lt = 0; lt < LTA; ++lt) dwt[lt] = f32x4{0, 0, 0, 0};
-  f32x2 tw[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) tw[t] = f32x2{0.f, 0.f};
-  double dth = 0.0;                             // sum over this lane's spots and all samples of -log1p(x) - E G Z / theta
-  const int arow = 16 * (r >> 2) + (r & 3);
-  typedef __attribute__((address_space(3))) void lds_void;
-  for (int i = threadIdx.x; i < 2 * FB; i += 256) sF[i] = 0.f;
-  __syncthreads();
-#if defined(__HIP_DEVICE_COMPILE__)
-  const __amdgpu_buffer_rsrc_t f_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.expF), 0, (int)((int64_t)a.E * per * sizeof(float)), 0x00020000);
-  const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.V), 0, (int)(a.N * sizeof(float)), 0x00020000);
-#endif
-  auto stage = [&](int64_t tt, int gi, int buf) __attribute__((always_inline)) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const int64_t n0 = tt * 64;
-    const int e0 = gi * EG, ne = (a.E - e0 < EG) ? a.E - e0 : EG;
-    for (int el = 0; el < ne; ++el)
-      for (int l = wave; l < a.Lt; l += 4)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(f_rsrc, (lds_void*)(sF + buf * FB + (el * LP + l) * PF), 4, lane * 4,
-                                                 (int)(((e0 + el) * per + (int64_t)l * a.N + n0) * 4), 0, 0);
-    if (wave == 0)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(v_rsrc, (lds_void*)(sV + buf * 64), 4, lane * 4, (int)(n0 * 4), 0, 0);
-#endif
-  };
-  auto load_y = [&](int64_t tt, f32x4 (&yv)[4]) __attribute__((always_inline)) {
-    const int64_t n0 = tt * 64;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int64_t n = n0 + 16 * q + 4 * c;
-      yv[c] = f32x4{0, 0, 0, 0};
-      if (dok) {
-        const float* yp = a.y + dcol * a.N + n;
-        if (vec && n + 3 < a.N) yv[c] = *reinterpret_cast<const f32x4*>(yp);
-        else {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) if (n + g < a.N) yv[c][g] = yp[g];
-        }
-      }
-    }
-  };
-  f32x4 yv[4], yn[4];
-  if (t_lo < t_hi) { stage(t_lo, 0, 0); load_y(t_lo, yv); }
-  int buf = 0;
-  for (int64_t tt = t_lo; tt < t_hi; ++tt) {
-    const int64_t n0 = tt * 64;
-    for (int gi = 0; gi < NG; ++gi, buf ^= 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (gi + 1 < NG) stage(tt, gi + 1, buf ^ 1);
-      else if (tt + 1 < t_hi) { stage(tt + 1, 0, buf ^ 1); load_y(tt + 1, yn); }
-      f32x4 vv[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) vv[c] = *reinterpret_cast<const f32x4*>(sV + buf * 64 + 16 * q + 4 * c);
-      const int ne = (a.E - gi * EG < EG) ? a.E - gi * EG : EG;
-      for (int e = 0; e < ne; ++e) {
-        const float* fe = sF + buf * FB + e * LP * PF;
-        f32x4 z[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          z[c] = f32x4{0, 0, 0, 0};
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) z[c] = mfma4(fe[(4 * ks + q) * PF + arow + 4 * c], wb[ks], z[c]);
-        }
-        // G^T in place of Z^T (1 / E applied at the end) and dtheta's term; a spot past N reads V = 0 or a finite
-        // neighbour through the buffer descriptor, so the masked form replaces V as well as Z
-        // (dtheta's term is -log1p(x) - w / theta = -(ln2 lu + c) - w / theta: the three sums apart, combined per tile)
-        float tpa = 0.f, tpb = 0.f, tpc = 0.f;
-        if (d_full && n0 + 64 <= a.N) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const NbElem o = nb_elem(z[c][g], yv[c][g], vv[c][g], ith);
-              tpa += o.lu;
-              tpb += o.c;
-              tpc += o.w;
-              z[c][g] = o.g;
-            }
-        } else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const bool ok = dok && n0 + 16 * q + 4 * c + g < a.N;
-              const float zz = ok ? z[c][g] : 1.f, v1 = ok ? vv[c][g] : 1.f;
-              const NbElem o = nb_elem(zz, yv[c][g], v1, ith);
-              tpa += ok ? o.lu : 0.f;
-              tpb += ok ? o.c : 0.f;
-              tpc += ok ? o.w : 0.f;
-              z[c][g] = ok ? o.g : 0.f;
-            }
-        }
-        dth -= (double)(__builtin_fmaf(LN2, tpa, tpb) + ith * tpc);   // fp32 sums of 16 terms, fp64 across tiles and samples
-#pragma unroll
-        for (int lt = 0; lt < LTM; ++lt)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(fe + (16 * lt + r) * PF + 16 * q + 4 * c);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) dwt[lt] = mfma4(fa[g], z[c][g], dwt[lt]);
-          }
-        if constexpr (TAIL) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const f32x4 fv = *reinterpret_cast<const f32x4*>(fe + (L0 + t) * PF + 16 * q + 4 * c);
-              tw[t] = pkfma(f32x2{z[c][0], z[c][1]}, f32x2{fv[0], fv[1]}, tw[t]);
-              tw[t] = pkfma(f32x2{z[c][2], z[c][3]}, f32x2{fv[2], fv[3]}, tw[t]);
-            }
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) yv[c] = yn[c];
-  }
-  if constexpr (TAIL) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float v = (tw[t][0] + tw[t][1]) * inv_e;
-      v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-      if (q == 0 && dok && L0 + t < a.Lt) a.dW_slab[((int64_t)blockIdx.y * a.D + dcol) * a.Lt + L0 + t] = v;
-    }
-  }
-  {
-    double v = dth * (double)inv_e;
-    v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-    if (q == 0 && dok) a.dth_slab[(int64_t)blockIdx.y * a.D + dcol] = v;
-  }
-  if (dok) {
-#pragma unroll
-    for (int lt = 0; lt < LTM; ++lt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int l = 16 * lt + 4 * q + g;
-        if (l < a.Lt) a.dW_slab[((int64_t)blockIdx.y * a.D + dcol) * a.Lt + l] = dwt[lt][g] * inv_e;
-      }
-  }
+  nb_pass_b<KS, NbDense>(a, SN);
 }
 
 // dmean, dscale (Lt,N), dV (N), dW (D,Lt) and dtheta (D) from the slabs (fixed summation order); log-lik total
@@ -591,20 +300,8 @@ struct NbPlan { int S, GS, SN; int64_t nblk; size_t bytes; float *expF, *ith, *d
 
 static NbPlan nb_plan(int64_t N, int64_t D, int Lt, int E, void* ws) {
   NbPlan pl;
-  pl.nblk = (N + 63) / 64;
-  pl.GS = 4;
-  int64_t S = (1536 + pl.nblk * E - 1) / (pl.nblk * E);
-  const int64_t smax = (D + 128 * pl.GS - 1) / (128 * pl.GS);
-  if (S > smax) S = smax;
-  if (S > 32) S = 32;
-  if (S < 1) S = 1;
-  pl.S = (int)S;
-  const int64_t gblk = (D + 63) / 64;
-  int64_t SN = (1024 + gblk - 1) / gblk;
-  if (SN > (N + 511) / 512) SN = (N + 511) / 512;
-  if (SN > 16) SN = 16;
-  if (SN < 1) SN = 1;
-  pl.SN = (int)SN;
+  const SlicePlan sp = slice_plan(N, D, E);
+  pl.S = sp.S; pl.GS = sp.GS; pl.SN = sp.SN; pl.nblk = sp.nblk;
   Carver c(ws);
   pl.expF = c.take<float>((int64_t)E * Lt * N);
   pl.ith = c.take<float>(D);
@@ -636,21 +333,9 @@ static bool nb_extents_ok(int64_t N, int64_t D, int Lt, int E) {
 
 template <int KS>
 static int nb_passes(const NbArgs& a, const NbPlan& pl, hipStream_t s) {
-  constexpr int LP = 16 * ((KS + 3) / 4);
-  const size_t lds = sizeof(float) * 2 * ((size_t)(a.E < NEG ? a.E : NEG) * LP * 68 + 64);
-  // the opt-in above 64 KB is per kernel function and device and is set once: to the most the kernel can need
-  constexpr size_t lds_max = sizeof(float) * 2 * ((size_t)NEG * LP * 68 + 64);
-  static_assert(lds_max <= 160 * 1024, "nb_gene_kernel: LDS of the largest sample group");
-  if (lds_max > 64 * 1024) {
-    static bool set[64] = {};
-    int dev = 0;
-    GPZ_HIP_OK(hipGetDevice(&dev));
-    if (!set[dev & 63]) {
-      GPZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(nb_gene_kernel<KS>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-      set[dev & 63] = true;
-    }
-  }
+  const size_t lds = pass_b_lds(KS, a.E < PASS_EG ? a.E : PASS_EG);
+  static_assert(pass_b_lds(KS, PASS_EG) <= 160 * 1024, "nb_gene_kernel: LDS of the largest sample group");
+  if (int rc = lds_opt_in<nb_gene_kernel<KS>>(pass_b_lds(KS, PASS_EG))) return rc;
   hipLaunchKernelGGL((nb_spot_kernel<KS>), dim3((unsigned)(pl.nblk * a.E), (unsigned)pl.S), dim3(64 * pl.GS), 0, s, a, pl.GS);
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(nb_const_kernel, dim3((unsigned)a.D), dim3(256), 0, s, a);

@@ -46,6 +46,7 @@
 // consecutive non-zeros of a gene row.  The workspace holds nothing of D x B or nnz elements.
 #include "common.h"
 #include "mmops.h"
+#include "sparse_rows.h"
 
 namespace gpz {
 namespace nbd {
@@ -66,13 +67,6 @@ constexpr float LN2 = 0.69314718055994530942f;
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {          // every lane ends with the same sum, formed in one fixed tree
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // log1p(x), x >= 0, compensated for the rounding of 1 + x (see the head of nb.hip); below 2^-12 the series
 // x - x^2 / 2 + x^3 / 3 (its first omitted term is below 4e-12 x), so that nothing rests on the logarithm next to 1
@@ -590,39 +584,6 @@ static int instance(int Lt) {
   return 0;
 }
 
-// One workgroup: cstart[d] = number of chunks of the rows before d, chunk_gene[w] = row of chunk w (-1 past the last one).
-__global__ __launch_bounds__(1024) void nds_chunks_kernel(SpArgs a) {
-  __shared__ int sh[1024];
-  const int t = threadIdx.x;
-  for (int64_t d = t; d < a.D; d += 1024)
-    a.cstart[d] = (int32_t)((a.row_ptr[d + 1] - a.row_ptr[d] + CHUNK - 1) / CHUNK);
-  __syncthreads();
-  const int64_t per = (a.D + 1023) / 1024;
-  const int64_t d_lo = t * per < a.D ? t * per : a.D, d_hi = d_lo + per < a.D ? d_lo + per : a.D;
-  int mine = 0;
-  for (int64_t d = d_lo; d < d_hi; ++d) mine += a.cstart[d];
-  sh[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {      // inclusive scan
-    const int v = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int64_t at = sh[t] - mine;
-  const int64_t total = sh[1023];
-  __syncthreads();                          // every count has been read before any cstart[d] becomes an offset
-  for (int64_t d = d_lo; d < d_hi; ++d) {
-    const int nc = a.cstart[d];
-    a.cstart[d] = (int32_t)at;
-    for (int c = 0; c < nc; ++c)
-      if (at + c < a.nchunks) a.chunk_gene[at + c] = (int32_t)d;
-    at += nc;
-  }
-  if (t == 0) a.cstart[a.D] = (int32_t)(total < a.nchunks ? total : a.nchunks);
-  for (int64_t w = total + t; w < a.nchunks; w += 1024) a.chunk_gene[w] = -1;
-}
-
 // 4 waves per workgroup, wave = chunk w: sum y and the lgamma sums over the chunk's entries that lie in the batch
 __global__ __launch_bounds__(256) void nds_const_kernel(SpArgs a) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -662,21 +623,6 @@ __global__ __launch_bounds__(256) void nds_rate_kernel(SpArgs a, float* rD) {
 #pragma unroll
   for (int k = 0; k < CQ; ++k) a.gc[(int64_t)k * a.D + d] = v[k];
   rD[d] = (float)(v[0] / a.vsum[0]);
-}
-
-template <int LT>
-__device__ __forceinline__ void load_w(const float* W, int64_t d, int Lt, float (&w)[LT]) {
-  const float* wr = W + d * Lt;
-  if (Lt == LT) {                           // a multiple of 4: rows start 16-byte aligned
-#pragma unroll
-    for (int l = 0; l < LT; l += 4) {
-      const f4 v = *reinterpret_cast<const f4*>(wr + l);
-      w[l] = v[0]; w[l + 1] = v[1]; w[l + 2] = v[2]; w[l + 3] = v[3];
-    }
-  } else {
-#pragma unroll
-    for (int l = 0; l < LT; ++l) w[l] = l < Lt ? wr[l] : 0.f;
-  }
 }
 
 // Spot pass.  4 waves per workgroup, wave = batch spot j (global spot n = idx[j]); lanes stride over the column's
@@ -974,7 +920,7 @@ extern "C" int gpz_nb_deviance_sparse(const float* mean, const float* scale, con
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(nd_table_kernel, dim3((unsigned)((D * TROW + 255) / 256)), dim3(256), 0, s, theta, D, p.T, p.lf);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(nds_chunks_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(chunks_kernel, dim3(1), dim3(1024), 0, s, a.row_ptr, a.D, a.nchunks, CHUNK, false, a.cstart, a.chunk_gene);
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(nds_const_kernel, dim3((unsigned)((a.nchunks + 3) / 4)), dim3(256), 0, s, a);
   GPZ_LAUNCH_OK();

@@ -24,7 +24,7 @@
 // every sum in a fixed order -> two calls agree bit for bit):
 //   nbs_prologue_kernel  expF (E,Lt,B) for the zero part; expF and expF eps transposed to [B][E][LT] for the non-zero part
 //                        (LT = Lt padded to the kernel instance, zeros beyond Lt); 1 / theta
-//   nbs_chunks_kernel    the gene pass's work list: row d is cut into ceil(len_d / 512) chunks of consecutive non-zeros
+//   chunks_kernel        the gene pass's work list: row d is cut into ceil(len_d / 512) chunks of consecutive non-zeros
 //   nbs_zspot_kernel     zero part, pass A of nb.hip without its y operand: value, dV0 and dexpF0 slabs
 //   nbs_zgene_kernel     zero part, pass B of nb.hip without its y operand: dW0 slabs and dtheta0
 //   nbs_spot_kernel      non-zero part, one wave per batch spot: value, dV and the dmean / dscale contributions
@@ -32,24 +32,24 @@
 //                        (nb_const_kernel's arithmetic over the chunk's stored entries that lie in the batch)
 //   nbs_finish_kernel    adds the two parts: slabs first, then the non-zero part, chunks in chunk order
 // The layouts are those of nb.hip (which lane holds which element of a rate tile) and of poisson_sparse.hip (the two
-// orders of the counts, idx / pos of a batch, the chunk list) and are described there.  The kernels are repeated here,
-// not shared, so that the object code of nb.hip and poisson_sparse.hip does not change.  The gene pass forms Z again
-// from W[d,:] and the spot's exp(F) run: the only arrays whose length depends on nnz are per chunk.
+// orders of the counts, idx / pos of a batch, the chunk list) and are described there.  The zero part's two passes are the
+// templates of nb_passes.h that nb.hip runs with counts, here under the policy without (ZeroPart); the chunk list, the load
+// of a row of W and the wave sum are sparse_rows.h's.  Only poisson.hip keeps its own text of the passes: its pass A runs
+// two waves per SIMD at the 256-VGPR limit and any textual change re-rolls its register allocation ("Why the
+// Poisson passes keep their own text").  The gene pass forms Z again from W[d,:] and the spot's exp(F) run: the only
+// arrays whose length depends on nnz are per chunk.
 #include "common.h"
 #include "mmops.h"
+#include "nb_passes.h"
+#include "sparse_rows.h"
 
 namespace gpz {
 namespace nbs {
 
 constexpr int NMAXL = 64;   // factors
 constexpr int NMAXE = 32;   // samples per call
-constexpr int NEG = 4;      // samples the zero part's pass B holds in LDS at a time
-constexpr float LN2 = 0.69314718055994530942f;
 constexpr int CHUNK = 512;          // non-zeros of one gene row per wave of the gene pass
 constexpr int GROUP_FLOATS = 3072;  // LDS floats per wave of the spot pass: exp(F) and exp(F) eps of one sample group
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct Args {
   const float *mean, *scale, *eps, *W, *V, *theta;             // (Lt,B), (Lt,B), (E,Lt,B), (D,Lt), (B,), (D,)
@@ -69,9 +69,6 @@ struct Args {
   int64_t N, B, D, nnz, nchunks;
   int Lt, LT, E, EG, S, SD, SV, SN, with_lgamma;
 };
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x2 pkfma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 __global__ __launch_bounds__(256) void nbs_prologue_kernel(Args a) {
   __shared__ float xt[NMAXL][65], et[NMAXL][65];
@@ -102,379 +99,98 @@ __global__ __launch_bounds__(256) void nbs_prologue_kernel(Args a) {
   }
 }
 
-// One workgroup: cstart[d] = number of chunks of the rows before d, chunk_gene[w] = row of chunk w (-1 past the last one).
-__global__ __launch_bounds__(1024) void nbs_chunks_kernel(Args a) {
-  __shared__ int sh[1024];
-  const int t = threadIdx.x;
-  for (int64_t d = t; d < a.D; d += 1024)
-    a.cstart[d] = (int32_t)((a.row_ptr[d + 1] - a.row_ptr[d] + CHUNK - 1) / CHUNK);
-  __syncthreads();
-  const int64_t per = (a.D + 1023) / 1024;
-  const int64_t d_lo = t * per < a.D ? t * per : a.D, d_hi = d_lo + per < a.D ? d_lo + per : a.D;
-  int mine = 0;
-  for (int64_t d = d_lo; d < d_hi; ++d) mine += a.cstart[d];
-  sh[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {      // inclusive scan
-    const int v = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int64_t at = sh[t] - mine;
-  const int64_t total = sh[1023];
-  for (int64_t d = d_lo; d < d_hi; ++d) {
-    const int nc = a.cstart[d];
-    a.cstart[d] = (int32_t)at;
-    for (int c = 0; c < nc; ++c)
-      if (at + c < a.nchunks) a.chunk_gene[at + c] = (int32_t)d;
-    at += nc;
-  }
-  if (t == 0) a.cstart[a.D] = (int32_t)(total < a.nchunks ? total : a.nchunks);
-  for (int64_t w = total + t; w < a.nchunks; w += 1024) a.chunk_gene[w] = -1;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // zero part
 // ---------------------------------------------------------------------------------------------------------------------
 
 // The element-wise part of both zero passes.  In: the rate factor zz = Z, V of the spot, 1 / theta of the gene.
 //   ru = 1 / u, lu = log2(u), c = (x - (u - 1)) / u          log1p(x) = ln2 lu + c
-// Two transcendentals per element; E G0 = -v ru, dV0's term is zz ru and dtheta0's is x ru - log1p(x).
+// Two transcendentals per element; E G0 = -v ru, dV0's term is zz ru and dtheta0's is x ru - log1p(x).  u and c's numerator
+// are formed in one rounding each, fma(mu, 1 / theta, 1) and fma(mu, 1 / theta, -(u - 1)); written out, because the results
+// are held bit for bit and the compiler's own choice of form changes with the text around the element.
 struct ZElem { float x, ru, lu, c; };
 __device__ __forceinline__ ZElem z_elem(float zz, float v, float ith) {
   ZElem o;
-  o.x = (v * zz) * ith;
-  const float u = 1.f + o.x;
+  const float mu = v * zz;
+  o.x = mu * ith;
+  const float u = __builtin_fmaf(mu, ith, 1.f);
   o.ru = __builtin_amdgcn_rcpf(u);
   o.lu = __builtin_amdgcn_logf(u);
-  o.c = (o.x - (u - 1.f)) * o.ru;
+  o.c = __builtin_fmaf(mu, ith, -(u - 1.f)) * o.ru;
   return o;
 }
 
-// Pass A  grid (E * ceil(B/64), S), 4 waves; nb_spot_kernel of nb.hip without y.
+// What nb_passes.h asks of a step: no count operand, the spot extent is the batch's.
+struct ZeroPart {
+  static constexpr bool HAS_Y = false;
+  static __device__ __forceinline__ int64_t spots(const Args& a) { return a.B; }
+  static __device__ __forceinline__ const float* y(const Args&) { return nullptr; }
+  // pass A, value of gene g: -theta (ln2 sum lu + sum c), the two sums apart and combined per group; dv is sum_d Z / u
+  struct SumsA { float la[4] = {0.f, 0.f, 0.f, 0.f}, lb[4] = {0.f, 0.f, 0.f, 0.f}; };
+  template <bool MASKED>
+  static __device__ __forceinline__ float elem_a(SumsA& s, int g, float z, float, float v, float, float ith, float& dv, bool ok) {
+    if constexpr (!MASKED) {
+      const ZElem o = z_elem(z, v, ith);
+      s.la[g] += o.lu;
+      s.lb[g] += o.c;
+      dv = __builtin_fmaf(z, o.ru, dv);
+      return -v * o.ru;
+    } else {
+      const float zz = ok ? z : 1.f;
+      const ZElem o = z_elem(zz, v, ith);
+      s.la[g] += ok ? o.lu : 0.f;
+      s.lb[g] += ok ? o.c : 0.f;
+      dv += ok ? zz * o.ru : 0.f;
+      return ok ? -v * o.ru : 0.f;
+    }
+  }
+  static __device__ __forceinline__ double fold_a(const SumsA& s, const float (&th)[4]) {
+    float lg4 = 0.f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) lg4 = __builtin_fmaf(th[g], __builtin_fmaf(LN2, s.la[g], s.lb[g]), lg4);
+    return -(double)lg4;
+  }
+  static __device__ __forceinline__ float close_dv(float dv, float, float inv_e) { return -dv * inv_e; }
+  // pass B, dtheta0's term x / u - (ln2 lu + c): the three sums apart, combined per tile
+  struct SumsB { float tpa = 0.f, tpb = 0.f, tpx = 0.f; };
+  template <bool MASKED>
+  static __device__ __forceinline__ float elem_b(SumsB& s, float z, float, float v, float ith, bool ok) {
+    if constexpr (!MASKED) {
+      const ZElem o = z_elem(z, v, ith);
+      s.tpa += o.lu;
+      s.tpb += o.c;
+      s.tpx = __builtin_fmaf(o.x, o.ru, s.tpx);
+      return -v * o.ru;
+    } else {
+      const float zz = ok ? z : 1.f, v1 = ok ? v : 1.f;
+      const ZElem o = z_elem(zz, v1, ith);
+      s.tpa += ok ? o.lu : 0.f;
+      s.tpb += ok ? o.c : 0.f;
+      s.tpx += ok ? o.x * o.ru : 0.f;
+      return ok ? -v1 * o.ru : 0.f;
+    }
+  }
+  static __device__ __forceinline__ double fold_b(const SumsB& s, float) { return (double)(s.tpx - __builtin_fmaf(LN2, s.tpa, s.tpb)); }
+};
+
+// Pass A  grid (E * ceil(B/64), S), 4 waves: nb_pass_a of nb_passes.h.
 #ifndef GPZ_NBS_SPOT_WAVES
 #define GPZ_NBS_SPOT_WAVES 1
 #endif
 template <int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GPZ_NBS_SPOT_WAVES, GPZ_NBS_SPOT_WAVES))) void nbs_zspot_kernel(Args a, int GS) {
-  constexpr int LT16 = (KS + 3) / 4;
-  __shared__ double sh[8];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, q = lane >> 4;
-  const int e = blockIdx.x % a.E, gs = wave;
-  const int s = blockIdx.y;
-  const int64_t n0 = (int64_t)(blockIdx.x / a.E) * 64;
-  const int64_t per = (int64_t)a.Lt * a.B;
-  const int64_t dper = (a.D + a.S - 1) / a.S;
-  const int64_t d_lo = s * dper, d_hi = (d_lo + dper < a.D) ? d_lo + dper : a.D;
-  const float inv_e = 1.f / (float)a.E;
-  const bool vec = (a.B & 3) == 0;
-  const bool tile_full = n0 + 64 <= a.B;
-  float vn[4], bz[KS][4];
-  bool nok[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int64_t n = n0 + 4 * r + c;
-    nok[c] = n < a.B;
-    vn[c] = nok[c] ? a.V[n] : 1.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int l = 4 * ks + q;
-      bz[ks][c] = (nok[c] && l < a.Lt) ? a.expF[e * per + (int64_t)l * a.B + n] : 0.f;
-    }
-  }
-  f32x4 dacc[LT16][4];
-#pragma unroll
-  for (int lt = 0; lt < LT16; ++lt)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) dacc[lt][c] = f32x4{0, 0, 0, 0};
-  float dv[4] = {0.f, 0.f, 0.f, 0.f};      // sum_d Z / u
-  double ll = 0.0;
-  // one 16-gene group's operands; th / ith are theta and 1 / theta of the genes 4q + g on this lane's register axis
-  // (1 for a gene that does not exist: its elements are masked, but the arithmetic must stay finite)
-  struct Group { float wa[KS]; float wt[4][LT16]; float th[4], ith[4]; };
-  auto load_group = [&](int64_t d0, Group& G) __attribute__((always_inline)) {
-    const int64_t d = d0 + r;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int l = 4 * ks + q;
-      G.wa[ks] = (d < d_hi && l < a.Lt) ? a.W[d * a.Lt + l] : 0.f;
-    }
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int64_t dg = d0 + 4 * q + g;
-      const bool ok = dg < d_hi;
-      G.th[g] = ok ? a.theta[dg] : 1.f;
-      G.ith[g] = ok ? a.ith[dg] : 1.f;
-#pragma unroll
-      for (int lt = 0; lt < LT16; ++lt) {
-        const int l = 16 * lt + r;
-        G.wt[g][lt] = (ok && l < a.Lt) ? a.W[dg * a.Lt + l] : 0.f;
-      }
-    }
-  };
-  Group cur, nxt;
-  const int64_t dstep = 16 * GS;
-  int64_t d0 = d_lo + 16 * gs;
-  if (d0 < d_hi) load_group(d0, cur);
-  for (; d0 < d_hi; d0 += dstep) {
-    if (d0 + dstep < d_hi) load_group(d0 + dstep, nxt);
-    f32x4 z[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      z[c] = f32x4{0, 0, 0, 0};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) z[c] = mfma4(cur.wa[ks], bz[ks][c], z[c]);
-    }
-    // element-wise: -theta log1p(x), dV0's sum, and G0 in place of Z (1 / E applied at the end)
-    // value of gene g: -theta (ln2 sum lu + sum c), the two sums apart and combined per group
-    float la[4] = {0.f, 0.f, 0.f, 0.f}, lb[4] = {0.f, 0.f, 0.f, 0.f};
-    if (d0 + 16 <= d_hi && tile_full) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const ZElem o = z_elem(z[c][g], vn[c], cur.ith[g]);
-          la[g] += o.lu;
-          lb[g] += o.c;
-          dv[c] = __builtin_fmaf(z[c][g], o.ru, dv[c]);
-          z[c][g] = -vn[c] * o.ru;
-        }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const bool dok = d0 + 4 * q + g < d_hi;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const bool ok = dok && nok[c];
-          const float zz = ok ? z[c][g] : 1.f;
-          const ZElem o = z_elem(zz, vn[c], cur.ith[g]);
-          la[g] += ok ? o.lu : 0.f;
-          lb[g] += ok ? o.c : 0.f;
-          dv[c] += ok ? zz * o.ru : 0.f;
-          z[c][g] = ok ? -vn[c] * o.ru : 0.f;
-        }
-      }
-    }
-    float lg4 = 0.f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) lg4 = __builtin_fmaf(cur.th[g], __builtin_fmaf(LN2, la[g], lb[g]), lg4);
-    ll -= (double)lg4;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int lt = 0; lt < LT16; ++lt)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) dacc[lt][c] = mfma4(cur.wt[g][lt], z[c][g], dacc[lt][c]);
-    cur = nxt;
-  }
-  const int64_t slab = (int64_t)s * GS + gs;
-#pragma unroll
-  for (int lt = 0; lt < LT16; ++lt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int l = 16 * lt + 4 * q + g;
-      if (l < a.Lt) {
-        float* dp = a.dexp_slab + ((slab * a.E + e) * a.Lt + l) * a.B + n0 + 4 * r;
-        if (vec && nok[3])
-          *reinterpret_cast<f32x4*>(dp) = f32x4{dacc[lt][0][g] * inv_e, dacc[lt][1][g] * inv_e, dacc[lt][2][g] * inv_e, dacc[lt][3][g] * inv_e};
-        else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) if (nok[c]) dp[c] = dacc[lt][c][g] * inv_e;
-        }
-      }
-    }
-  const int nw = a.E * GS;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    float v = -dv[c] * inv_e;
-    v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-    if (q == 0 && nok[c]) a.dV_slab[((int64_t)s * nw + e * GS + gs) * a.B + n0 + 4 * r + c] = v;
-  }
-  const double t = block_sum(ll * (double)inv_e, sh);
-  if (threadIdx.x == 0) a.ll_slab[(int64_t)s * gridDim.x + blockIdx.x] = t;
+  nb_pass_a<KS, ZeroPart>(a, GS);
 }
 
-// Pass B  grid (ceil(D/64), SN), 4 waves; nb_gene_kernel of nb.hip without y.
+// Pass B  grid (ceil(D/64), SN), 4 waves: nb_pass_b of nb_passes.h.
 template <int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void nbs_zgene_kernel(Args a, int SN) {
-  constexpr bool TAIL = (KS % 4) == 1;
-  constexpr int LTM = TAIL ? KS / 4 : (KS + 3) / 4, LTA = LTM > 0 ? LTM : 1, L0 = 16 * LTM;
-  constexpr int LT16 = (KS + 3) / 4, LP = 16 * LT16, PF = 68;
-  extern __shared__ float smem_nbs[];
-  const int EG = a.E < NEG ? a.E : NEG, NG = (a.E + EG - 1) / EG;
-  const int FB = EG * LP * PF;
-  float* sF = smem_nbs;                         // [2][EG][LP][PF]
-  float* sV = smem_nbs + 2 * FB;                // [2][64]
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, q = lane >> 4;
-  const int64_t d0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
-  const int64_t dcol = d0 + r;
-  const bool dok = dcol < a.D;
-  const bool d_full = d0 + 16 <= a.D;
-  const int64_t ntiles = (a.B + 63) / 64, tper = (ntiles + SN - 1) / SN;
-  const int64_t t_lo = blockIdx.y * tper, t_hi = (t_lo + tper < ntiles) ? t_lo + tper : ntiles;
-  const float inv_e = 1.f / (float)a.E;
-  const float ith = dok ? a.ith[dcol] : 1.f;
-  float wb[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    const int l = 4 * ks + q;
-    wb[ks] = (dok && l < a.Lt) ? a.W[dcol * a.Lt + l] : 0.f;
-  }
-  f32x4 dwt[LTA];
-#pragma unroll
-  for (int lt = 0; lt < LTA; ++lt) dwt[lt] = f32x4{0, 0, 0, 0};
-  f32x2 tw[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) tw[t] = f32x2{0.f, 0.f};
-  double dth = 0.0;                             // sum over this lane's spots and all samples of x / u - log1p(x)
-  const int arow = 16 * (r >> 2) + (r & 3);
-  for (int i = threadIdx.x; i < 2 * FB; i += 256) sF[i] = 0.f;
-  __syncthreads();
-#if defined(__HIP_DEVICE_COMPILE__)
-  typedef __attribute__((address_space(3))) void lds_void;
-  const int64_t per = (int64_t)a.Lt * a.B;
-  const __amdgpu_buffer_rsrc_t f_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.expF), 0, (int)((int64_t)a.E * per * sizeof(float)), 0x00020000);
-  const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.V), 0, (int)(a.B * sizeof(float)), 0x00020000);
-#endif
-  auto stage = [&](int64_t tt, int gi, int buf) __attribute__((always_inline)) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const int64_t n0 = tt * 64;
-    const int e0 = gi * EG, ne = (a.E - e0 < EG) ? a.E - e0 : EG;
-    for (int el = 0; el < ne; ++el)
-      for (int l = wave; l < a.Lt; l += 4)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(f_rsrc, (lds_void*)(sF + buf * FB + (el * LP + l) * PF), 4, lane * 4,
-                                                 (int)(((e0 + el) * per + (int64_t)l * a.B + n0) * 4), 0, 0);
-    if (wave == 0)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(v_rsrc, (lds_void*)(sV + buf * 64), 4, lane * 4, (int)(n0 * 4), 0, 0);
-#endif
-  };
-  if (t_lo < t_hi) stage(t_lo, 0, 0);
-  int buf = 0;
-  for (int64_t tt = t_lo; tt < t_hi; ++tt) {
-    const int64_t n0 = tt * 64;
-    for (int gi = 0; gi < NG; ++gi, buf ^= 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (gi + 1 < NG) stage(tt, gi + 1, buf ^ 1);
-      else if (tt + 1 < t_hi) stage(tt + 1, 0, buf ^ 1);
-      f32x4 vv[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) vv[c] = *reinterpret_cast<const f32x4*>(sV + buf * 64 + 16 * q + 4 * c);
-      const int ne = (a.E - gi * EG < EG) ? a.E - gi * EG : EG;
-      for (int e = 0; e < ne; ++e) {
-        const float* fe = sF + buf * FB + e * LP * PF;
-        f32x4 z[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          z[c] = f32x4{0, 0, 0, 0};
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) z[c] = mfma4(fe[(4 * ks + q) * PF + arow + 4 * c], wb[ks], z[c]);
-        }
-        // G0^T in place of Z^T (1 / E applied at the end) and dtheta0's term x / u - (ln2 lu + c): the three sums apart,
-        // combined per tile; a spot past B reads V = 0 or a finite neighbour through the buffer descriptor, so the
-        // masked form replaces V as well as Z
-        float tpa = 0.f, tpb = 0.f, tpx = 0.f;
-        if (d_full && n0 + 64 <= a.B) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const ZElem o = z_elem(z[c][g], vv[c][g], ith);
-              tpa += o.lu;
-              tpb += o.c;
-              tpx = __builtin_fmaf(o.x, o.ru, tpx);
-              z[c][g] = -vv[c][g] * o.ru;
-            }
-        } else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const bool ok = dok && n0 + 16 * q + 4 * c + g < a.B;
-              const float zz = ok ? z[c][g] : 1.f, v1 = ok ? vv[c][g] : 1.f;
-              const ZElem o = z_elem(zz, v1, ith);
-              tpa += ok ? o.lu : 0.f;
-              tpb += ok ? o.c : 0.f;
-              tpx += ok ? o.x * o.ru : 0.f;
-              z[c][g] = ok ? -v1 * o.ru : 0.f;
-            }
-        }
-        dth += (double)(tpx - __builtin_fmaf(LN2, tpa, tpb));   // fp32 sums of 16 terms, fp64 across tiles and samples
-#pragma unroll
-        for (int lt = 0; lt < LTM; ++lt)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(fe + (16 * lt + r) * PF + 16 * q + 4 * c);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) dwt[lt] = mfma4(fa[g], z[c][g], dwt[lt]);
-          }
-        if constexpr (TAIL) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const f32x4 fv = *reinterpret_cast<const f32x4*>(fe + (L0 + t) * PF + 16 * q + 4 * c);
-              tw[t] = pkfma(f32x2{z[c][0], z[c][1]}, f32x2{fv[0], fv[1]}, tw[t]);
-              tw[t] = pkfma(f32x2{z[c][2], z[c][3]}, f32x2{fv[2], fv[3]}, tw[t]);
-            }
-        }
-      }
-    }
-  }
-  if constexpr (TAIL) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float v = (tw[t][0] + tw[t][1]) * inv_e;
-      v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-      if (q == 0 && dok && L0 + t < a.Lt) a.dW_slab[((int64_t)blockIdx.y * a.D + dcol) * a.Lt + L0 + t] = v;
-    }
-  }
-  {
-    double v = dth * (double)inv_e;
-    v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-    if (q == 0 && dok) a.dth_slab[(int64_t)blockIdx.y * a.D + dcol] = v;
-  }
-  if (dok) {
-#pragma unroll
-    for (int lt = 0; lt < LTM; ++lt)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int l = 16 * lt + 4 * q + g;
-        if (l < a.Lt) a.dW_slab[((int64_t)blockIdx.y * a.D + dcol) * a.Lt + l] = dwt[lt][g] * inv_e;
-      }
-  }
+  nb_pass_b<KS, ZeroPart>(a, SN);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // non-zero part
 // ---------------------------------------------------------------------------------------------------------------------
-
-template <int LT>
-__device__ __forceinline__ void load_w(const float* W, int64_t d, int Lt, float (&w)[LT]) {
-  const float* wr = W + d * Lt;
-  if (Lt == LT) {                           // a multiple of 4: rows start 16-byte aligned
-#pragma unroll
-    for (int l = 0; l < LT; l += 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(wr + l);
-      w[l] = v[0]; w[l + 1] = v[1]; w[l + 2] = v[2]; w[l + 3] = v[3];
-    }
-  } else {
-#pragma unroll
-    for (int l = 0; l < LT; ++l) w[l] = l < Lt ? wr[l] : 0.f;
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {     // every lane ends with the same sum, formed in one fixed tree
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // Spot pass.  4 waves per workgroup, wave = batch spot j (global spot n = idx[j]); sp_spot_kernel of poisson_sparse.hip
 // with the gene's theta as one more gathered operand.  Per non-zero and sample:
@@ -569,16 +285,6 @@ __global__ __launch_bounds__(256) void nbs_spot_kernel(Args a) {
   }
 }
 
-// psi(x), x > 0, fp64: the argument shifted above 6 by psi(x) = psi(x + 1) - 1 / x, then the asymptotic series (its first
-// omitted term is below 1e-12 there)
-__device__ __forceinline__ double digamma_pos(double x) {
-  double r = 0.0;
-  while (x < 6.0) { r -= 1.0 / x; x += 1.0; }
-  const double i = 1.0 / x, i2 = i * i;
-  const double ser = i2 * (1.0 / 12 - i2 * (1.0 / 120 - i2 * (1.0 / 252 - i2 * (1.0 / 240 - i2 * (1.0 / 132 - i2 * (691.0 / 32760 - i2 / 12))))));
-  return r + log(x) - 0.5 * i - ser;
-}
-
 // Gene pass.  4 waves per workgroup, wave = chunk w of the work list: at most 512 consecutive non-zeros of one gene row.
 // The wave packs the chunk's entries that lie in the batch (pos[n] >= 0) and are not stored zeros into LDS, in their
 // order, then every lane takes every 64th packed entry (sp_gene_kernel of poisson_sparse.hip).  The terms of y and theta
@@ -667,7 +373,7 @@ __global__ __launch_bounds__(256) void nbs_gene_kernel(Args a) {
       run *= p;
       if (run > 1e150 || run < 1e-150) { cl += log(run); run = 1.0; }
     }
-    if (a.with_lgamma) lg += (double)((whole && yi < 256) ? lfact[yi] : lgammaf(y + 1.f));
+    if (a.with_lgamma) lg += (double)lgamma1p_term(lfact, y, yi, whole);
   }
   cl += log(run);
   if (scnt > 0) {
@@ -781,20 +487,8 @@ struct Plan { int S, GS, SN, LT, EG; int64_t nblk, nchunks; size_t bytes; };
 
 static Plan make_plan(int64_t B, int64_t D, int Lt, int E, int64_t nnz, Args* a, void* ws) {
   Plan pl;
-  pl.nblk = (B + 63) / 64;
-  pl.GS = 4;
-  int64_t S = (1536 + pl.nblk * E - 1) / (pl.nblk * E);
-  const int64_t smax = (D + 128 * pl.GS - 1) / (128 * pl.GS);
-  if (S > smax) S = smax;
-  if (S > 32) S = 32;
-  if (S < 1) S = 1;
-  pl.S = (int)S;
-  const int64_t gblk = (D + 63) / 64;
-  int64_t SN = (1024 + gblk - 1) / gblk;
-  if (SN > (B + 511) / 512) SN = (B + 511) / 512;
-  if (SN > 16) SN = 16;
-  if (SN < 1) SN = 1;
-  pl.SN = (int)SN;
+  const SlicePlan sp = slice_plan(B, D, E);
+  pl.S = sp.S; pl.GS = sp.GS; pl.SN = sp.SN; pl.nblk = sp.nblk;
   pl.LT = nz_instance(Lt);
   pl.EG = nz_group(pl.LT, E);
   pl.nchunks = D + nnz / CHUNK;              // sum_d ceil(len_d / C) <= D + floor(nnz / C)
@@ -844,21 +538,9 @@ static int check_shape(const char* who, int64_t N, int64_t B, int64_t D, int Lt,
 
 template <int KS>
 static int zero_passes(const Args& a, const Plan& pl, hipStream_t s) {
-  constexpr int LP = 16 * ((KS + 3) / 4);
-  const size_t lds = sizeof(float) * 2 * ((size_t)(a.E < NEG ? a.E : NEG) * LP * 68 + 64);
-  // the opt-in above 64 KB is per kernel function and device and is set once: to the most the kernel can need
-  constexpr size_t lds_max = sizeof(float) * 2 * ((size_t)NEG * LP * 68 + 64);
-  static_assert(lds_max <= 160 * 1024, "nbs_zgene_kernel: LDS of the largest sample group");
-  if (lds_max > 64 * 1024) {
-    static bool set[64] = {};
-    int dev = 0;
-    GPZ_HIP_OK(hipGetDevice(&dev));
-    if (!set[dev & 63]) {
-      GPZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(nbs_zgene_kernel<KS>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-      set[dev & 63] = true;
-    }
-  }
+  const size_t lds = pass_b_lds(KS, a.E < PASS_EG ? a.E : PASS_EG);
+  static_assert(pass_b_lds(KS, PASS_EG) <= 160 * 1024, "nbs_zgene_kernel: LDS of the largest sample group");
+  if (int rc = lds_opt_in<nbs_zgene_kernel<KS>>(pass_b_lds(KS, PASS_EG))) return rc;
   hipLaunchKernelGGL((nbs_zspot_kernel<KS>), dim3((unsigned)(pl.nblk * a.E), (unsigned)pl.S), dim3(64 * pl.GS), 0, s, a, pl.GS);
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL((nbs_zgene_kernel<KS>), dim3((unsigned)((a.D + 63) / 64), (unsigned)pl.SN), dim3(256), lds, s, a, pl.SN);
@@ -895,7 +577,7 @@ extern "C" int gpz_nb_nsf_sparse_plan(int64_t N, int64_t B, int64_t D, int32_t L
   if (gene_slices) *gene_slices = p.S;
   if (spot_slices) *spot_slices = p.SN;
   if (samples_per_group) *samples_per_group = p.EG;
-  if (zero_samples_per_group) *zero_samples_per_group = E < NEG ? E : NEG;
+  if (zero_samples_per_group) *zero_samples_per_group = E < PASS_EG ? E : PASS_EG;
   return 0;
 }
 
@@ -936,7 +618,7 @@ extern "C" int gpz_nb_nsf_sparse(const float* mean, const float* scale, const fl
   a.N = N; a.B = B; a.D = D; a.nnz = nnz; a.Lt = Lt; a.E = E; a.with_lgamma = with_lgamma;
   hipLaunchKernelGGL(nbs_prologue_kernel, dim3((unsigned)((B + 63) / 64 * E)), dim3(256), 0, s, a);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(nbs_chunks_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(chunks_kernel, dim3(1), dim3(1024), 0, s, row_ptr, D, a.nchunks, CHUNK, false, a.cstart, a.chunk_gene);
   GPZ_LAUNCH_OK();
   int rc;
   switch (zero_ksteps(Lt)) {

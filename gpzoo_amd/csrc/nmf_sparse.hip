@@ -27,7 +27,7 @@
 //   ns_colsum_kernel + ns_colsum_final_kernel   colsum(W) from WP
 //   ns_gene_kernel           one wave per (gene, chunk of 512 consecutive non-zeros): the chunk's partial numerator
 //   ns_h_finish_kernel       adds a gene's chunk partials in chunk order, applies the update to H and HT
-// Once per call: ns_transpose_kernel (H -> HT) and ns_chunks_kernel (the gene pass's work list).  A spot's row has at most
+// Once per call: ns_transpose_kernel (H -> HT) and chunks_kernel (the gene pass's work list).  A spot's row has at most
 // D entries and spots are of similar depth, so spot rows are not cut (as in poisson_sparse.hip).
 //
 // gpz_counts_matmul (fp64) is the same wave per spot / per (gene, chunk) with the lanes across the k <= 128 columns of Q:
@@ -36,6 +36,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "sparse_rows.h"
 
 namespace gpz {
 namespace {
@@ -73,13 +74,6 @@ int ns_instance(int L) {
   const int sizes[] = {4, 8, 12, 16, 20, 24, 32, 40, 48, 64};
   for (int s : sizes) if (L <= s) return s;
   return 0;
-}
-
-template <typename T>
-__device__ __forceinline__ T ns_wave_sum(T v) {     // every lane ends with the same sum, formed in one fixed tree
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // a padded factor row (LT a multiple of 4, the row 16-byte aligned)
@@ -149,38 +143,6 @@ __global__ __launch_bounds__(64) void ns_colsum_final_kernel(const double* __res
   out[l] = v;
 }
 
-// One workgroup: cstart[d] = number of chunks of the rows before d, chunk_gene[w] = row of chunk w (-1 past the last one).
-__global__ __launch_bounds__(1024) void ns_chunks_kernel(const int64_t* __restrict__ row_ptr, int64_t D, int64_t nchunks,
-                                                         int32_t* __restrict__ cstart, int32_t* __restrict__ chunk_gene) {
-  __shared__ int sh[1024];
-  const int t = threadIdx.x;
-  for (int64_t d = t; d < D; d += 1024) cstart[d] = (int32_t)((row_ptr[d + 1] - row_ptr[d] + NS_CHUNK - 1) / NS_CHUNK);
-  __syncthreads();
-  const int64_t per = (D + 1023) / 1024;
-  const int64_t d_lo = t * per < D ? t * per : D, d_hi = d_lo + per < D ? d_lo + per : D;
-  int mine = 0;
-  for (int64_t d = d_lo; d < d_hi; ++d) mine += cstart[d];
-  sh[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {      // inclusive scan
-    const int v = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int64_t at = sh[t] - mine;
-  const int64_t total = sh[1023];
-  for (int64_t d = d_lo; d < d_hi; ++d) {
-    const int nc = cstart[d];
-    cstart[d] = (int32_t)at;
-    for (int c = 0; c < nc; ++c)
-      if (at + c < nchunks) chunk_gene[at + c] = (int32_t)d;
-    at += nc;
-  }
-  if (t == 0) cstart[D] = (int32_t)(total < nchunks ? total : nchunks);
-  for (int64_t w = total + t; w < nchunks; w += 1024) chunk_gene[w] = -1;
-}
-
 // Spot pass.  4 waves per workgroup, wave = spot n; no barrier, so a wave without a spot leaves at once.
 // UPDATE: the W update of spot n, written to W and to WP (zeros beyond L).  Otherwise the spot's two sums of the divergence.
 template <typename T, int LT, bool UPDATE>
@@ -214,7 +176,7 @@ __global__ __launch_bounds__(256) void ns_spot_kernel(NsArgs<T> a) {
     T mine = T(0);
 #pragma unroll
     for (int l = 0; l < LT; ++l) {
-      const T t = ns_wave_sum(acc[l]);
+      const T t = wave_sum(acc[l]);
       if (lane == l) mine = t;
     }
     if (lane < LT) {
@@ -228,8 +190,8 @@ __global__ __launch_bounds__(256) void ns_spot_kernel(NsArgs<T> a) {
       a.WP[n * LT + lane] = out;
     }
   } else {
-    dv = ns_wave_sum(dv);
-    dx = ns_wave_sum(dx);
+    dv = wave_sum(dv);
+    dx = wave_sum(dx);
     if (lane == 0) {
       a.dspot[2 * n] = dv;
       a.dspot[2 * n + 1] = dx;
@@ -262,7 +224,7 @@ __global__ __launch_bounds__(256) void ns_gene_kernel(NsArgs<T> a) {
   T mine = T(0);
 #pragma unroll
   for (int l = 0; l < LT; ++l) {
-    const T t = ns_wave_sum(acc[l]);
+    const T t = wave_sum(acc[l]);
     if (lane == l) mine = t;
   }
   if (lane < LT) a.part[wi * LT + lane] = mine;
@@ -435,7 +397,7 @@ int ns_prologue(const NsArgs<T>& a, bool chunks, hipStream_t s) {
   hipLaunchKernelGGL((ns_transpose_kernel<T>), dim3((unsigned)((a.D + 63) / 64)), dim3(256), 0, s, a.H, a.D, a.L, a.LT, a.HT);
   GPZ_LAUNCH_OK();
   if (chunks) {
-    hipLaunchKernelGGL(ns_chunks_kernel, dim3(1), dim3(1024), 0, s, a.c.row_ptr, a.D, a.nchunks, a.cstart, a.chunk_gene);
+    hipLaunchKernelGGL(chunks_kernel, dim3(1), dim3(1024), 0, s, a.c.row_ptr, a.D, a.nchunks, NS_CHUNK, false, a.cstart, a.chunk_gene);
     GPZ_LAUNCH_OK();
   }
   return 0;
@@ -609,7 +571,7 @@ extern "C" int gpz_counts_matmul(const int64_t* col_ptr, const int32_t* col_gene
     GPZ_LAUNCH_OK();
     return 0;
   }
-  hipLaunchKernelGGL(ns_chunks_kernel, dim3(1), dim3(1024), 0, s, row_ptr, D, a.nchunks, a.cstart, a.chunk_gene);
+  hipLaunchKernelGGL(chunks_kernel, dim3(1), dim3(1024), 0, s, row_ptr, D, a.nchunks, NS_CHUNK, false, a.cstart, a.chunk_gene);
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL((ns_matmul_kernel<true>), dim3((unsigned)((a.nchunks + 3) / 4)), dim3(256), 0, s, a);
   GPZ_LAUNCH_OK();

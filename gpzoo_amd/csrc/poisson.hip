@@ -19,6 +19,7 @@
 //   finish_kernel     sums the slabs into dmean, dscale, dV, dW and the scalar
 #include "common.h"
 #include "mmops.h"
+#include "nb_passes.h"   // the vector types, mfma4 / pkfma, the slice plan and the LDS opt-in; the two passes here keep their own text
 
 namespace gpz {
 
@@ -47,10 +48,6 @@ __global__ void expf_kernel(PoissonArgs a) {
   a.expF[i] = __expf(a.mean[ln] + a.scale[ln] * a.eps[i]);
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // Both passes put their three dense products -- the rate Z = W expF, dexpF = W^T G and dW = G expF^T with
 // G = (y / Z - V) / E -- on v_mfma_f32_16x16x4_f32 and keep the element-wise part (log, reciprocal, the Poisson
 // terms) on the accumulator registers in between; nothing but y, W and expF is read and only the gradients are
@@ -73,8 +70,6 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __bui
 // E = 3.  The same in pass A was measured and NOT kept: that pass already issues 4.3 vector instructions per MFMA (log,
 // reciprocal and the Poisson terms per element), the extra ones cost more issue time than the 16 MFMAs they replace
 // (0.60 -> 0.86 ms with the operands single-buffered to make room for them, 0.72 ms for the single-buffering alone).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pkfma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 template <int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void spot_mfma_kernel(PoissonArgs a, int GS) {
@@ -492,22 +487,8 @@ struct PoissonPlan { int S, GS, SN; int64_t nblk; size_t bytes; float *expF, *de
 
 static PoissonPlan poisson_plan(int64_t N, int64_t D, int Lt, int E, void* ws) {
   PoissonPlan pl;
-  pl.nblk = (N + 63) / 64;                     // spot tiles of pass A
-  pl.GS = 4;                                   // 16-gene sub-groups (waves) per workgroup
-  // pass A: enough (spot tile, gene slice) workgroups to fill 256 CUs a few times over, slices of >= 8 gene groups per wave
-  int64_t S = (1536 + pl.nblk * E - 1) / (pl.nblk * E);
-  const int64_t smax = (D + 128 * pl.GS - 1) / (128 * pl.GS);
-  if (S > smax) S = smax;
-  if (S > 32) S = 32;
-  if (S < 1) S = 1;
-  pl.S = (int)S;
-  // pass B: gene blocks of 64 x spot slices
-  const int64_t gblk = (D + 63) / 64;
-  int64_t SN = (1024 + gblk - 1) / gblk;
-  if (SN > (N + 511) / 512) SN = (N + 511) / 512;
-  if (SN > 16) SN = 16;
-  if (SN < 1) SN = 1;
-  pl.SN = (int)SN;
+  const SlicePlan sp = slice_plan(N, D, E);
+  pl.S = sp.S; pl.GS = sp.GS; pl.SN = sp.SN; pl.nblk = sp.nblk;
   Carver c(ws);
   pl.expF = c.take<float>((int64_t)E * Lt * N);
   pl.dexp = c.take<float>((int64_t)pl.S * pl.GS * E * Lt * N);
@@ -531,22 +512,9 @@ extern "C" size_t gpz_poisson_nsf_workspace_bytes(int64_t N, int64_t D, int32_t 
 
 template <int KS>
 static int poisson_passes(const PoissonArgs& a, const PoissonPlan& pl, hipStream_t s) {
-  constexpr int LP = 16 * ((KS + 3) / 4);
-  const size_t lds = sizeof(float) * 2 * ((size_t)(a.E < PEG ? a.E : PEG) * LP * 68 + 64);
-  // The opt-in above 64 KB is per kernel function and device and is set ONCE, so it is set to what the kernel can need
-  // at most (a full sample group), not to this call's size: a later call with more samples must still fit under it.
-  constexpr size_t lds_max = sizeof(float) * 2 * ((size_t)PEG * LP * 68 + 64);
-  static_assert(lds_max <= 160 * 1024, "gene_mfma_kernel: LDS of the largest sample group");
-  if (lds_max > 64 * 1024) {
-    static bool set[64] = {};
-    int dev = 0;
-    GPZ_HIP_OK(hipGetDevice(&dev));
-    if (!set[dev & 63]) {
-      GPZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(gene_mfma_kernel<KS>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-      set[dev & 63] = true;
-    }
-  }
+  const size_t lds = pass_b_lds(KS, a.E < PEG ? a.E : PEG);
+  static_assert(pass_b_lds(KS, PEG) <= 160 * 1024, "gene_mfma_kernel: LDS of the largest sample group");
+  if (int rc = lds_opt_in<gene_mfma_kernel<KS>>(pass_b_lds(KS, PEG))) return rc;
   hipLaunchKernelGGL((spot_mfma_kernel<KS>), dim3((unsigned)(pl.nblk * a.E), (unsigned)pl.S), dim3(64 * pl.GS), 0, s, a, pl.GS);
   GPZ_LAUNCH_OK();
   if (a.with_lgamma) hipLaunchKernelGGL(lgamma_sum_kernel, dim3((unsigned)a.nlg), dim3(256), 0, s, a);

@@ -21,7 +21,7 @@
 //                        Lt): one spot's samples and factors are one contiguous run
 //   sp_colsum_kernel     column sums of W (for c) and, after the spot pass, of V sum_e expF (for s): partials per 256 rows,
 //                        then sp_colsum_final_kernel adds them in ascending order
-//   sp_chunks_kernel     the gene pass's work list: row d is cut into ceil(len_d / 512) chunks of consecutive non-zeros
+//   chunks_kernel     the gene pass's work list: row d is cut into ceil(len_d / 512) chunks of consecutive non-zeros
 //   sp_spot_kernel       one wave per batch spot, lanes stride over the column's non-zeros: log-lik, dV, dmean, dscale
 //   sp_gene_kernel       one wave per (gene, chunk): the chunk's partial of sum_e sum_k q expF
 //   sp_finish_kernel     dW from the chunk partials in chunk order minus s; the two scalars
@@ -30,6 +30,7 @@
 // reading the device.  So there is no array of nnz elements in the workspace at all.
 #include "common.h"
 #include "mmops.h"
+#include "sparse_rows.h"
 
 namespace gpz {
 
@@ -123,61 +124,6 @@ __global__ __launch_bounds__(64) void sp_colsum_final_kernel(const double* part,
   out[l] = (float)v;
 }
 
-// One workgroup: cstart[d] = number of chunks of the rows before d, chunk_gene[w] = row of chunk w (-1 past the last one).
-__global__ __launch_bounds__(1024) void sp_chunks_kernel(SparseArgs a) {
-  __shared__ int sh[1024];
-  const int t = threadIdx.x;
-  // chunks per row, with coalesced independent loads, parked in cstart
-  for (int64_t d = t; d < a.D; d += 1024)
-    a.cstart[d] = (int32_t)((a.row_ptr[d + 1] - a.row_ptr[d] + SP_CHUNK - 1) / SP_CHUNK);
-  __syncthreads();
-  const int64_t per = (a.D + 1023) / 1024;
-  const int64_t d_lo = t * per < a.D ? t * per : a.D, d_hi = d_lo + per < a.D ? d_lo + per : a.D;
-  int mine = 0;
-  for (int64_t d = d_lo; d < d_hi; ++d) mine += a.cstart[d];
-  sh[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {      // inclusive scan
-    const int v = t >= o ? sh[t - o] : 0;
-    __syncthreads();
-    sh[t] += v;
-    __syncthreads();
-  }
-  int64_t at = sh[t] - mine;
-  const int64_t total = sh[1023];
-  for (int64_t d = d_lo; d < d_hi; ++d) {
-    const int nc = a.cstart[d];
-    a.cstart[d] = (int32_t)at;
-    for (int c = 0; c < nc; ++c)
-      if (at + c < a.nchunks) a.chunk_gene[at + c] = (int32_t)d;
-    at += nc;
-  }
-  if (t == 0) a.cstart[a.D] = (int32_t)(total < a.nchunks ? total : a.nchunks);
-  for (int64_t w = total + t; w < a.nchunks; w += 1024) a.chunk_gene[w] = -1;
-}
-
-template <int LT>
-__device__ __forceinline__ void sp_load_w(const float* W, int64_t d, int Lt, float (&w)[LT]) {
-  const float* wr = W + d * Lt;
-  if (Lt == LT) {                           // a multiple of 4: rows start 16-byte aligned
-#pragma unroll
-    for (int l = 0; l < LT; l += 4) {
-      const sf32x4 v = *reinterpret_cast<const sf32x4*>(wr + l);
-      w[l] = v[0]; w[l + 1] = v[1]; w[l + 2] = v[2]; w[l + 3] = v[3];
-    }
-  } else {
-#pragma unroll
-    for (int l = 0; l < LT; ++l) w[l] = l < Lt ? wr[l] : 0.f;
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ T sp_wave_sum(T v) {     // every lane ends with the same sum, formed in one fixed tree
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // Spot pass.  4 waves per workgroup, wave = batch spot j (global spot n = idx[j]).  The spot's exp(F) and exp(F) eps runs go
 // through LDS in groups of EG samples; each lane takes every 64th non-zero of the column, reads its gene's row of W and forms
 //   Z[e] = w . expF[e],  q[e] = y / Z[e],  A[l] = sum_e q[e] expF[e,l],  B[l] = sum_e q[e] expF[e,l] eps[e,l]
@@ -217,7 +163,7 @@ __global__ __launch_bounds__(256) void sp_spot_kernel(SparseArgs a) {
       const float y = a.col_val[k];
       if (y == 0.f) continue;                            // an explicit zero: 0 log(.) is never formed
       float w[LT], A[LT], Bv[LT];
-      sp_load_w<LT>(a.W, a.col_gene[k], a.Lt, w);
+      load_w<LT>(a.W, a.col_gene[k], a.Lt, w);
 #pragma unroll
       for (int l = 0; l < LT; ++l) A[l] = Bv[l] = 0.f;
       float slog = 0.f;
@@ -259,14 +205,14 @@ __global__ __launch_bounds__(256) void sp_spot_kernel(SparseArgs a) {
   float my_dm = 0.f, my_ds = 0.f;
 #pragma unroll
   for (int l = 0; l < LT; ++l) {
-    const float tm = sp_wave_sum(dm[l]), ts = sp_wave_sum(ds[l]);
+    const float tm = wave_sum(dm[l]), ts = wave_sum(ds[l]);
     if (lane == l) { my_dm = tm; my_ds = ts; }
   }
   const float cl = lane < LT ? sc[lane] : 0.f;
-  const float tsum = sp_wave_sum(cl * sxl);              // sum_e t[e,n]
-  ysum = sp_wave_sum(ysum);
-  ll = sp_wave_sum(ll);
-  lg = sp_wave_sum(lg);
+  const float tsum = wave_sum(cl * sxl);              // sum_e t[e,n]
+  ysum = wave_sum(ysum);
+  ll = wave_sum(ll);
+  lg = wave_sum(lg);
   if (!valid) return;
   if (lane < a.Lt) {
     a.dmean[(int64_t)lane * a.B + j] = inv_e * (my_dm - vn * cl * sxl);
@@ -317,7 +263,7 @@ __global__ __launch_bounds__(256) void sp_gene_kernel(SparseArgs a) {
   __syncthreads();                 // every wave, with or without a chunk, arrives here exactly once
   if (g < 0) return;
   float w[LT], acc[LT];
-  sp_load_w<LT>(a.W, g, a.Lt, w);
+  load_w<LT>(a.W, g, a.Lt, w);
 #pragma unroll
   for (int l = 0; l < LT; ++l) acc[l] = 0.f;
   for (int i = lane; i < cnt; i += 64) {
@@ -342,7 +288,7 @@ __global__ __launch_bounds__(256) void sp_gene_kernel(SparseArgs a) {
   float mine = 0.f;
 #pragma unroll
   for (int l = 0; l < LT; ++l) {
-    const float t = sp_wave_sum(acc[l]);
+    const float t = wave_sum(acc[l]);
     if (lane == l) mine = t;
   }
   if (lane < LT) a.part[wi * LT + lane] = mine;
@@ -480,7 +426,7 @@ extern "C" int gpz_poisson_nsf_sparse(const float* mean, const float* scale, con
   GPZ_LAUNCH_OK();
   hipLaunchKernelGGL(sp_colsum_final_kernel, dim3(1), dim3(64), 0, s, a.cpart, a.nbW, a.LT, a.csum);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(sp_chunks_kernel, dim3(1), dim3(1024), 0, s, a);
+  hipLaunchKernelGGL(chunks_kernel, dim3(1), dim3(1024), 0, s, a.row_ptr, a.D, a.nchunks, SP_CHUNK, false, a.cstart, a.chunk_gene);
   GPZ_LAUNCH_OK();
   int rc;
   switch (a.LT) {

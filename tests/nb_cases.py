@@ -39,6 +39,12 @@ SWEEP = [
     (257, 1, 20, 3, False, "a single spot under every gene block"),
 ]
 
+# (D, N, Lt, E): the lowest and the highest factor count of each of the nine kernel instances on the smallest shape that has
+# both paths of both passes in one launch -- N = 68 is a multiple of 4 (the 16-byte paths), spot tile 0 is full (the
+# interior branch) and tile 1 holds 4 spots (the masked branch), gene groups 0..15 and 16..31 are full and 32..39 is
+# partial; one gene slice, one spot slice
+INSTANCE_ENDS = [(40, 68, Lt, 2) for Lt in (1, 4, 5, 8, 9, 16, 17, 20, 21, 24, 25, 32, 33, 40, 41, 48, 49, 64)]
+
 
 def make_inputs(D, N, Lt, E, seed, theta=None):
     """Inputs built like test_random_poisson_shapes; theta log-spaced over [0.3, 50] across the genes (or the given value

@@ -29,8 +29,9 @@ def cdiv(a: int, b: int) -> int:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the library's own launch arithmetic, restated (csrc/poisson.hip: poisson_plan, the dispatch switch, poisson_passes,
-# gene_mfma_kernel's constants; csrc/common.h: Carver; gpzoo_amd/ops.py: the split of the samples)
+# the library's own launch arithmetic, restated (csrc/nb_passes.h: slice_plan, pass_b_lds and the LDS opt-in;
+# csrc/poisson.hip: poisson_plan, the dispatch switch, poisson_passes, gene_mfma_kernel's constants; csrc/common.h: Carver;
+# gpzoo_amd/ops.py: the split of the samples)
 # ---------------------------------------------------------------------------------------------------------------------
 
 def kernel_instance(Lt: int) -> int:

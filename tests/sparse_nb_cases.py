@@ -212,6 +212,18 @@ def tile_case(shape):
         _corners(D, N)))
 
 
+# 2b. both ends of every kernel instance of the zero part on nb_cases.INSTANCE_ENDS' shape: (B, D, Lt, E) = (68, 40, Lt, 2)
+# has aligned rows, a full and a ragged spot tile, two full 16-gene groups and a partial one in a single launch of each pass
+INSTANCE_END_SHAPES = [(N, D, Lt, E) for D, N, Lt, E in NB.INSTANCE_ENDS]
+
+
+def instance_end_case(shape):
+    N, D, Lt, E = shape
+    return _cached(("ends",) + tuple(shape), lambda: sharpen(
+        lambda pr, over: make_nb_case(N, D, Lt, E, seed=700 + Lt, density=0.08, probes=pr, theta_over=over),
+        _corners(D, N)))
+
+
 # 3. chunk boundaries
 CHUNK_GENES = SC.CHUNK_GENES
 CHUNK_SHAPE = (1037, 80, 20, 3)

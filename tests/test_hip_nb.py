@@ -19,6 +19,15 @@ def test_nb_sweep(i):
     NC.check(ll, got, ref, grads, dict(D=D, N=N, Lt=Lt, E=E, with_lgamma=with_lgamma, why=why))
 
 
+@pytest.mark.parametrize("D,N,Lt,E", NC.INSTANCE_ENDS, ids=["Lt%d" % c[2] for c in NC.INSTANCE_ENDS])
+def test_nb_instance_ends(D, N, Lt, E):
+    """Both ends of every kernel instance, each with the interior and the masked branch of both passes in one launch."""
+    c = NC.make_inputs(D, N, Lt, E, seed=1500 + Lt)
+    ref, grads = NC.oracle(c, True)
+    ll, got = NC.run(c, True)
+    NC.check(ll, got, ref, grads, dict(D=D, N=N, Lt=Lt, E=E))
+
+
 def test_host_split_counts_the_sample_independent_terms_once():
     """E = 33 goes through two calls (32 + 1); lgamma(y + theta) - lgamma(theta), the psi terms of dtheta and lgamma(y + 1)
     do not depend on the sample and must enter the value and dtheta once."""

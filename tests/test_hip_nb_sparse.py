@@ -64,6 +64,13 @@ def test_case_against_oracle(name):
         assert torch.equal(a, b), k
 
 
+@pytest.mark.parametrize("shape", SN.INSTANCE_END_SHAPES, ids=["Lt%d" % s[2] for s in SN.INSTANCE_END_SHAPES])
+def test_zero_part_instance_ends(shape):
+    """Both ends of every kernel instance of the zero part, each with the interior and the masked branch of both passes."""
+    c = SN.instance_end_case(shape)
+    check(c, run(c, True), True, "ends-" + SN._shape_id(shape))
+
+
 def test_near_poisson_limit():
     c = BY_NAME["poisson_limit"]
     atol = SN.poisson_limit_theta_atol(c)

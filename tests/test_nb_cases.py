@@ -31,6 +31,21 @@ def test_sweep_reaches_both_ends_of_every_kernel_instance():
     assert served == set(inst)
 
 
+def test_instance_ends_reach_both_ends_of_every_kernel_instance():
+    """INSTANCE_ENDS runs each of the nine instances at the lowest and the highest factor count it serves, on one shape with
+    aligned rows, a full and a ragged spot tile, full and a partial gene group, and one slice of either kind."""
+    inst = instances()
+    assert len(inst) == 9
+    ends = sorted(Lt for _, _, Lt, _ in NC.INSTANCE_ENDS)
+    assert ends == sorted(Lt for lo_hi in inst.values() for Lt in lo_hi) and len(ends) == 18
+    assert {(D, N, E) for D, N, _, E in NC.INSTANCE_ENDS} == {(40, 68, 2)}
+    for D, N, Lt, E in NC.INSTANCE_ENDS:
+        p = plan(N, D, Lt, E)
+        assert inst[p["factors_padded"]][0] <= Lt <= inst[p["factors_padded"]][1]
+        assert p["aligned_rows"] and p["gene_slices"] == 1 and p["spot_slices"] == 1
+        assert 64 < N < 128 and N % 64 and D > 32 and D % 16
+
+
 def test_sweep_takes_both_alignment_paths_and_every_extent():
     aligned = {plan(N, D, Lt, E)["aligned_rows"] for D, N, Lt, E, _, _ in NC.SWEEP}
     assert aligned == {True, False}

@@ -88,6 +88,17 @@ def test_every_kernel_instance_is_visited():
         assert p["factors_padded"] >= Lt and p["zero_factors_padded"] >= Lt and p["factors_padded"] % 4 == 0
 
 
+def test_instance_end_shapes_reach_both_ends_of_every_zero_instance():
+    every = {}
+    for Lt in range(1, 65):
+        every.setdefault(SN.plan(68, 68, 40, Lt, 2)["zero_factors_padded"], []).append(Lt)
+    ends = sorted(Lt for v in every.values() for Lt in (min(v), max(v)))
+    assert len(every) == 9 and sorted(s[2] for s in SN.INSTANCE_END_SHAPES) == ends
+    for N, D, Lt, E in SN.INSTANCE_END_SHAPES:
+        p = SN.plan(N, N, D, Lt, E)
+        assert (N, D, E) == (68, 40, 2) and p["gene_slices"] == 1 and p["spot_slices"] == 1
+
+
 def test_case_list_contains_each_boundary():
     # tile edges of the zero part
     assert {s[0] for s in SN.TILE_SHAPES} == set(NB.SPOTS) == {1, 63, 64, 65, 500}
