@@ -14,7 +14,8 @@
 //   I = [ C - xbar (K S + A) + N K xbar^2 ] / ( K (Q - N xbar^2) )
 // -- sum_i z_i sum_j z_j of the dense kernel (spatial.hip) expanded around the zeros, which are never visited.
 //
-// Gene pass (both entries): one workgroup of GR_THREADS threads per gene at a time, genes dealt to a fixed number of
+// Gene pass (both entries; its helpers are gene_rows.h's, shared with gene_dispersion.hip): one workgroup of GR_THREADS
+// threads per gene at a time, genes dealt to a fixed number of
 // workgroups in a fixed order (gene d, d + G, ...).  Thread t adds the entries t, t + GR_THREADS, ... of the row in that
 // order in fp64, the GR_THREADS partial sums are added in a fixed binary tree: the result of a gene depends on neither the
 // grid nor the workgroup that computes it, and two calls agree bit for bit.  A row of N entries is GR_THREADS-wide
@@ -29,48 +30,15 @@
 // Built with -ffp-contract=off: every product and sum of the closing formulas is rounded on its own, so the numbers are
 // those of the same expressions written in numpy (the CPU tests evaluate them that way), not of a compiler's choice of fma.
 // The kernels wait for memory, not for the ALUs, so this costs nothing.
-#include "common.h"
+#include "gene_rows.h"
 
 namespace gpz {
 namespace grk {
 
-constexpr int GR_THREADS = 256;    // threads of a workgroup = stored entries of a row per sweep (the plan's gene_chunk)
 constexpr int GR_MAX_WG = 256;     // workgroups of the Moran pass (one per CU): its scratch is GR_MAX_WG lines, and more lines
                                    // in flight bought nothing (measured: DESIGN.md section 5)
 constexpr int GR_DEV_WG = 2048;    // workgroups of the deviance pass (eight per CU, a full CU of waves; it has no lines)
 constexpr int GR_KMAX = 32;
-
-struct GrRows {
-  const int64_t* row_ptr; const int32_t* row_spot; const int32_t* row_perm; const float* col_val;
-  int64_t N, D, nnz;
-};
-
-// red[0] = the sum of red[0 .. GR_THREADS) in a fixed binary tree; every thread of the workgroup calls it
-template <int NV>
-__device__ inline void gr_tree(double (*red)[GR_THREADS]) {
-  __syncthreads();
-  for (int h = GR_THREADS / 2; h >= 1; h >>= 1) {
-    if (int(threadIdx.x) < h)
-      for (int v = 0; v < NV; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
-    __syncthreads();
-  }
-}
-
-// the row of gene d, clamped to the stored entries: an inconsistent row_ptr reads nothing out of bounds
-__device__ inline void gr_row(const GrRows& r, int64_t d, int64_t& lo, int64_t& hi) {
-  lo = r.row_ptr[d];
-  hi = r.row_ptr[d + 1];
-  lo = lo < 0 ? 0 : (lo > r.nnz ? r.nnz : lo);
-  hi = hi < lo ? lo : (hi > r.nnz ? r.nnz : hi);
-}
-
-__device__ inline bool gr_entry(const GrRows& r, int64_t k, int32_t& spot, float& x) {
-  spot = r.row_spot[k];
-  const int32_t p = r.row_perm[k];
-  if (spot < 0 || spot >= r.N || p < 0 || p >= r.nnz) return false;
-  x = r.col_val[p];
-  return true;
-}
 
 // S = sum_n size[n]: one workgroup, strided per thread, then the tree
 __global__ __launch_bounds__(GR_THREADS) void gr_total_kernel(const double* __restrict__ size, int64_t N, double* __restrict__ total) {
@@ -234,14 +202,6 @@ static GrPlan gr_plan(int64_t N, int64_t D, bool moran, void* scratch) {
   }
   p.bytes = c.used();
   return p;
-}
-
-static int gr_check_shape(const char* who, int64_t N, int64_t D, int64_t nnz) {
-  GPZ_REQUIRE(N >= 1 && D >= 1 && nnz >= 0, "%s: bad extents (N = %lld, D = %lld, nnz = %lld)", who, (long long)N, (long long)D,
-              (long long)nnz);
-  GPZ_REQUIRE(N < (1ll << 31) && D < (1ll << 31) && nnz < (1ll << 31), "%s: spots, genes and non-zeros are indexed with 32 bits",
-              who);
-  return 0;
 }
 
 static int gr_check_k(const char* who, int64_t N, int32_t K) {

@@ -577,16 +577,30 @@ LIKELIHOODS = ("poisson", "nb")
 
 def _init_likelihood(module, likelihood, theta0, D):
     """The ``likelihood=`` / ``theta0=`` keywords of the count models.  "poisson" adds nothing (the parameters stay the
-    reference's); "nb" adds ``theta`` (D,), raw, with softplus(theta) = theta0 (``init_softplus``)."""
+    reference's); "nb" adds ``theta`` (D,), raw, with softplus(theta) = theta0 (``init_softplus``).
+
+    ``theta0``: one positive number for every gene, or a (D,) array or tensor of finite positive values, e.g. the start from
+    a gene-wise fit, ``theta0=disp.theta.nan_to_num(nan=10.0).clamp(1e-2, 1e3)`` with ``disp = gene_dispersion(y)``.  That
+    fit holds each gene's rate at the constant-rate null, which absorbs the biological variation the factors will explain:
+    its theta is a lower-biased start, not an estimate of the model's theta."""
     if likelihood not in LIKELIHOODS:
         raise ValueError(f"{type(module).__name__}: likelihood={likelihood!r} unknown (one of {LIKELIHOODS})")
     module.likelihood = likelihood
     if likelihood == "nb":
         import numpy as np
         from .utilities import init_softplus
-        if not float(theta0) > 0:
-            raise ValueError(f"{type(module).__name__}: theta0 must be positive, got {theta0}")
-        raw = init_softplus(np.full((D,), float(theta0), dtype=np.float64))
+        who = type(module).__name__
+        if isinstance(theta0, (list, tuple)) or (isinstance(theta0, (torch.Tensor, np.ndarray)) and theta0.ndim > 0):
+            start = (theta0.detach().cpu() if isinstance(theta0, torch.Tensor) else torch.as_tensor(np.asarray(theta0))).double().numpy()
+            if start.shape != (D,):
+                raise ValueError(f"{who}: theta0 of shape {start.shape} for {D} genes (a number or ({D},) values expected)")
+            if not (np.isfinite(start).all() and (start > 0).all()):
+                raise ValueError(f"{who}: every theta0 must be positive and finite")
+        else:
+            if not float(theta0) > 0:
+                raise ValueError(f"{who}: theta0 must be positive, got {theta0}")
+            start = np.full((D,), float(theta0), dtype=np.float64)
+        raw = init_softplus(start)
         module.theta = nn.Parameter(torch.as_tensor(raw, dtype=torch.get_default_dtype()))
 
 

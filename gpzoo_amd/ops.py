@@ -1590,6 +1590,67 @@ def gene_morans_i_sparse(values, nbr) -> torch.Tensor:
     return out
 
 
+def gene_dispersion_plan(N: int, D: int, nnz: int) -> dict:
+    """How ``gene_dispersion_sparse`` covers a shape (gpz_gene_dispersion_sparse_plan, a host-only query: no device needed):
+    ``gene_chunk`` (stored entries of a gene row per sweep of its workgroup), ``workgroups`` (genes in flight), ``tol_t`` (the
+    solver stops at a step or bracket of this size in log theta), ``partials_bytes``."""
+    lib = _lib.load()
+    gc, wg, tol, nb = C.c_int32(), C.c_int32(), C.c_double(), C.c_int64()
+    if lib.gpz_gene_dispersion_sparse_plan(int(N), int(D), int(nnz), C.byref(gc), C.byref(wg), C.byref(tol), C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, workgroups=wg.value, tol_t=tol.value, partials_bytes=int(nb.value))
+
+
+def gene_dispersion_sparse(counts, size, theta_min: float = 1e-4, theta_max: float = 1e6, max_iter: int = 50):
+    """Per-gene (theta, gain, poisson_loglik, status, iterations) of a whole ``SparseCounts``: the maximum-likelihood
+    negative-binomial inverse dispersion under the constant-rate null mu_n = p size_n, p = sum y / sum size
+    (gpz_gene_dispersion_sparse; include/gpzoo_hip.h has the statistic).  ``size`` (N,) fp64 on the counts' device, >= 0 and
+    positive wherever a spot has a stored count.  theta, gain, poisson_loglik fp64 (D,), status and iterations int32 (D,):
+    status 0 an interior root, 1 theta = +inf (no overdispersion below ``theta_max``; gain 0), 2 ``theta_min``, 3 not
+    converged in ``max_iter`` <= 200 score evaluations (``max_iter=0``: the moment start), 4 a gene without counts (NaN).
+    A stored value that is negative or not an integer, or a bad size, raises ValueError (checked on the device; one
+    synchronisation)."""
+    import math
+    from .likelihoods import SparseCounts, _counts_expected
+    who = "gene_dispersion_sparse"
+    _counts_expected(counts, who)
+    if not isinstance(counts, SparseCounts):
+        raise TypeError(f"{who}: counts must be a SparseCounts, got {type(counts).__name__}")
+    c = _whole_values(counts, who)
+    theta_min, theta_max = float(theta_min), float(theta_max)
+    if not (0.0 < theta_min < theta_max and math.isfinite(theta_max)):
+        raise ValueError(f"{who}: theta range ({theta_min}, {theta_max}) unsupported (0 < theta_min < theta_max, both finite)")
+    if int(max_iter) != max_iter or not 0 <= int(max_iter) <= 200:
+        raise ValueError(f"{who}: max_iter = {max_iter!r} outside [0, 200]")
+    D, N = c.shape
+    if not isinstance(size, torch.Tensor) or size.dtype != torch.float64 or tuple(size.shape) != (N,):
+        raise ValueError(f"{who}: size must be an ({N},) float64 tensor")
+    _need_cuda(c.col_val)
+    if size.device != c.device:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {c.device}, size on {size.device}")
+    size = size.detach().contiguous()
+    lib = _lib.load()
+    dev = c.device
+    nb = C.c_int64()
+    if lib.gpz_gene_dispersion_sparse_plan(N, D, c.nnz, None, None, None, C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    out = [torch.empty(D, dtype=torch.float64, device=dev) for _ in range(3)]
+    out += [torch.empty(D, dtype=torch.int32, device=dev) for _ in range(2)]
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nb.value)
+        rc = lib.gpz_gene_dispersion_sparse(_ptr(c.row_ptr), _ptr(c.row_spot), _ptr(c.row_perm), _ptr(c.col_val), _ptr(size), N, D,
+                                            c.nnz, theta_min, theta_max, int(max_iter), *(_ptr(t) for t in out), _ptr(info),
+                                            _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_gene_dispersion_sparse")
+    flags = int(info.item())
+    if flags & 1:
+        raise ValueError(f"{who}: a stored value is negative, not an integer or >= 2^24 (counts expected)")
+    if flags & 2:
+        raise ValueError(f"{who}: size must be >= 0 and finite, and positive wherever a spot has a stored count")
+    return tuple(out)
+
+
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
     """How ``poisson_nsf_sparse`` covers a shape (gpz_poisson_nsf_sparse_plan, a host-only query: no device needed):
     ``gene_chunk`` (non-zeros of a gene row per wave of the gene pass), ``spot_chunk`` (the same for a spot's column; 0:

@@ -600,6 +600,22 @@ def _whole_counts_only(counts, who):
     return counts
 
 
+def _gene_sizes(c, size_factors, who):
+    """The (N,) fp64 sizes of the spots on the counts' device: None = the spots' total counts, else an (N,) or (N, 1) array
+    of positive finite values."""
+    N = c.shape[1]
+    if size_factors is None:
+        return _spot_totals_tensor(c)
+    import numpy as np
+    sf = size_factors.detach() if isinstance(size_factors, torch.Tensor) else torch.as_tensor(np.asarray(size_factors))
+    if tuple(sf.shape) not in ((N,), (N, 1)):
+        raise ValueError(f"{who}: size_factors of shape {tuple(sf.shape)} for {N} spots ((N,) or (N, 1) expected)")
+    size = sf.reshape(-1).to(device=c.device, dtype=torch.float64)
+    if not bool((size > 0).all() & torch.isfinite(size).all()):
+        raise ValueError(f"{who}: size_factors must be positive and finite")
+    return size
+
+
 _DEVIANCE_FAMILIES = {"poisson": 0, "binomial": 1}
 
 
@@ -616,20 +632,54 @@ def gene_deviance(counts, family="poisson", size_factors=None):
     c = _whole_counts_only(counts, "gene_deviance")
     if family not in _DEVIANCE_FAMILIES:
         raise ValueError(f"gene_deviance: family {family!r} unknown ('poisson', 'binomial')")
-    N = c.shape[1]
-    if size_factors is None:
-        size = _spot_totals_tensor(c)
-    else:
-        if family == "binomial":
-            raise ValueError("gene_deviance: the binomial deviance takes the spots' total counts as sizes (size_factors=None)")
-        import numpy as np
-        sf = size_factors.detach() if isinstance(size_factors, torch.Tensor) else torch.as_tensor(np.asarray(size_factors))
-        if tuple(sf.shape) not in ((N,), (N, 1)):
-            raise ValueError(f"gene_deviance: size_factors of shape {tuple(sf.shape)} for {N} spots ((N,) or (N, 1) expected)")
-        size = sf.reshape(-1).to(device=c.device, dtype=torch.float64)
-        if not bool((size > 0).all() & torch.isfinite(size).all()):
-            raise ValueError("gene_deviance: size_factors must be positive and finite")
+    if size_factors is not None and family == "binomial":
+        raise ValueError("gene_deviance: the binomial deviance takes the spots' total counts as sizes (size_factors=None)")
+    size = _gene_sizes(c, size_factors, "gene_deviance")
     return ops.gene_deviance_sparse(c, size.contiguous(), _DEVIANCE_FAMILIES[family])[2]
+
+
+class GeneDispersion(NamedTuple):
+    """``gene_dispersion``: the negative-binomial fit of every gene under the constant-rate null, (D,) tensors on the counts'
+    device.  ``theta`` fp64: the maximum-likelihood inverse dispersion, +inf where the gene shows no overdispersion below the
+    range's upper end, NaN for a gene without counts; ``loglik`` = ``poisson_loglik`` + gain at that theta; ``lr`` = 2 gain,
+    the likelihood-ratio statistic against Poisson; ``pvalue`` = erfc(sqrt(gain)) / 2, its tail under the boundary mixture
+    (chi2_0 + chi2_1) / 2 (1 at the Poisson limit); ``status`` int32 (0 interior root, 1 Poisson limit, 2 at the range's
+    lower end, 3 not converged, 4 no counts) and ``iterations`` int32 (score evaluations after the two at the ends)."""
+    theta: torch.Tensor
+    loglik: torch.Tensor
+    poisson_loglik: torch.Tensor
+    lr: torch.Tensor
+    pvalue: torch.Tensor
+    status: torch.Tensor
+    iterations: torch.Tensor
+
+
+def gene_dispersion(counts, size_factors=None, *, theta_range=(1e-4, 1e6), max_iter=50):
+    """The gene-wise negative-binomial inverse dispersion of a whole ``SparseCounts`` by maximum likelihood, on the counts'
+    device (``ops.gene_dispersion_sparse``) -- what edgeR, DESeq2 and glmGamPoi's ``overdispersion_mle`` compute on the host,
+    with the rate of gene d held at the null of ``gene_deviance``: mu_dn = p_d size_n, p_d = sum_n y_dn / sum_n size_n.  It
+    answers which genes are overdispersed at all (``pvalue``, ``lr``: is ``likelihood="nb"`` worth its cost over Poisson?)
+    and where theta can start for each gene (``theta0=`` of the count models).  The null absorbs all biological variation
+    of a gene into its dispersion, so ``theta`` is a lower-biased start for a factor model's theta, not an estimate of it.
+
+    ``size_factors``: None = the spots' total counts, else an (N,) or (N, 1) array of positive values.  ``theta_range``:
+    the interval theta is sought in.  ``max_iter`` <= 200: score evaluations per gene.  Returns a ``GeneDispersion``.  A
+    ``SparseExpression``, ``counts.T`` or a view raises TypeError."""
+    import math
+    from . import ops
+    c = _whole_counts_only(counts, "gene_dispersion")
+    try:
+        lo, hi = (float(v) for v in theta_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"gene_dispersion: theta_range {theta_range!r} must be (theta_min, theta_max)") from None
+    if not (0.0 < lo < hi and math.isfinite(hi)):
+        raise ValueError(f"gene_dispersion: theta_range ({lo}, {hi}) unsupported (0 < theta_min < theta_max, both finite)")
+    size = _gene_sizes(c, size_factors, "gene_dispersion")
+    theta, gain, pl, status, iterations = ops.gene_dispersion_sparse(c, size.contiguous(), lo, hi, max_iter)
+    pvalue = 0.5 * torch.erfc(torch.sqrt(gain.clamp_min(0.0)))
+    pvalue = torch.where(status == 1, torch.ones_like(pvalue), pvalue)            # theta = inf: the chi2_0 half, all of it
+    pvalue = torch.where(status == 4, torch.full_like(pvalue, float("nan")), pvalue)
+    return GeneDispersion(theta, pl + gain, pl, 2.0 * gain, pvalue, status, iterations)
 
 
 class GeneAutocorr(NamedTuple):
@@ -729,7 +779,8 @@ def rank_genes(counts, by="deviance", *, coords=None, nfeat=None, **kw):
     """``(order, score)`` of the genes of a whole ``SparseCounts``: ``order`` int64 (D,), or (nfeat,), in decreasing score
     (NaN last, ties in gene order), ``score`` fp64 aligned with it; ``counts.select_genes(order)`` is then the reference's
     ``ad[:, :nfeat]`` of a data set sorted by importance.  ``by``: "deviance" (``gene_deviance``, Poisson),
-    "binomial_deviance", or "moran" (``gene_autocorr`` of ``log_normalize(counts, center=False)`` over ``coords``).  Extra
+    "binomial_deviance", "moran" (``gene_autocorr`` of ``log_normalize(counts, center=False)`` over ``coords``), or
+    "overdispersion" (``gene_dispersion(counts).lr``, the likelihood-ratio statistic of NB against Poisson).  Extra
     keywords go to the scorer."""
     if by == "deviance":
         score = gene_deviance(counts, "poisson", **kw)
@@ -740,8 +791,10 @@ def rank_genes(counts, by="deviance", *, coords=None, nfeat=None, **kw):
         if coords is None and kw.get("graph") is None:
             raise ValueError("rank_genes: by='moran' needs coords (or graph=)")
         score = gene_autocorr(log_normalize(counts, center=False), coords, **kw).I
+    elif by == "overdispersion":
+        score = gene_dispersion(counts, **kw).lr
     else:
-        raise ValueError(f"rank_genes: by={by!r} unknown ('deviance', 'binomial_deviance', 'moran')")
+        raise ValueError(f"rank_genes: by={by!r} unknown ('deviance', 'binomial_deviance', 'moran', 'overdispersion')")
     order = _rank_order(score, nfeat)
     return order, score[order]
 

@@ -62,7 +62,10 @@
  * gpz_gene_deviance_sparse and gpz_gene_morans_i_sparse, each with its host-only *_plan query -- two per-gene scores of
  * counts stored as their non-zeros, for ranking and selecting genes ahead of a fit: the Poisson / binomial deviance against a
  * constant-rate null (scry's devianceFeatureSelection) and Moran's I over the spots' K-neighbour graph (squidpy's
- * spatial_autocorr, one gene per column); their scratch is `partials`, sized by the plan query's partials_bytes.
+ * spatial_autocorr, one gene per column); their scratch is `partials`, sized by the plan query's partials_bytes;
+ * gpz_gene_dispersion_sparse and the host-only gpz_gene_dispersion_sparse_plan -- the maximum-likelihood negative-binomial
+ * inverse dispersion of every gene of the same stored counts under the constant-rate null, with its gain over Poisson: which
+ * genes are overdispersed, and where theta starts (edgeR / DESeq2 / glmGamPoi's gene-wise estimate); scratch `partials` again.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -446,6 +449,40 @@ int gpz_gene_morans_i_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, 
 int gpz_gene_morans_i_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
                              const int64_t* nbr, int64_t N, int64_t D, int64_t nnz, int32_t K, double* I, int32_t* info,
                              void* partials, size_t partials_bytes, void* stream);
+
+/* Gene-wise negative-binomial inverse dispersion by maximum likelihood (csrc/gene_dispersion.hip), over the same by-gene
+ * arrays as the two entries above, fp64 throughout.  Null of gene d: mu_n = p_d size_n, p_d = sum_n y_dn / sum_n size_n (the
+ * null of gpz_gene_deviance_sparse and gpz_nb_deviance; the rate's MLE for constant sizes, a convention otherwise).  theta[d]
+ * maximises l_d(theta) = sum_n log NB(y_dn | mu_n, theta) over [theta_min, theta_max]: the root in t = log theta of
+ *   S_d(t) = sum_{all n} theta h(mu_n / theta) + sum_{stored} theta sum_{k < y} (mu_n - k) / ((theta + k)(theta + mu_n)),
+ *   h(x) = x / (1 + x) - log1p(x),
+ * found by Newton steps in t kept inside a sign-changing bracket (bisection otherwise), from the moment estimate
+ *   theta_0 = sum_n mu_n^2 / (sum_n (y_n - mu_n)^2 - sum_n y_n), theta_max where the denominator is <= 0, clipped into the
+ * range; it stops at a step or bracket <= tol_t (the plan reports it: 1e-9) or after max_iter <= 200 score evaluations.
+ *   theta[d]           the root (status 0); +inf when S_d(log theta_max) >= 0 (1: no overdispersion in range); theta_min when
+ *                      S_d(log theta_min) <= 0 (2); the last iterate, theta_0 for max_iter = 0, when not converged (3);
+ *                      NaN for a gene without counts (4)
+ *   gain[d]            l_d(theta[d]) - l_d(inf) = sum_{all n} [mu_n - theta log1p(mu_n / theta)]
+ *                      + sum_{stored} sum_{k < y} log((theta + k) / (theta + mu_n)); exactly 0 at status 1 and 4
+ *   poisson_loglik[d]  l_d(inf) = sum_{stored} [y log mu_n - lgamma(y + 1)] - sum_n y_dn; 0 at status 4
+ *   status[d], iterations[d]  int32; iterations counts the score evaluations after the two at the ends of the range
+ * Every term is evaluated without cancellation inside it (series for small mu / theta, explicit sums over k below 16 and the
+ * combined difference of the psi / lgamma asymptotic series above: csrc/gene_dispersion.hip).  size (N,) fp64 >= 0 and > 0
+ * wherever a spot has a stored count; a spot of size 0 contributes nothing.  When all sizes are equal (found once per call)
+ * the all-spot sums are N f(x) and no sweep over the spots is made.  A stored value that is negative, not an integer or
+ * >= 2^24 is not used and sets bit 0 of info[0] (device int32); a negative or non-finite size, or a stored count at a spot
+ * of size 0, is not used and sets bit 1.  Every accumulation is fp64 in a fixed order with no atomics on values: two calls
+ * agree bit for bit.  The scratch is `partials` (four fp64 words, whatever the shape), sized by the host-only plan query,
+ * which also reports gene_chunk, workgroups and tol_t (any out pointer may be NULL); it need not be cleared.  Nothing of
+ * D x N or nnz elements is allocated.  N, D, nnz < 2^31; partials 16-byte aligned.  Argument errors (null pointers, bad
+ * extents, a range that is not 0 < theta_min < theta_max finite, max_iter outside [0, 200], misaligned or short partials)
+ * return -1 before any launch with the reason in gpz_last_error. */
+int gpz_gene_dispersion_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t* gene_chunk, int32_t* workgroups,
+                                    double* tol_t, int64_t* partials_bytes);
+int gpz_gene_dispersion_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                               const double* size, int64_t N, int64_t D, int64_t nnz, double theta_min, double theta_max,
+                               int32_t max_iter, double* theta, double* gain, double* poisson_loglik, int32_t* status,
+                               int32_t* iterations, int32_t* info, void* partials, size_t partials_bytes, void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
