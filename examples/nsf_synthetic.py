@@ -11,7 +11,8 @@ cent dense) and fits through ``SparseCounts``: the same model and the same loop,
 
 ``--holdout FRAC`` holds that fraction of the spots out (``train_val_split``, the split of the reference's
 ``anndata_to_train_val``), fits on the rest and prints the Poisson deviance of the held-out spots under the predictive mean
-rate and the share of the null model's deviance it explains (``model.deviance``); it works with ``--sparse-counts`` too.
+rate and the share of the null model's deviance it explains (``model.deviance``); it works with ``--sparse-counts`` too.  With ``--residual-autocorr`` it prints the ten genes with the largest
+``z`` of ``model.residual_autocorr`` after the fit: where spatial structure is left in what the model did not explain.
 
 ``--likelihood nb`` draws overdispersed (gamma-Poisson) counts with a known inverse dispersion per gene, fits the model with
 ``likelihood="nb"`` (the fused negative-binomial step) and prints the fitted theta next to the true one; with ``--holdout``
@@ -69,6 +70,8 @@ def main():
     ap.add_argument("--theta0", default="10", metavar="VALUE|mle",
                     help="nb: where every gene's theta starts; mle: each gene's own maximum-likelihood theta under the "
                          "constant-rate null (gene_dispersion; needs --sparse-counts)")
+    ap.add_argument("--residual-autocorr", action="store_true",
+                    help="after the fit, print the ten genes whose residuals are most spatially autocorrelated")
     a = ap.parse_args()
     if a.theta0 == "mle" and (a.likelihood != "nb" or a.sparse_counts is None):
         ap.error("--theta0 mle needs --likelihood nb and --sparse-counts (gene_dispersion reads a SparseCounts)")
@@ -163,6 +166,19 @@ def main():
                   "(%d of %d genes gain)" % (float(nb.total), float(nb.mean), float(nb.explained),
                                              float(nb.loglik - nb.poisson_loglik), int((gain > 0).sum()), gain.numel()))
             assert float(nb.total) == float(nb.total) and abs(float(nb.loglik)) != float("inf")
+    if a.residual_autocorr:
+        # is spatial structure left in what the fit did not explain, and in which genes: Moran's I of each gene's Pearson
+        # residuals over the fitted spots' 6-nearest-neighbour graph (z ranks genes; it is not a calibrated test)
+        t0 = time.perf_counter()
+        ra = model.residual_autocorr(X, Y)
+        top = torch.argsort(ra.z, descending=True)[:10].cpu()
+        dt = time.perf_counter() - t0
+        print("residual autocorrelation (Pearson, family %s) of %d genes over %d spots  [%.1f ms]; expected I %.2e, sd %.2e"
+              % (a.likelihood, a.genes, X.shape[0], 1e3 * dt, float(ra.expected), float(ra.variance.sqrt())))
+        for i in top.tolist():
+            print("  gene %5d  I %+.4f  z %+7.2f  residual mean %+.3f  variance %.3f"
+                  % (i, float(ra.I[i]), float(ra.z[i]), float(ra.residual_mean[i]), float(ra.residual_var[i])))
+        assert bool(torch.isfinite(ra.I).all())
 
 
 if __name__ == "__main__":

@@ -102,6 +102,16 @@ _SIGNATURES = {
                                                   C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "gpz_gene_dispersion_sparse": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] * 3 + [C.c_double, C.c_double, C.c_int32] +
                                    [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_residual_morans_i_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 5 + [C.POINTER(C.c_int64)]),
+    "gpz_count_residuals": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 2 +
+                            [C.c_size_t, C.c_void_p]),
+    "gpz_count_residuals_sparse": (C.c_int, [C.c_void_p] * 10 + [C.c_int64] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 2 +
+                                   [C.c_size_t, C.c_void_p]),
+    "gpz_residual_morans_i": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] * 3 + [C.c_int32] * 5 + [C.c_int64] + [C.c_void_p] * 5 +
+                              [C.c_size_t, C.c_void_p]),
+    "gpz_residual_morans_i_sparse": (C.c_int, [C.c_void_p] * 11 + [C.c_int64] * 4 + [C.c_int32] * 5 + [C.c_int64] +
+                                     [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "gpz_nb_nsf_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6),
     "gpz_nb_nsf_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),

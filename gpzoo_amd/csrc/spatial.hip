@@ -22,6 +22,7 @@
 // tile is skipped only when the bound is STRICTLY above the lane's K-th best (an equal d^2 with a lower index can enter).
 // Every sum of the Moran statistic is taken in a fixed order (no floating-point atomics): two calls agree bit for bit.
 #include "common.h"
+#include "moran_pass.h"
 
 #include <math.h>
 
@@ -326,9 +327,10 @@ MiPlan mi_plan(int64_t N, int64_t L, void* ws) {
   return p;
 }
 
-// Block (chunk, column tile): each thread sums its rows in order, then row slot 0 adds the slots in order.
+// Block (chunk, column tile): each thread sums its rows in order, then row slot 0 adds the slots in order.  V holds N rows
+// of ld values each, of which the first L are the columns (ld = L for gpz_morans_i; a residual slab is wider).
 template <typename T, bool TERMS>
-__global__ __launch_bounds__(MI_THREADS) void mi_rows(const T* __restrict__ V, int64_t N, int64_t L, int cw,
+__global__ __launch_bounds__(MI_THREADS) void mi_rows(const T* __restrict__ V, int64_t N, int64_t L, int64_t ld, int cw,
                                                       const int64_t* __restrict__ nbr, int K, const double* __restrict__ mean,
                                                       double* __restrict__ part, int32_t* __restrict__ info) {
   __shared__ double red[2][MI_THREADS];
@@ -340,7 +342,7 @@ __global__ __launch_bounds__(MI_THREADS) void mi_rows(const T* __restrict__ V, i
     const double ref = TERMS ? mean[l] : double(V[l]);
     const double w = 1.0 / K;
     for (int64_t i = r0 + slot; i < r1; i += slots) {
-      const double z = double(V[i * L + l]) - ref;
+      const double z = double(V[i * ld + l]) - ref;
       if (!TERMS) {
         a += z;
         continue;
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(MI_THREADS) void mi_rows(const T* __restrict__ V, i
           *info = 1;
           continue;
         }
-        lag += double(V[j * L + l]) - ref;
+        lag += double(V[j * ld + l]) - ref;
       }
       a += z * (lag * w);
       b += z * z;
@@ -377,10 +379,12 @@ __global__ __launch_bounds__(MI_THREADS) void mi_rows(const T* __restrict__ V, i
 }
 
 // Block = column: the chunks' partials in a fixed order (strided per thread, then a fixed tree).  TERMS == false: the
-// mean (first value + shifted sum / N); TERMS == true: I = numerator / denominator (0 / 0 = NaN: a constant column).
+// mean (first value + shifted sum / N); TERMS == true: I = numerator / denominator (0 / 0 = NaN: a constant column), and
+// the column's variance, denominator / N, where the caller asks for it (var, nullable).
 template <typename T, bool TERMS>
 __global__ __launch_bounds__(MI_THREADS) void mi_final(const double* __restrict__ part, int64_t chunks, int64_t L, int64_t N,
-                                                       const T* __restrict__ V, double* __restrict__ out) {
+                                                       const T* __restrict__ V, double* __restrict__ out,
+                                                       double* __restrict__ var) {
   __shared__ double red[2][MI_THREADS];
   const int64_t l = blockIdx.x;
   double a = 0.0, b = 0.0;
@@ -403,22 +407,27 @@ __global__ __launch_bounds__(MI_THREADS) void mi_final(const double* __restrict_
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) out[l] = TERMS ? red[0][0] / red[1][0] : double(V[l]) + red[0][0] / double(N);
+  if (threadIdx.x == 0) {
+    out[l] = TERMS ? red[0][0] / red[1][0] : double(V[l]) + red[0][0] / double(N);
+    if (TERMS && var) var[l] = red[1][0] / double(N);
+  }
 }
 
+// The four launches over the first L columns of V (N rows of ld values); the means are left in pl.mean.
 template <typename T>
-int mi_run(const void* values, int64_t N, int64_t L, const int64_t* nbr, int K, double* I, int32_t* info, const MiPlan& pl,
-           hipStream_t s) {
+int mi_run(const void* values, int64_t N, int64_t L, int64_t ld, const int64_t* nbr, int K, double* I, double* var,
+           int32_t* info, const MiPlan& pl, hipStream_t s) {
   const T* V = static_cast<const T*>(values);
   const int cw = mi_cw(L);
   const dim3 rows(unsigned(pl.chunks), unsigned((L + cw - 1) / cw)), block(MI_THREADS);
-  hipLaunchKernelGGL((mi_rows<T, false>), rows, block, 0, s, V, N, L, cw, nbr, K, pl.mean, pl.part, info);
+  hipLaunchKernelGGL((mi_rows<T, false>), rows, block, 0, s, V, N, L, ld, cw, nbr, K, pl.mean, pl.part, info);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((mi_final<T, false>), dim3(unsigned(L)), block, 0, s, pl.part, pl.chunks, L, N, V, pl.mean);
+  hipLaunchKernelGGL((mi_final<T, false>), dim3(unsigned(L)), block, 0, s, pl.part, pl.chunks, L, N, V, pl.mean,
+                     static_cast<double*>(nullptr));
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((mi_rows<T, true>), rows, block, 0, s, V, N, L, cw, nbr, K, pl.mean, pl.part, info);
+  hipLaunchKernelGGL((mi_rows<T, true>), rows, block, 0, s, V, N, L, ld, cw, nbr, K, pl.mean, pl.part, info);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((mi_final<T, true>), dim3(unsigned(L)), block, 0, s, pl.part, pl.chunks, L, N, V, I);
+  hipLaunchKernelGGL((mi_final<T, true>), dim3(unsigned(L)), block, 0, s, pl.part, pl.chunks, L, N, V, I, var);
   GPZ_LAUNCH_OK();
   return 0;
 }
@@ -440,6 +449,17 @@ int mi_check_args(int64_t N, int64_t L, int32_t K, int32_t dtype) {
 }
 
 }  // namespace
+
+// moran_pass.h: the same four launches over a residual slab, with the column means and variances as outputs
+size_t moran_slab_bytes(int64_t B, int64_t cols) { return mi_plan(B, cols, nullptr).bytes; }
+
+int moran_slab_run(const float* slab, int64_t B, int64_t cols, int64_t ld, const int64_t* nbr, int K, double* I, double* mean,
+                   double* var, int32_t* info, void* scratch, hipStream_t s) {
+  MiPlan pl = mi_plan(B, cols, scratch);
+  pl.mean = mean;
+  return mi_run<float>(slab, B, cols, ld, nbr, K, I, var, info, pl, s);
+}
+
 }  // namespace gpz
 
 using namespace gpz;
@@ -496,6 +516,6 @@ extern "C" int gpz_morans_i(const void* values, int64_t N, int64_t L, int32_t dt
   GPZ_REQUIRE(ws_bytes >= pl.bytes, "gpz_morans_i: workspace of %zu bytes, %zu needed", ws_bytes, pl.bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
   GPZ_HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t), s));
-  return dtype == GPZ_F32 ? mi_run<float>(values, N, L, nbr, K, I, info, pl, s)
-                          : mi_run<double>(values, N, L, nbr, K, I, info, pl, s);
+  return dtype == GPZ_F32 ? mi_run<float>(values, N, L, L, nbr, K, I, nullptr, info, pl, s)
+                          : mi_run<double>(values, N, L, L, nbr, K, I, nullptr, info, pl, s);
 }

@@ -775,6 +775,91 @@ def _hybrid_spots(n_fitted, n_spots, idx, V, who):
                          "other spots cannot be scored" + (" (V= does not change that)" if V is not None else ""))
 
 
+class ResidualAutocorr(NamedTuple):
+    """What ``residual_autocorr`` returns; every tensor is fp64 and carries no graph.  ``I`` (D,): Moran's I of each gene's
+    residuals over the spots' neighbour graph.  ``expected`` and ``variance``: 0-d, the moments of I under normality for that
+    graph (they depend on the graph alone).  ``z`` = (I - expected) / sqrt(variance) (D,).  ``residual_mean`` and
+    ``residual_var`` (D,): each gene's residual mean and variance over the spots -- near 0 and 1 for Pearson residuals of a
+    well-calibrated fit."""
+    I: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+    residual_mean: torch.Tensor
+    residual_var: torch.Tensor
+
+
+def _cat_factors(qF_list, W_list):
+    return (torch.cat([q.mean for q in qF_list], dim=0), torch.cat([q.scale for q in qF_list], dim=0),
+            torch.cat(list(W_list), dim=1))
+
+
+def residual_autocorr(qF_list, W_list, V_pos, y, nbr, *, theta_pos=None, kind="pearson", lognormal_mean=True, slab_genes=0):
+    """Is spatial structure left in what the model did not explain, and in which genes: Moran's I of every gene's residuals
+    under the predictive mean rate mu = V * sum_k W_k E_q[exp F_k] (as in ``poisson_deviance``) over the neighbour table
+    ``nbr`` (B, K) of the B scored spots -- the evidence for adding factors, shortening a length scale or moving a gene to
+    the spatial part of a hybrid.  ``kind``: "pearson", (y - mu) / sqrt(mu (1 + mu / theta)), or "deviance",
+    sign(y - mu) sqrt(unit deviance); ``theta_pos`` (D,) selects the negative binomial, None the Poisson family.  ``y``: dense
+    (D, B) counts or a whole ``SparseCounts``.  Neither the (D, B) rate nor the residuals are materialised
+    (``ops.residual_morans_i``).  Returns a ``ResidualAutocorr``.
+
+    ``z`` uses squidpy's normal approximation of I's moments under no autocorrelation and ignores the degrees of freedom
+    the fit used: it ranks genes, it is not a calibrated test."""
+    from . import ops
+    from .utilities import _moran_moments
+    with torch.no_grad():
+        mean, scale, W = _cat_factors(qF_list, W_list)
+        r = ops.residual_morans_i(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes)
+        expected, variance = _moran_moments(nbr.to(device=r["I"].device, dtype=torch.int64))
+        return ResidualAutocorr(I=r["I"], expected=expected, variance=variance, z=(r["I"] - expected) / torch.sqrt(variance),
+                                residual_mean=r["residual_mean"], residual_var=r["residual_var"])
+
+
+def count_residuals(qF_list, W_list, V_pos, y, genes, *, theta_pos=None, kind="pearson", lognormal_mean=True):
+    """(len(genes), B) fp32 residuals of the listed genes, gene-major like ``y``, under the rate of ``residual_autocorr``: one
+    gene's residual map for plotting.  ``genes``: gene indices in any order, repeats allowed."""
+    from . import ops
+    if genes is None:
+        raise ValueError("count_residuals: genes (a list of gene indices) needed; the full (D, B) array is what this avoids")
+    with torch.no_grad():
+        mean, scale, W = _cat_factors(qF_list, W_list)
+        return ops.count_residuals(mean, scale, W, V_pos, y, theta_pos, genes, kind, lognormal_mean).T.contiguous()
+
+
+class _ResidualScores:
+    """``residual_autocorr`` and ``residuals`` of the count models.  A model supplies ``_score_parts(X, idx, V, kwargs)`` ->
+    (qF_list, W_list, V_pos, Xb), the pieces its ``deviance`` assembles."""
+
+    def _residual_theta(self, kind, family, theta):
+        """The refusals that need no device, and the per-gene theta (None: Poisson) as ``deviance`` resolves it."""
+        if kind not in ("pearson", "deviance"):
+            raise ValueError(f'{type(self).__name__}.residual_autocorr: kind must be "pearson" or "deviance", got {kind!r}')
+        return _deviance_theta(self, self.sf.W if hasattr(self, "sf") else self.W, family, theta)
+
+    def residual_autocorr(self, X, y, idx=None, V=None, *, kind="pearson", family="model", theta=None, n_neighs=6, graph=None,
+                          lognormal_mean=True, **kwargs):
+        """Moran's I of every gene's residuals at ``X`` (or ``X[idx]``) over the scored spots' ``n_neighs``-nearest-neighbour
+        graph (``ops.spatial_knn``), or over ``graph=``, an (B, K) table: a ``ResidualAutocorr``.  ``y`` (D, B) dense or a
+        whole ``SparseCounts``; ``V`` as in ``deviance``.  ``family`` defaults to "model", unlike ``deviance``: residuals are
+        standardised by the model's own variance, so an NB fit is scored with its theta (``theta=`` overrides it, or scores
+        a Poisson fit under ``family="nb"``)."""
+        from . import ops
+        theta_pos = self._residual_theta(kind, family, theta)
+        with torch.no_grad():
+            qF, W, Vp, Xb = self._score_parts(X, idx, V, kwargs)
+            nbr = ops.spatial_knn(Xb, int(n_neighs)) if graph is None else torch.as_tensor(graph)
+            return residual_autocorr(qF, W, Vp, y, nbr, theta_pos=theta_pos, kind=kind, lognormal_mean=lognormal_mean)
+
+    def residuals(self, X, y, genes, idx=None, V=None, *, kind="pearson", family="model", theta=None, lognormal_mean=True,
+                  **kwargs):
+        """(len(genes), B) fp32 residuals of the listed genes at ``X`` (or ``X[idx]``): the rows ``residual_autocorr`` scores.
+        Arguments as there."""
+        theta_pos = self._residual_theta(kind, family, theta)
+        with torch.no_grad():
+            qF, W, Vp, Xb = self._score_parts(X, idx, V, kwargs)
+            return count_residuals(qF, W, Vp, y, genes, theta_pos=theta_pos, kind=kind, lognormal_mean=lognormal_mean)
+
+
 class PoissonFactorization(nn.Module):
     """softplus(W) @ exp(F): base of PNMF / NSF2 / the hybrids; reference likelihoods.py:39-53.
     ``likelihood="nb"`` (here and on every count model below): negative-binomial noise with the per-gene parameter
@@ -817,7 +902,7 @@ class PNMF(PoissonFactorization):
         return ll, qF, pF
 
 
-class NSF2(PoissonFactorization):
+class NSF2(PoissonFactorization, _ResidualScores):
     """Non-negative spatial factorisation over an SVGP prior; reference likelihoods.py:74-97."""
 
     def __init__(self, gp, y, L=10, likelihood="poisson", theta0=10.0):
@@ -859,8 +944,13 @@ class NSF2(PoissonFactorization):
             qF = self.prior(X=Xb, **kwargs)[0]
             return _deviance_of([qF], [torch.nn.functional.softplus(self.W)], Vp, theta_pos, y, lognormal_mean)
 
+    def _score_parts(self, X, idx, V, kwargs):
+        Xb = X if idx is None else X[idx]
+        Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+        return [self.prior(X=Xb, **kwargs)[0]], [torch.nn.functional.softplus(self.W)], Vp, Xb
 
-class NSF(nn.Module):
+
+class NSF(nn.Module, _ResidualScores):
     """Same model with W, V held directly; reference likelihoods.py:227-268."""
 
     def __init__(self, gp, y, L=10, likelihood="poisson", theta0=10.0):
@@ -904,6 +994,11 @@ class NSF(nn.Module):
             qF = self.gp(X=Xb, **kwargs)[0]
             return _deviance_of([qF], [torch.nn.functional.softplus(self.W)], Vp, theta_pos, y, lognormal_mean)
 
+    def _score_parts(self, X, idx, V, kwargs):
+        Xb = X if idx is None else X[idx]
+        Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+        return [self.gp(X=Xb, **kwargs)[0]], [torch.nn.functional.softplus(self.W)], Vp, Xb
+
 
 class MGGP_NSF(NSF):
     """NSF over a multi-group GP (groupsX is positional); reference likelihoods.py:341-374."""
@@ -944,8 +1039,16 @@ class MGGP_NSF(NSF):
             qF = self._gp(Xb, gb, False)[0]
             return _deviance_of([qF], [torch.nn.functional.softplus(self.W)], Vp, theta_pos, y, lognormal_mean)
 
+    def _score_parts(self, X, idx, V, kwargs):
+        groupsX = kwargs.get("groupsX")
+        if groupsX is None:
+            raise TypeError("MGGP_NSF.residual_autocorr and MGGP_NSF.residuals need groupsX=")
+        Xb, gb = (X, groupsX) if idx is None else (X[idx], groupsX[idx])
+        Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+        return [self._gp(Xb, gb, False)[0]], [torch.nn.functional.softplus(self.W)], Vp, Xb
 
-class Hybrid_NSF2(nn.Module):
+
+class Hybrid_NSF2(nn.Module, _ResidualScores):
     """Spatial (GP) + non-spatial (GaussianPrior) factors; reference likelihoods.py:100-164."""
 
     def __init__(self, gp, prior, y, L=10, T=10, likelihood="poisson", theta0=10.0):
@@ -997,6 +1100,15 @@ class Hybrid_NSF2(nn.Module):
             qF2 = (self.cf.prior() if idx is None else self.cf.prior.forward_batched(idx))[0]
             sp = torch.nn.functional.softplus
             return _deviance_of([qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], Vp, theta_pos, y, lognormal_mean)
+
+    def _score_parts(self, X, idx, V, kwargs):
+        Xb = X if idx is None else X[idx]
+        _hybrid_spots(self.V.shape[0], Xb.shape[0], idx, V, type(self).__name__)
+        Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+        qF1 = self.sf.prior(X=Xb, **kwargs)[0]
+        qF2 = (self.cf.prior() if idx is None else self.cf.prior.forward_batched(idx))[0]
+        sp = torch.nn.functional.softplus
+        return [qF1, qF2], [sp(self.sf.W), sp(self.cf.W)], Vp, Xb
 
 
 class Hybrid_NSF_Exact(Hybrid_NSF2):
@@ -1085,6 +1197,14 @@ class Hybrid_NSF(NSF):
             qF = self.gp(X=Xb, **kwargs)[0]
             qF2 = distributions.Normal(mF, torch.nn.functional.softplus(rs), validate_args=False)
             return _deviance_of([qF, qF2], [self.W, self.W2], Vp, theta_pos, y, lognormal_mean)
+
+    def _score_parts(self, X, idx, V, kwargs):
+        Xb = X if idx is None else X[idx]
+        _hybrid_spots(self.V.shape[0], Xb.shape[0], idx, V, type(self).__name__)
+        Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+        mF, rs = (self.mF, self.scale_qF) if idx is None else (self.mF[:, idx], self.scale_qF[:, idx])
+        qF2 = distributions.Normal(mF, torch.nn.functional.softplus(rs), validate_args=False)
+        return [self.gp(X=Xb, **kwargs)[0], qF2], [self.W, self.W2], Vp, Xb
 
 
 # --------------------------------------------------------------------------------------------

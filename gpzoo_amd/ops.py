@@ -1651,6 +1651,147 @@ def gene_dispersion_sparse(counts, size, theta_min: float = 1e-4, theta_max: flo
     return tuple(out)
 
 
+RESIDUAL_KINDS = {"pearson": 0, "deviance": 1}
+
+
+def residual_autocorr_plan(B: int, D: int, Lt: int, nnz: int = 0, slab_genes: int = 0) -> dict:
+    """How ``residual_morans_i`` covers B spots and D scored genes (gpz_residual_morans_i_plan, a host-only query: no device
+    needed): ``slab_genes`` (columns of the spot-major fp32 residual slab: the largest multiple of 64 within 256 MiB, at least
+    64 and at most D rounded up to 64, or the caller's positive multiple of 64) and ``n_slabs``; the residual pass's
+    ``spots_per_tile``, ``genes_per_block``, ``spot_slices`` and ``factors_padded``; ``gene_chunk`` (stored entries of a gene
+    row per wave, sparse counts); ``partials_bytes`` (the scratch, slab included)."""
+    lib = _lib.load()
+    sg, ns, nb = C.c_int64(), C.c_int64(), C.c_int64()
+    v = [C.c_int32() for _ in range(5)]
+    rc = lib.gpz_residual_morans_i_plan(int(B), int(D), int(Lt), int(nnz), int(slab_genes), C.byref(sg), C.byref(ns),
+                                        *(C.byref(x) for x in v), C.byref(nb))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(slab_genes=sg.value, n_slabs=ns.value, spots_per_tile=v[0].value, genes_per_block=v[1].value,
+                spot_slices=v[2].value, gene_chunk=v[3].value, factors_padded=v[4].value, partials_bytes=int(nb.value))
+
+
+def _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind):
+    """Everything the residual entries check before any device work, and their arguments in the entries' types."""
+    from .likelihoods import SparseCounts, TransposedCounts, _counts_expected
+    if isinstance(y, TransposedCounts):
+        raise TypeError(f"{who}: y is the .T (obs x feat) of a SparseCounts; pass the SparseCounts itself (genes x spots)")
+    _counts_expected(y, who)
+    sparse = isinstance(y, SparseCounts)
+    if sparse:
+        if y.base is not y:
+            raise TypeError(f"{who}: a view y[:, idx]; the whole data set is needed")
+    elif not isinstance(y, torch.Tensor):
+        raise TypeError(f"{who}: y must be a dense (D, B) tensor or a whole SparseCounts, got {type(y).__name__}")
+    if kind not in RESIDUAL_KINDS:
+        raise ValueError(f'{who}: kind must be "pearson" or "deviance", got {kind!r}')
+    if mean.dim() != 2:
+        raise ValueError(f"{who}: mean must be (Lt, B), got shape {tuple(mean.shape)}")
+    Lt, B = mean.shape
+    D = y.shape[0]
+    if (tuple(y.shape) != (D, B) or scale.shape != (Lt, B) or W_pos.shape != (D, Lt) or V_pos.shape != (B,)
+            or (theta_pos is not None and theta_pos.shape != (D,))):
+        raise ValueError(f"{who}: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, W {tuple(W_pos.shape)}, "
+                         f"V {tuple(V_pos.shape)}" + ("" if theta_pos is None else f", theta {tuple(theta_pos.shape)}")
+                         + " do not fit together")
+    g = None
+    if genes is not None:
+        g = genes.detach() if isinstance(genes, torch.Tensor) else torch.as_tensor(genes)
+        if g.dim() != 1 or g.numel() < 1 or g.is_floating_point() or g.dtype == torch.bool:
+            raise ValueError(f"{who}: genes must be a non-empty 1-D list of gene indices")
+        if bool(((g < 0) | (g >= D)).any()):
+            raise IndexError(f"{who}: a gene index lies outside [0, {D})")
+    _need_cuda(mean, scale, W_pos, V_pos, theta_pos, None if sparse else y)
+    dev = _same_device(mean, scale, W_pos, V_pos, theta_pos, None if sparse else y)
+    if sparse and y.device != dev:
+        raise RuntimeError(f"gpzoo_amd: the counts live on {y.device}, the model on {dev}: move them with counts.to(device)")
+    f32 = torch.float32
+    prep = lambda t: None if t is None else t.detach().to(f32).contiguous()  # noqa: E731
+    mean, scale, W_pos, V_pos, theta_pos = prep(mean), prep(scale), prep(W_pos), prep(V_pos), prep(theta_pos)
+    if not sparse:
+        y = prep(y)
+    if g is not None:
+        g = g.to(device=dev, dtype=torch.int32).contiguous()
+    G = D if g is None else int(g.numel())
+    return dict(mean=mean, scale=scale, W=W_pos, V=V_pos, theta=theta_pos, y=y, genes=g, sparse=sparse, dev=dev, B=B, D=D,
+                G=G, Lt=Lt, nnz=y.nnz if sparse else 0, family=int(theta_pos is not None), kind=RESIDUAL_KINDS[kind])
+
+
+def _residual_inputs(a):
+    """The leading pointer arguments of the four residual entries."""
+    head = [_ptr(a[k]) for k in ("mean", "scale", "W", "V", "theta")]
+    y = a["y"]
+    if a["sparse"]:
+        return head + [_ptr(y.row_ptr), _ptr(y.row_spot), _ptr(y.row_perm), _ptr(y.col_val), _ptr(a["genes"])]
+    return head + [_ptr(y), _ptr(a["genes"])]
+
+
+def count_residuals(mean, scale, W_pos, V_pos, y, theta_pos=None, genes=None, kind="pearson", lognormal_mean: bool = True):
+    """(B, G) fp32 residuals, spot-major, of the counts under the predictive mean rate mu = V W m of ``poisson_deviance``
+    (gpz_count_residuals / gpz_count_residuals_sparse).  ``kind="pearson"``: (y - mu) / sqrt(mu (1 + mu / theta));
+    ``"deviance"``: sign(y - mu) sqrt(unit deviance).  ``theta_pos`` (D,) selects the negative binomial, None the Poisson
+    family.  ``genes``: a list of gene indices in any order, repeats allowed (column g is gene ``genes[g]``), or None for all.
+    ``y``: dense (D, B), or a whole ``SparseCounts`` (the same bits as on its dense array)."""
+    who = "count_residuals"
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
+    lib = _lib.load()
+    nb = residual_autocorr_plan(a["B"], a["G"], a["Lt"], a["nnz"], 64)["partials_bytes"]
+    out = torch.empty((a["B"], a["G"]), dtype=torch.float32, device=a["dev"])
+    tail = [a["Lt"], a["family"], a["kind"], int(bool(lognormal_mean)), _ptr(out)]
+    with torch.cuda.device(a["dev"]):
+        ws = _workspace(a["dev"], nb)
+        if a["sparse"]:
+            rc = lib.gpz_count_residuals_sparse(*_residual_inputs(a), a["B"], a["D"], a["nnz"], a["G"], *tail, _ptr(ws), ws.numel(),
+                                                _stream(a["dev"]))
+        else:
+            rc = lib.gpz_count_residuals(*_residual_inputs(a), a["B"], a["D"], a["G"], *tail, _ptr(ws), ws.numel(),
+                                         _stream(a["dev"]))
+    _lib.check(rc, "gpz_count_residuals")
+    return out
+
+
+def residual_morans_i(mean, scale, W_pos, V_pos, y, nbr, theta_pos=None, genes=None, kind="pearson",
+                      lognormal_mean: bool = True, slab_genes: int = 0) -> dict:
+    """Moran's I of every gene's residuals (``count_residuals``' arguments) over the neighbour table nbr (B, K) int64 of
+    distinct neighbours, 1 <= K <= 32, with weights 1 / K (gpz_residual_morans_i / gpz_residual_morans_i_sparse): a dict of
+    fp64 (G,) tensors ``I``, ``residual_mean`` and ``residual_var`` (sum z^2 / B).  The genes are taken in slabs of
+    ``slab_genes`` columns (0: ``residual_autocorr_plan``'s choice); neither the (D, B) rate nor the (D, B) residuals exist.
+    Sums in a fixed order: repeated calls agree bit for bit.  A table entry outside [0, B) or naming its own row raises
+    ValueError (checked on the device; one synchronisation)."""
+    who = "residual_morans_i"
+    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
+        raise ValueError(f"{who}: nbr must be a (B, K) integer table")
+    K = int(nbr.shape[1])
+    if not 1 <= K <= 32:
+        raise ValueError(f"{who}: K = {K} neighbours unsupported (1..32)")
+    if int(slab_genes) != slab_genes or int(slab_genes) < 0 or int(slab_genes) % 64:
+        raise ValueError(f"{who}: slab_genes = {slab_genes!r} is not a positive multiple of 64 (or 0: the plan's choice)")
+    if nbr.shape[0] != mean.shape[-1]:
+        raise ValueError(f"{who}: nbr {tuple(nbr.shape)} for {mean.shape[-1]} spots")
+    if K >= nbr.shape[0]:
+        raise ValueError(f"{who}: {K} neighbours of {nbr.shape[0]} spots (K < B needed)")
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
+    lib = _lib.load()
+    dev, G = a["dev"], a["G"]
+    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
+    nb = residual_autocorr_plan(a["B"], G, a["Lt"], a["nnz"], int(slab_genes))["partials_bytes"]
+    out = [torch.empty(G, dtype=torch.float64, device=dev) for _ in range(3)]
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    tail = [a["Lt"], K, a["family"], a["kind"], int(bool(lognormal_mean)), int(slab_genes), *(_ptr(t) for t in out), _ptr(info)]
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nb)
+        if a["sparse"]:
+            rc = lib.gpz_residual_morans_i_sparse(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], a["nnz"], G, *tail, _ptr(ws),
+                                                  ws.numel(), _stream(dev))
+        else:
+            rc = lib.gpz_residual_morans_i(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], G, *tail, _ptr(ws), ws.numel(),
+                                           _stream(dev))
+    _lib.check(rc, "gpz_residual_morans_i")
+    if int(info.item()) != 0:
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
+    return dict(I=out[0], residual_mean=out[1], residual_var=out[2])
+
+
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
     """How ``poisson_nsf_sparse`` covers a shape (gpz_poisson_nsf_sparse_plan, a host-only query: no device needed):
     ``gene_chunk`` (non-zeros of a gene row per wave of the gene pass), ``spot_chunk`` (the same for a spot's column; 0:

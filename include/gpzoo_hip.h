@@ -65,7 +65,11 @@
  * spatial_autocorr, one gene per column); their scratch is `partials`, sized by the plan query's partials_bytes;
  * gpz_gene_dispersion_sparse and the host-only gpz_gene_dispersion_sparse_plan -- the maximum-likelihood negative-binomial
  * inverse dispersion of every gene of the same stored counts under the constant-rate null, with its gain over Poisson: which
- * genes are overdispersed, and where theta starts (edgeR / DESeq2 / glmGamPoi's gene-wise estimate); scratch `partials` again.
+ * genes are overdispersed, and where theta starts (edgeR / DESeq2 / glmGamPoi's gene-wise estimate); scratch `partials` again;
+ * gpz_count_residuals, gpz_count_residuals_sparse, gpz_residual_morans_i, gpz_residual_morans_i_sparse and the host-only
+ * gpz_residual_morans_i_plan -- Pearson or deviance residuals of counts under the predictive mean rate of a fitted count
+ * model, and Moran's I of every gene's residuals over the spots' K-neighbour graph (is spatial structure left in what the
+ * model did not explain, and in which genes), dense counts or counts stored as their non-zeros; scratch `partials` again.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -483,6 +487,54 @@ int gpz_gene_dispersion_sparse(const int64_t* row_ptr, const int32_t* row_spot, 
                                const double* size, int64_t N, int64_t D, int64_t nnz, double theta_min, double theta_max,
                                int32_t max_iter, double* theta, double* gain, double* poisson_loglik, int32_t* status,
                                int32_t* iterations, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+
+/* Residuals of counts under the predictive mean rate of a fitted count model, and Moran's I of every gene's residuals
+ * (csrc/residual.hip).  With m = exp(mean + scale^2 / 2) (lognormal_mean != 0; exp(mean) otherwise) the rate is
+ * mu[d,n] = V[n] sum_l W[d,l] m[l,n]; mean, scale (Lt, B), W (D, Lt), V (B,), theta (D,) (family 1; may be NULL for family 0).
+ *   kind 0, Pearson:   r = (y - mu) / sqrt(mu (1 + mu / theta)); family 0 (Poisson): (y - mu) / sqrt(mu)
+ *   kind 1, deviance:  r = sign(y - mu) sqrt(max(d, 0)), d = 2 (y log(y / mu) - (y - mu)) (Poisson, 2 mu at y = 0) or
+ *                      d = 2 [y log(y / mu) - (y + theta) log1p((y - mu) / (mu + theta))] (family 1, negative binomial), in the
+ *                      cancellation-free forms of gpz_poisson_deviance / gpz_nb_deviance
+ * genes: int32 (G,) indices into [0, D), in any order and with repeats, or NULL for all genes (then G = D); an index outside
+ * [0, D) gives a column of zeros.  Counts: y (D, B) dense, read once; or the by-gene arrays of a WHOLE data set stored as its
+ * non-zeros (row_ptr, row_spot, row_perm, col_val as in gpz_gene_deviance_sparse; B = its N spots).  The sparse entries fill
+ * every element with the zero-count residual (no counts are read) and then overwrite the stored entries, forming mu again at
+ * each one in the dense pass's arithmetic: they give the bits of the dense entries on the densified counts.
+ *   gpz_count_residuals*    out (B, G) fp32, spot-major: out[n * G + g] is the residual of listed gene g at spot n.
+ *   gpz_residual_morans_i*  per listed gene, fp64 (G,): I = sum_n z_n (1 / K) sum_k z_nbr[n,k] / sum_n z_n^2 with
+ *                           z = r - mean(r) (what gpz_morans_i gives for the column), res_mean = mean(r) and
+ *                           res_var = sum_n z_n^2 / B.  nbr int64 (B, K), distinct neighbours; an entry outside [0, B) or
+ *                           naming its own row is skipped and sets info[0] (device int32) to 1.  The genes are taken in
+ *                           slabs of slab_genes columns of fp32 residuals, spot-major, inside `partials`; slab_genes = 0 takes
+ *                           the plan's choice, the largest multiple of 64 with B * slab_genes * 4 bytes <= 256 MiB (at least
+ *                           64, at most G rounded up to 64 and 2^20); a positive multiple of 64 overrides it.
+ * Nothing of D x B or nnz elements is allocated.  fp32 element-wise work; every sum is fp64 in a fixed order, with no
+ * atomics: two calls agree bit for bit.  gpz_residual_morans_i_plan (host-only; any out pointer may be NULL; D = the number
+ * of scored genes) reports slab_genes, n_slabs, the tile shape and partials_bytes for the Moran entries; the residual
+ * entries need no more than the partials of the plan with slab_genes_wanted = 64.  `partials` need not be cleared.
+ * Limits, refused with -1 and the reason in gpz_last_error before any launch: 1 <= K <= 32, K < B < 2^31 (B < 2^27 with
+ * stored counts), D, G, nnz < 2^31, 1 <= Lt <= 64, partials 16-byte aligned and large enough, family and kind 0 or 1. */
+int gpz_residual_morans_i_plan(int64_t B, int64_t D, int32_t Lt, int64_t nnz, int64_t slab_genes_wanted, int64_t* slab_genes,
+                               int64_t* n_slabs, int32_t* spots_per_tile, int32_t* genes_per_block, int32_t* spot_slices,
+                               int32_t* gene_chunk, int32_t* factors_padded, int64_t* partials_bytes);
+int gpz_count_residuals(const float* mean, const float* scale, const float* W, const float* V, const float* theta, const float* y,
+                        const int32_t* genes, int64_t B, int64_t D, int64_t G, int32_t Lt, int32_t family, int32_t kind,
+                        int32_t lognormal_mean, float* out, void* partials, size_t partials_bytes, void* stream);
+int gpz_count_residuals_sparse(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                               const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                               const int32_t* genes, int64_t B, int64_t D, int64_t nnz, int64_t G, int32_t Lt, int32_t family,
+                               int32_t kind, int32_t lognormal_mean, float* out, void* partials, size_t partials_bytes,
+                               void* stream);
+int gpz_residual_morans_i(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                          const float* y, const int32_t* genes, const int64_t* nbr, int64_t B, int64_t D, int64_t G, int32_t Lt,
+                          int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean, int64_t slab_genes, double* I,
+                          double* res_mean, double* res_var, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+int gpz_residual_morans_i_sparse(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                                 const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                 const int32_t* genes, const int64_t* nbr, int64_t B, int64_t D, int64_t nnz, int64_t G,
+                                 int32_t Lt, int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean, int64_t slab_genes,
+                                 double* I, double* res_mean, double* res_var, int32_t* info, void* partials,
+                                 size_t partials_bytes, void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
