@@ -7,14 +7,17 @@ on synthetic counts, against the same model started from mu = 0 and random loadi
 
     PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30
                                                    --inducing-from {subset,kmeans} --mu-from {smooth,projection}
-                                                   --sparse-counts DENSITY [--select-genes NFEAT --rank-by {deviance,moran}]]
+                                                   --sparse-counts DENSITY [--select-genes NFEAT --rank-by {deviance,moran}]
+                                                   [--moran-perms P]]
 
 ``--sparse-counts DENSITY`` thins the counts to about that fraction of non-zeros and runs the whole chain on them as a
 ``SparseCounts``: the size factors and the NMF start from ``counts.T``, the fit from ``counts``.  The dense count array
 then never reaches the device.  ``--select-genes NFEAT`` ranks the genes of those counts first (``rank_genes``: Poisson deviance
 against a constant-rate null, or Moran's I of the log-normalised counts over the spots' 6-neighbour graph) and runs the chain
 on the NFEAT best (``counts.select_genes``) -- the reference's ``ad[:, :nfeat]`` of genes sorted by importance.  The size
-factors stay those of the whole data set.
+factors stay those of the whole data set.  ``--moran-perms P`` then scores the genes that are left with Moran's I under P
+random relabellings of the spots (``gene_autocorr(..., n_perms=P)``) and prints how many have a Benjamini-Hochberg adjusted
+pseudo p-value below 0.05 (with P permutations no p-value is below 1 / (P + 1): a few hundred are needed for that).
 """
 import argparse
 
@@ -25,8 +28,9 @@ import torch.nn as nn
 from gpzoo.gp import SVGP
 from gpzoo.kernels import NSF_RBF
 from gpzoo.likelihoods import NSF2, SparseCounts
-from gpzoo.utilities import (init_softplus, kmeans_inducing_points, project_factors_to_inducing, regularized_nmf,
-                             rank_genes, rescale_spatial_coords, scanpy_sizefactors, smooth_spatial_factors, train)
+from gpzoo.utilities import (fdr_bh, gene_autocorr, init_softplus, kmeans_inducing_points, log_normalize,
+                             project_factors_to_inducing, regularized_nmf, rank_genes, rescale_spatial_coords, scanpy_sizefactors,
+                             smooth_spatial_factors, train)
 
 
 def synthetic_counts(N, D, L, rng):
@@ -68,9 +72,14 @@ def main():
                     help="with --sparse-counts: rank the genes and keep the NFEAT best before the NMF start")
     ap.add_argument("--rank-by", "--rank_by", choices=("deviance", "moran"), default="deviance",
                     help="the score --select-genes ranks by (rank_genes)")
+    ap.add_argument("--moran-perms", "--moran_perms", type=int, default=None, metavar="P",
+                    help="with --sparse-counts: Moran's I of the genes under P relabellings of the spots, and how many genes "
+                         "have fdr_bh(pval_sim) < 0.05")
     a = ap.parse_args()
     if a.select_genes is not None and a.sparse_counts is None:
         raise SystemExit("--select-genes ranks the stored non-zeros of a SparseCounts: pass --sparse-counts DENSITY with it")
+    if a.moran_perms is not None and a.sparse_counts is None:
+        raise SystemExit("--moran-perms scores the stored non-zeros of a SparseCounts: pass --sparse-counts DENSITY with it")
     dev = torch.device("cuda")
     rng = np.random.default_rng(0)
     X, Y = synthetic_counts(a.spots, a.genes, a.factors, rng)
@@ -89,6 +98,12 @@ def main():
             Y = Y.select_genes(order)
             print(f"selected {Y.shape[0]} of {a.genes} genes by {a.rank_by}: score {float(score[0]):.4g} ... {float(score[-1]):.4g}, "
                   f"{Y.nnz} non-zeros kept")
+        if a.moran_perms is not None:
+            ac = gene_autocorr(log_normalize(Y, center=False), X, n_perms=a.moran_perms)
+            q = fdr_bh(ac.pval_sim)
+            print(f"Moran's I under {ac.n_perms} relabellings of the spots: {int((q < 0.05).sum())} of {Y.shape[0]} genes with "
+                  f"fdr_bh(pval_sim) < 0.05 (smallest attainable p {1 / (ac.n_perms + 1):.3g}), median z_sim "
+                  f"{float(ac.z_sim.nanmedian()):.3g}")
         F, W = regularized_nmf(Y.T, L, sz=sz, **nmf_kw)
     else:
         sz = scanpy_sizefactors(Y)

@@ -25,20 +25,19 @@
 // itself at the start of the launch.  Per gene it scatters the row into the line, gathers the K neighbours of every stored
 // entry from it, and then clears exactly the words it scattered: O(nnz (K + 2)) memory operations, no search, and a
 // scratch of workgroups x N x 4 bytes whatever D is.  The in-degree of the table is counted once per call with integer
-// atomics (a histogram; no atomics on values); that pass also checks every entry of the table and raises info.
+// atomics (a histogram; no atomics on values); that pass also checks every entry of the table and raises info.  The Moran
+// kernels and the closing expression live in moran_expr.h, which moran_perm.hip (the permutation null) includes too.
 //
 // Built with -ffp-contract=off: every product and sum of the closing formulas is rounded on its own, so the numbers are
 // those of the same expressions written in numpy (the CPU tests evaluate them that way), not of a compiler's choice of fma.
 // The kernels wait for memory, not for the ALUs, so this costs nothing.
 #include "gene_rows.h"
+#include "moran_expr.h"
 
 namespace gpz {
 namespace grk {
 
-constexpr int GR_MAX_WG = 256;     // workgroups of the Moran pass (one per CU): its scratch is GR_MAX_WG lines, and more lines
-                                   // in flight bought nothing (measured: DESIGN.md section 5)
 constexpr int GR_DEV_WG = 2048;    // workgroups of the deviance pass (eight per CU, a full CU of waves; it has no lines)
-constexpr int GR_KMAX = 32;
 
 // S = sum_n size[n]: one workgroup, strided per thread, then the tree
 __global__ __launch_bounds__(GR_THREADS) void gr_total_kernel(const double* __restrict__ size, int64_t N, double* __restrict__ total) {
@@ -95,92 +94,6 @@ __global__ __launch_bounds__(GR_THREADS) void gr_deviance_kernel(GrRows r, const
   }
 }
 
-// every entry of the table once: the in-degree histogram (integer atomics) and the check of mi_rows -- an entry outside
-// [0, N) or naming its own row is counted nowhere, read nowhere, and raises info
-__global__ __launch_bounds__(GR_THREADS) void gr_indeg_kernel(const int64_t* __restrict__ nbr, int64_t N, int K,
-                                                              int32_t* __restrict__ indeg, int32_t* __restrict__ info) {
-  const int64_t e = int64_t(blockIdx.x) * GR_THREADS + threadIdx.x;
-  if (e >= N * K) return;
-  const int64_t i = e / K, j = nbr[e];
-  if (j < 0 || j >= N || j == i) {
-    *info = 1;
-    return;
-  }
-  atomicAdd(indeg + j, 1);
-}
-
-__global__ __launch_bounds__(GR_THREADS) void gr_moran_kernel(GrRows r, const int64_t* __restrict__ nbr, int K,
-                                                              const int32_t* __restrict__ indeg, float* __restrict__ lines,
-                                                              double* __restrict__ I) {
-  __shared__ double red[4][GR_THREADS];
-  __shared__ float lohi[2][GR_THREADS];
-  const int64_t N = r.N;
-  float* __restrict__ line = lines + int64_t(blockIdx.x) * N;
-  for (int64_t n = threadIdx.x; n < N; n += GR_THREADS) line[n] = 0.0f;
-  __syncthreads();
-  for (int64_t d = blockIdx.x; d < r.D; d += gridDim.x) {
-    int64_t lo, hi;
-    gr_row(r, d, lo, hi);
-    for (int64_t k = lo + threadIdx.x; k < hi; k += GR_THREADS) {
-      int32_t spot;
-      float x;
-      if (gr_entry(r, k, spot, x)) line[spot] = x;
-    }
-    __syncthreads();
-    double s = 0.0, q = 0.0, c = 0.0, a = 0.0;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int64_t k = lo + threadIdx.x; k < hi; k += GR_THREADS) {
-      int32_t spot;
-      float xf;
-      if (!gr_entry(r, k, spot, xf)) continue;
-      const double x = double(xf);
-      const int64_t* __restrict__ row = nbr + int64_t(spot) * K;
-      double lag = 0.0;
-      for (int m = 0; m < K; ++m) {
-        const int64_t j = row[m];
-        if (j < 0 || j >= N || j == spot) continue;              // gr_indeg_kernel has told the caller
-        lag += double(line[j]);
-      }
-      s += x;
-      q += x * x;
-      c += x * lag;
-      a += double(indeg[spot]) * x;
-      mn = xf < mn ? xf : mn;
-      mx = xf > mx ? xf : mx;
-    }
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = q;
-    red[2][threadIdx.x] = c;
-    red[3][threadIdx.x] = a;
-    lohi[0][threadIdx.x] = mn;
-    lohi[1][threadIdx.x] = mx;
-    __syncthreads();                                              // every gather of the line is done
-    for (int64_t k = lo + threadIdx.x; k < hi; k += GR_THREADS) {
-      const int32_t spot = r.row_spot[k];
-      if (spot >= 0 && spot < N) line[spot] = 0.0f;
-    }
-    for (int h = GR_THREADS / 2; h >= 1; h >>= 1) {
-      if (int(threadIdx.x) < h) {
-        for (int v = 0; v < 4; ++v) red[v][threadIdx.x] += red[v][threadIdx.x + h];
-        const float l2 = lohi[0][threadIdx.x + h], h2 = lohi[1][threadIdx.x + h];
-        if (l2 < lohi[0][threadIdx.x]) lohi[0][threadIdx.x] = l2;
-        if (h2 > lohi[1][threadIdx.x]) lohi[1][threadIdx.x] = h2;
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      const double Nd = double(N), Kd = double(K);
-      const double S = red[0][0], Q = red[1][0], Cs = red[2][0], A = red[3][0];
-      const double xbar = S / Nd;
-      const double den = Kd * (Q - Nd * (xbar * xbar));
-      const double num = Cs - xbar * (Kd * S + A) + Nd * Kd * (xbar * xbar);
-      const bool constant = hi - lo == N && lohi[0][0] == lohi[1][0];     // stored at every spot with one single value
-      I[d] = (hi > lo && !constant && den > 0.0) ? num / den : double(NAN);
-    }
-    __syncthreads();                                              // the line is clear and red is free for the next gene
-  }
-}
-
 struct GrPlan {
   double* total;      // deviance: S
   int32_t* indeg;     // Moran: (N,)
@@ -202,12 +115,6 @@ static GrPlan gr_plan(int64_t N, int64_t D, bool moran, void* scratch) {
   }
   p.bytes = c.used();
   return p;
-}
-
-static int gr_check_k(const char* who, int64_t N, int32_t K) {
-  GPZ_REQUIRE(K >= 1 && K <= GR_KMAX && K < N, "%s: K = %d neighbours of N = %lld spots unsupported (1 <= K <= %d, K < N)", who, K,
-              (long long)N, GR_KMAX);
-  return 0;
 }
 
 }  // namespace grk
@@ -277,7 +184,8 @@ extern "C" int gpz_gene_morans_i_sparse(const int64_t* row_ptr, const int32_t* r
   hipLaunchKernelGGL(gr_indeg_kernel, dim3(unsigned((N * K + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, N, int(K),
                      p.indeg, info);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(gr_moran_kernel, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, nbr, int(K), p.indeg, p.lines, I);
+  hipLaunchKernelGGL(gr_moran_kernel<SparseRows>, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, SparseRows{r}, nbr, int(K), p.indeg,
+                     p.lines, I, static_cast<double*>(nullptr));
   GPZ_LAUNCH_OK();
   return 0;
 }

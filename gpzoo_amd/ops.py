@@ -1590,6 +1590,107 @@ def gene_morans_i_sparse(values, nbr) -> torch.Tensor:
     return out
 
 
+_LINE_MODES = {0: 0, 1: 1, 2: 2, "auto": 0, "global": 1, "lds": 2}
+
+
+def _line_mode(who: str, line_mode) -> int:
+    if isinstance(line_mode, bool) or line_mode not in _LINE_MODES:
+        raise ValueError(f"{who}: line_mode {line_mode!r} unknown (0 / 'auto', 1 / 'global', 2 / 'lds')")
+    return _LINE_MODES[line_mode]
+
+
+def morans_perm_plan(N: int, D: int, K: int, P: int, nnz: Optional[int] = None, perm_batch: int = 0, line_mode=0) -> dict:
+    """How ``gene_morans_perm_sparse`` (``nnz`` stored entries) or ``morans_perm_rows`` (``nnz=None``) covers a shape
+    (gpz_gene_morans_perm_sparse_plan / gpz_morans_perm_rows_plan, host-only queries: no device needed): ``perm_batch``
+    (permutations per launch) and ``line_mode`` (1 scratch memory, 2 LDS) as resolved, ``workgroups`` (genes in flight),
+    ``partials_bytes``.  A ``line_mode`` of 2 where a line of N floats does not fit the LDS raises ValueError."""
+    lib = _lib.load()
+    pb, lm, wg, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    mode = _line_mode("morans_perm_plan", line_mode)
+    outs = (C.byref(pb), C.byref(lm), C.byref(wg), C.byref(nb))
+    if nnz is None:
+        rc = lib.gpz_morans_perm_rows_plan(int(N), int(D), int(K), int(P), int(perm_batch), mode, *outs)
+    else:
+        rc = lib.gpz_gene_morans_perm_sparse_plan(int(N), int(D), int(nnz), int(K), int(P), int(perm_batch), mode, *outs)
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(perm_batch=pb.value, line_mode=lm.value, workgroups=wg.value, partials_bytes=int(nb.value))
+
+
+def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, perms, return_sims, perm_batch, line_mode):
+    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
+        raise ValueError(f"{who}: nbr must be an ({N}, K) integer table")
+    if (not isinstance(perms, torch.Tensor) or perms.dim() != 2 or perms.shape[0] < 1 or perms.shape[1] != N
+            or perms.dtype.is_floating_point or perms.dtype == torch.bool):
+        raise ValueError(f"{who}: perms must be a (P, {N}) integer tensor, P >= 1")
+    if isinstance(perm_batch, bool) or not isinstance(perm_batch, int) or perm_batch < 0:
+        raise ValueError(f"{who}: perm_batch {perm_batch!r} must be a non-negative integer (0 = chosen by the plan)")
+    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
+    if perms.dtype != torch.int32:
+        perms = perms.to(device=dev, dtype=torch.int64).clamp(-1, N)                  # a wide entry stays out of range in 32 bits
+    perms = perms.to(device=dev, dtype=torch.int32).contiguous()
+    K, P = int(nbr.shape[1]), int(perms.shape[0])
+    plan = morans_perm_plan(N, D, K, P, nnz, perm_batch, _line_mode(who, line_mode))
+    lib = _lib.load()
+    I, mean, m2 = (torch.empty(D, dtype=torch.float64, device=dev) for _ in range(3))
+    n_ge, n_le = (torch.empty(D, dtype=torch.int32, device=dev) for _ in range(2))
+    sims = torch.empty((D, P), dtype=torch.float64, device=dev) if return_sims else None
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, plan["partials_bytes"])
+        rc = getattr(lib, entry)(*inputs, _ptr(nbr), _ptr(perms), N, D, *(() if nnz is None else (nnz,)), K, P, plan["perm_batch"],
+                                 plan["line_mode"], _ptr(I), _ptr(sims), _ptr(n_ge), _ptr(n_le), _ptr(mean), _ptr(m2), _ptr(info),
+                                 _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, entry)
+    code = int(info.item())
+    if code == 1:
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, N) or naming its own row")
+    if code != 0:
+        raise ValueError(f"{who}: a row of perms is not a permutation of 0 .. N - 1 (an entry outside [0, N) or an index named twice)")
+    return MoransPerm(I, n_ge, n_le, mean, m2, sims)
+
+
+@dataclass
+class MoransPerm:
+    """``gene_morans_perm_sparse`` / ``morans_perm_rows``: ``I`` (D,) fp64; ``n_ge`` / ``n_le`` (D,) int32, the permutations
+    with I_pi >= I / <= I; ``sim_mean`` and ``sim_m2`` (D,) fp64, the mean of I_pi and sum (I_pi - mean)^2; ``sims`` (D, P)
+    fp64 or None."""
+    I: torch.Tensor
+    n_ge: torch.Tensor
+    n_le: torch.Tensor
+    sim_mean: torch.Tensor
+    sim_m2: torch.Tensor
+    sims: Optional[torch.Tensor]
+
+
+def gene_morans_perm_sparse(values, nbr, perms, *, return_sims: bool = False, perm_batch: int = 0, line_mode=0) -> MoransPerm:
+    """Moran's I of every gene of a whole ``SparseCounts`` / ``SparseExpression`` under the P relabellings of the spots in
+    ``perms`` (P, N) integer, x^pi[i] = x[pi[i]], over nbr (N,K) int64, 1 <= K <= 32 (gpz_gene_morans_perm_sparse): ``I`` is
+    ``gene_morans_i_sparse``'s, bit for bit; the counts compare N C - S A in fp64, exact for integer-valued data.  A
+    ``MoransPerm``; all of it is independent of ``perm_batch`` (permutations per launch, 0 = the plan's) and ``line_mode``
+    (0 / "auto", 1 / "global", 2 / "lds").  A bad neighbour table and a row of ``perms`` that is no permutation raise
+    ValueError (checked on the device; one synchronisation)."""
+    who = "gene_morans_perm_sparse"
+    v = _whole_values(values, who)
+    _need_cuda(v.col_val)
+    D, N = v.shape
+    inputs = (_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val))
+    return _morans_perm(who, "gpz_gene_morans_perm_sparse", N, D, v.nnz, v.device, inputs, nbr, perms, return_sims, perm_batch, line_mode)
+
+
+def morans_perm_rows(values, nbr, perms, *, return_sims: bool = False, perm_batch: int = 0, line_mode=0) -> MoransPerm:
+    """``gene_morans_perm_sparse`` for a dense fp32 (D, N) tensor, one gene per row (gpz_morans_perm_rows): every spot is an
+    entry, zeros included, and the row is its own line.  ``I`` is the expanded form's, within rounding of ``morans_i`` of the
+    transpose."""
+    who = "morans_perm_rows"
+    if not isinstance(values, torch.Tensor) or values.dim() != 2 or values.dtype != torch.float32:
+        raise ValueError(f"{who}: a dense (D, N) float32 tensor expected")
+    _need_cuda(values)
+    V = values.detach().contiguous()
+    D, N = V.shape
+    return _morans_perm(who, "gpz_morans_perm_rows", N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims, perm_batch, line_mode)
+
+
 def gene_dispersion_plan(N: int, D: int, nnz: int) -> dict:
     """How ``gene_dispersion_sparse`` covers a shape (gpz_gene_dispersion_sparse_plan, a host-only query: no device needed):
     ``gene_chunk`` (stored entries of a gene row per sweep of its workgroup), ``workgroups`` (genes in flight), ``tol_t`` (the

@@ -8,7 +8,7 @@ caller's tensors live on.
 """
 from __future__ import annotations
 
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -346,7 +346,8 @@ def dims_autocorr(factors, coords, sort=True, *, n_neighs=6):
     values in column order (``factors[:, idx]`` orders the factors by spatial autocorrelation).  ``sort=False``: the
     reference's ``df.sort_index()`` over AnnData's default names "0" ... "L-1", which is a STRING sort -- for L >= 11 the
     order is 0, 1, 10, 11, ..., 19, 2, 20, ...; idx and I stay aligned either way.  The reference's
-    ``print('here_andata')`` is not reproduced."""
+    ``print('here_andata')`` is not reproduced.  For permutation p-values of the factors, score them as genes:
+    ``gene_autocorr(factors.T, coords, n_perms=...)``."""
     import numpy as np
     from . import ops
 
@@ -709,14 +710,65 @@ def _moran_moments(nbr):
     return expected, variance
 
 
-def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None):
+class GeneAutocorrPerm(NamedTuple):
+    """``gene_autocorr(..., n_perms=)``: the fields of ``GeneAutocorr`` (``I``, ``expected``, ``variance``, ``z``: what the
+    call without permutations returns, bit for bit) and the permutation null of squidpy's ``spatial_autocorr(n_perms=)``,
+    (D,) tensors on the values' device.  ``n_perms`` = P (int); ``n_ge`` / ``n_le`` int32: the permutations whose I is >= /
+    <= the observed one; ``pval_greater`` = (n_ge + 1) / (P + 1), ``pval_less`` = (n_le + 1) / (P + 1), ``pval_sim`` the
+    smaller of the two (squidpy's folded pseudo p-value, identical to it when no simulation ties with I); ``mean_sim`` and
+    ``var_sim`` (the population variance, as ``np.var``) of the simulated I; ``z_sim`` = (I - mean_sim) / sqrt(var_sim), NaN
+    where var_sim is 0; ``pval_z_sim`` = erfc(|z_sim| / sqrt 2) / 2; ``sims`` (D, P) fp64 or None.  A gene whose I is NaN has
+    NaN p-values and zero counts."""
+    I: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+    n_perms: int
+    n_ge: torch.Tensor
+    n_le: torch.Tensor
+    pval_greater: torch.Tensor
+    pval_less: torch.Tensor
+    pval_sim: torch.Tensor
+    mean_sim: torch.Tensor
+    var_sim: torch.Tensor
+    z_sim: torch.Tensor
+    pval_z_sim: torch.Tensor
+    sims: Optional[torch.Tensor]
+
+
+def _autocorr_perms(who, N, n_perms, perms):
+    """The checked arguments of the permutation null: (P, perms or None)."""
+    import numpy as np
+    if n_perms is not None and perms is not None:
+        raise ValueError(f"{who}: n_perms and perms exclude each other (perms carries its own count)")
+    if perms is not None:
+        pm = perms.detach() if isinstance(perms, torch.Tensor) else torch.as_tensor(np.asarray(perms))
+        if pm.dim() != 2 or pm.shape[0] < 1 or pm.shape[1] != N or pm.dtype.is_floating_point or pm.dtype == torch.bool:
+            raise ValueError(f"{who}: perms must be a (P, {N}) integer tensor, P >= 1, got {tuple(pm.shape)} of {pm.dtype}")
+        return int(pm.shape[0]), pm
+    if isinstance(n_perms, bool) or not isinstance(n_perms, int) or n_perms < 1:
+        raise ValueError(f"{who}: n_perms={n_perms!r} must be a positive integer")
+    return n_perms, None
+
+
+def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, seed=0, perms=None, return_sims=False):
     """Moran's I of every gene over the spots' directed ``n_neighs``-nearest-neighbour graph -- squidpy's
     ``spatial_autocorr(mode="moran")`` with one gene per column, the other standard ranking of spatial data.  ``values``: a
     whole ``SparseCounts`` or ``SparseExpression`` (the offset does not change I), scored from its stored entries
     (``ops.gene_morans_i_sparse``; nothing of D x N elements is formed), or a dense (D, N) tensor, scored by
     ``ops.morans_i``.  The graph is ``ops.spatial_knn(coords, n_neighs)`` (``coords`` (N, d), d <= 4), or ``graph=``, an
     (N, K) int64 table of distinct neighbours, K <= 32.  Returns a ``GeneAutocorr``.  A gene without stored entries and a
-    constant gene give NaN; I of a nearly constant gene loses digits in proportion to mean^2 / variance."""
+    constant gene give NaN; I of a nearly constant gene loses digits in proportion to mean^2 / variance.
+
+    ``n_perms=P`` (or ``perms=``, a (P, N) integer tensor of permutations, used as given) adds the permutation null of
+    squidpy's ``spatial_autocorr(..., n_perms=)`` and returns a ``GeneAutocorrPerm``: I is recomputed under P random
+    relabellings of the spots (``ops.gene_morans_perm_sparse`` over the stored entries, ``ops.morans_perm_rows`` for a dense
+    tensor, which is scored in fp32), in O(entries x K) per permutation.  Permutation p is ``torch.randperm(N, generator=g,
+    device=...)`` from one generator seeded with ``seed``, drawn one at a time in order.  ``return_sims=True`` keeps the
+    (D, P) simulated values.  This permutes the spot labels against a fixed graph, which is PySAL's definition; squidpy
+    shuffles the rows of its adjacency matrix instead -- both are null models of exchangeable spots, but the numbers differ
+    draw by draw.  The smallest attainable p-value is 1 / (P + 1).  The comparisons I_pi >= I are exact for integer-valued
+    data (counts), ties included; for other values a mathematical tie may fall either way in the last bit."""
     import numpy as np
     from . import ops
     from .likelihoods import SparseCounts, SparseExpression, TransposedCounts
@@ -732,6 +784,9 @@ def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None):
         raise ValueError(f"{who}: a dense (D, N) floating-point tensor expected, got {tuple(values.shape)} of {values.dtype}")
     D, N = values.shape
     dev = values.device
+    permute = n_perms is not None or perms is not None
+    if permute:
+        P, perms = _autocorr_perms(who, N, n_perms, perms)
     if graph is not None:
         nbr = graph.detach() if isinstance(graph, torch.Tensor) else torch.as_tensor(np.asarray(graph))
         if nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
@@ -752,13 +807,57 @@ def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None):
     K = int(nbr.shape[1])
     if not 1 <= K <= 32 or K >= N:
         raise ValueError(f"{who}: {K} neighbours of {N} spots unsupported (1 <= K <= 32, K < N)")
-    if sparse:
+    if permute and perms is None:
+        g = torch.Generator(device=dev)
+        g.manual_seed(int(seed))
+        perms = torch.empty((P, N), dtype=torch.int32, device=dev)
+        for p in range(P):
+            perms[p] = torch.randperm(N, generator=g, device=dev)
+    if sparse and permute:
+        r = ops.gene_morans_perm_sparse(values, nbr, perms, return_sims=return_sims)
+        I = r.I
+    elif sparse:
         I = ops.gene_morans_i_sparse(values, nbr)
     else:
         V = values.detach()
         I = ops.morans_i((V if V.dtype in (torch.float32, torch.float64) else V.float()).T.contiguous(), nbr)
+        if permute:
+            r = ops.morans_perm_rows(V.float(), nbr, perms, return_sims=return_sims)
     expected, variance = _moran_moments(nbr)
-    return GeneAutocorr(I, expected, variance, (I - expected) / torch.sqrt(variance))
+    base = GeneAutocorr(I, expected, variance, (I - expected) / torch.sqrt(variance))
+    if not permute:
+        return base
+    nan = torch.isnan(I) | torch.isnan(r.sim_mean)
+    quiet = torch.full_like(I, float("nan"))
+    n_ge, n_le = (torch.where(nan, torch.zeros_like(n), n) for n in (r.n_ge, r.n_le))
+    pg, pl = (torch.where(nan, quiet, (n.double() + 1.0) / (P + 1.0)) for n in (n_ge, n_le))
+    mean_sim = torch.where(nan, quiet, r.sim_mean)
+    var_sim = torch.where(nan, quiet, r.sim_m2 / P)
+    z_sim = torch.where(var_sim > 0, (I - mean_sim) / torch.sqrt(var_sim), quiet)
+    pval_z = 0.5 * torch.erfc(z_sim.abs() / 2.0 ** 0.5)
+    return GeneAutocorrPerm(*base, P, n_ge, n_le, pg, pl, torch.minimum(pg, pl), mean_sim, var_sim, z_sim, pval_z, r.sims)
+
+
+def fdr_bh(p):
+    """Benjamini-Hochberg adjusted p-values of a 1-D tensor (the FDR correction squidpy and statsmodels put on top of
+    ``pval_sim``): with the m entries that are not NaN sorted increasingly, q_(i) = min_{j >= i} min(1, m p_(j) / j) -- the
+    step-up rule as a running minimum from the largest p.  NaN entries are not counted in m and stay NaN.  Pure torch, on the
+    tensor's device; returns fp64."""
+    if not isinstance(p, torch.Tensor) or p.dim() != 1:
+        raise ValueError("fdr_bh: a 1-D tensor of p-values expected")
+    p = p.detach().to(torch.float64)
+    out = torch.full_like(p, float("nan"))
+    ok = ~torch.isnan(p)
+    m = int(ok.sum())
+    if m == 0:
+        return out
+    vals, order = torch.sort(p[ok], descending=True, stable=True)
+    rank = torch.arange(m, 0, -1, dtype=torch.float64, device=p.device)
+    q = torch.cummin(vals * m / rank, dim=0).values.clamp(max=1.0)
+    adj = torch.empty_like(q)
+    adj[order] = q
+    out[ok] = adj
+    return out
 
 
 def _rank_order(score, nfeat=None):

@@ -69,7 +69,10 @@
  * gpz_count_residuals, gpz_count_residuals_sparse, gpz_residual_morans_i, gpz_residual_morans_i_sparse and the host-only
  * gpz_residual_morans_i_plan -- Pearson or deviance residuals of counts under the predictive mean rate of a fitted count
  * model, and Moran's I of every gene's residuals over the spots' K-neighbour graph (is spatial structure left in what the
- * model did not explain, and in which genes), dense counts or counts stored as their non-zeros; scratch `partials` again.
+ * model did not explain, and in which genes), dense counts or counts stored as their non-zeros; scratch `partials` again;
+ * gpz_gene_morans_perm_sparse, gpz_morans_perm_rows and their host-only *_plan queries -- Moran's I of every gene under P
+ * relabellings of the spots (the permutation null of squidpy's spatial_autocorr(n_perms=)): the simulated values, the counts
+ * behind the pseudo p-value and the simulated mean and variance, from stored non-zeros or dense rows; scratch `partials`.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -487,6 +490,53 @@ int gpz_gene_dispersion_sparse(const int64_t* row_ptr, const int32_t* row_spot, 
                                const double* size, int64_t N, int64_t D, int64_t nnz, double theta_min, double theta_max,
                                int32_t max_iter, double* theta, double* gain, double* poisson_loglik, int32_t* status,
                                int32_t* iterations, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+
+/* Moran's I of every gene under P relabellings of the spots (csrc/moran_perm.hip): the permutation null of squidpy's
+ * spatial_autocorr(..., n_perms=) and of PySAL's Moran.  perms (P, N) int32, row p a permutation pi of 0 .. N - 1; the permuted
+ * gene is x^pi[i] = x[pi[i]], scored over the fixed table nbr (N, K) int64, 1 <= K <= 32, K < N, weights 1 / K.  The graph is
+ * relabelled, not the values: T_pi[pi[i], m] = pi[nbr[i, m]] and indeg_pi[pi[i]] = indeg[i] go to the scratch memory for a
+ * batch of perm_batch permutations at a time, and in the expansion of gpz_gene_morans_i_sparse only
+ *   C_pi = sum_{i stored} x_i sum_m x[T_pi[i, m]]   and   A_pi = sum_{i stored} indeg_pi(i) x_i
+ * depend on pi: O(entries x K) per permutation, nothing of D x N elements is formed.
+ *   gpz_gene_morans_perm_sparse  the by-gene arrays of a WHOLE data set stored as its non-zeros, as gpz_gene_morans_i_sparse
+ *   gpz_morans_perm_rows         values fp32 (D, N), contiguous: every spot is an entry, zeros included
+ * Outputs, fp64 (D,) unless said otherwise:
+ *   I         gpz_gene_morans_i_sparse's I of the unpermuted gene, bit for bit (the rows entry: the same expansion over all N
+ *             spots); NaN as there
+ *   sims      (D, P), may be NULL: I_pi, the same expression on (S, Q, C_pi, A_pi); a row of perms that is the identity gives
+ *             I, bit for bit
+ *   n_ge, n_le   int32: the permutations with I_pi >= I and with I_pi <= I, decided on t = N C - S A in fp64 (the numerator
+ *             is C - S A / N and the denominator does not depend on pi).  Exact for integer-valued data with |t| < 2^53:
+ *             ties are then counted as ties on every run and every path; for other data a mathematical tie may fall
+ *             either way in the last bit.  0 for a gene whose I is NaN
+ *   sim_mean, sim_m2   mean of I_pi over the P permutations and sum (I_pi - mean)^2, by Welford's update in permutation
+ *             order; NaN where I is
+ * info[0] (device int32): 1 when an entry of nbr lies outside [0, N) or names its own row (as gpz_gene_morans_i_sparse), 2 when
+ * a row of perms is no permutation (an entry outside [0, N), or an index named twice); such entries are skipped, nothing is
+ * read or written out of range, and the outputs are then meaningless.
+ * line_mode: where a gene's line of N floats lives while its permutations are evaluated -- 1 the scratch memory, 2 the
+ * workgroup's LDS (an argument error unless 4 N + 512 <= 163840 bytes), 0 = the plan's choice: LDS wherever it fits.
+ * perm_batch: permutations per launch, at most 32; 0 = the plan's choice: the tables of a batch take at most 256 MiB, at
+ * most P, and at most 16 with the line in LDS (one permutation per wave of the workgroup) or 8 with the line in the scratch
+ * memory (more tables in flight cost time there).  Every sum is fp64 in
+ * a fixed order with no atomics on values (integer atomics count the in-degree and the writes of the relabelling): all
+ * outputs are reproducible bit for bit and independent of perm_batch and line_mode.  The scratch is `partials`, sized by the
+ * host-only plan query (any out pointer may be NULL), which reports perm_batch and line_mode as resolved, workgroups (genes
+ * in flight) and partials_bytes; it need not be cleared.  N, D, nnz, P < 2^31, P >= 1; partials 16-byte aligned.  Argument
+ * errors return -1 before any launch with the reason in gpz_last_error. */
+int gpz_gene_morans_perm_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int64_t P, int32_t perm_batch_wanted,
+                                     int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
+                                     int64_t* partials_bytes);
+int gpz_gene_morans_perm_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int64_t nnz, int32_t K, int64_t P,
+                                int32_t perm_batch, int32_t line_mode, double* I, double* sims, int32_t* n_ge, int32_t* n_le,
+                                double* sim_mean, double* sim_m2, int32_t* info, void* partials, size_t partials_bytes,
+                                void* stream);
+int gpz_morans_perm_rows_plan(int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch_wanted, int32_t line_mode_wanted,
+                              int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups, int64_t* partials_bytes);
+int gpz_morans_perm_rows(const float* values, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K, int64_t P,
+                         int32_t perm_batch, int32_t line_mode, double* I, double* sims, int32_t* n_ge, int32_t* n_le,
+                         double* sim_mean, double* sim_m2, int32_t* info, void* partials, size_t partials_bytes, void* stream);
 
 /* Residuals of counts under the predictive mean rate of a fitted count model, and Moran's I of every gene's residuals
  * (csrc/residual.hip).  With m = exp(mean + scale^2 / 2) (lognormal_mean != 0; exp(mean) otherwise) the rate is
