@@ -7,13 +7,13 @@ on synthetic counts, against the same model started from mu = 0 and random loadi
 
     PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30
                                                    --inducing-from {subset,kmeans} --mu-from {smooth,projection}
-                                                   --sparse-counts DENSITY [--select-genes NFEAT --rank-by {deviance,moran}]
+                                                   --sparse-counts DENSITY [--select-genes NFEAT --rank-by {deviance,moran,geary}]
                                                    [--moran-perms P]]
 
 ``--sparse-counts DENSITY`` thins the counts to about that fraction of non-zeros and runs the whole chain on them as a
 ``SparseCounts``: the size factors and the NMF start from ``counts.T``, the fit from ``counts``.  The dense count array
 then never reaches the device.  ``--select-genes NFEAT`` ranks the genes of those counts first (``rank_genes``: Poisson deviance
-against a constant-rate null, or Moran's I of the log-normalised counts over the spots' 6-neighbour graph) and runs the chain
+against a constant-rate null, or Moran's I / 1 - Geary's C of the log-normalised counts over the spots' 6-neighbour graph) and runs the chain
 on the NFEAT best (``counts.select_genes``) -- the reference's ``ad[:, :nfeat]`` of genes sorted by importance.  The size
 factors stay those of the whole data set.  ``--moran-perms P`` then scores the genes that are left with Moran's I under P
 random relabellings of the spots (``gene_autocorr(..., n_perms=P)``) and prints how many have a Benjamini-Hochberg adjusted
@@ -70,7 +70,7 @@ def main():
                     help="keep about this fraction of the counts as non-zeros and run the chain through SparseCounts")
     ap.add_argument("--select-genes", "--select_genes", type=int, default=None, metavar="NFEAT",
                     help="with --sparse-counts: rank the genes and keep the NFEAT best before the NMF start")
-    ap.add_argument("--rank-by", "--rank_by", choices=("deviance", "moran"), default="deviance",
+    ap.add_argument("--rank-by", "--rank_by", choices=("deviance", "moran", "geary"), default="deviance",
                     help="the score --select-genes ranks by (rank_genes)")
     ap.add_argument("--moran-perms", "--moran_perms", type=int, default=None, metavar="P",
                     help="with --sparse-counts: Moran's I of the genes under P relabellings of the spots, and how many genes "
@@ -94,7 +94,7 @@ def main():
         sz = scanpy_sizefactors(Y.T)
         sz = np.maximum(sz, sz[sz > 0].min())           # a spot thinned to nothing says nothing about its depth; log(sz) stays finite
         if a.select_genes is not None:
-            order, score = rank_genes(Y, by=a.rank_by, coords=X if a.rank_by == "moran" else None, nfeat=a.select_genes)
+            order, score = rank_genes(Y, by=a.rank_by, coords=X if a.rank_by in ("moran", "geary") else None, nfeat=a.select_genes)
             Y = Y.select_genes(order)
             print(f"selected {Y.shape[0]} of {a.genes} genes by {a.rank_by}: score {float(score[0]):.4g} ... {float(score[-1]):.4g}, "
                   f"{Y.nnz} non-zeros kept")

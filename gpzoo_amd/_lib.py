@@ -106,6 +106,22 @@ _SIGNATURES = {
                                   [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64)]),
     "gpz_morans_perm_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 2 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32] +
                              [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+    "gpz_gene_spatial_stats_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32),
+                                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "gpz_gene_spatial_stats_sparse": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] * 3 + [C.c_int32] + [C.c_void_p] * 7 +
+                                      [C.c_size_t, C.c_void_p]),
+    "gpz_spatial_stats_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64)]),
+    "gpz_spatial_stats": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 7 +
+                          [C.c_size_t, C.c_void_p]),
+    "gpz_gene_autocorr_perm_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                     C.c_int32] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64)]),
+    "gpz_gene_autocorr_perm_sparse": (C.c_int, [C.c_void_p] * 6 + [C.c_int64] * 3 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                                                    C.c_int32] + [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
+    "gpz_autocorr_perm_rows_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] +
+                                    [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_int64)]),
+    "gpz_autocorr_perm_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 2 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] +
+                               [C.c_void_p] * 8 + [C.c_size_t, C.c_void_p]),
     "gpz_gene_dispersion_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                   C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "gpz_gene_dispersion_sparse": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] * 3 + [C.c_double, C.c_double, C.c_int32] +

@@ -1,5 +1,7 @@
-// moran_perm.hip -- Moran's I of every gene under P relabellings of the spots: the permutation null of squidpy's
-// spatial_autocorr(..., n_perms=) / PySAL's Moran, in O(entries x K) per permutation and never forming D x N.
+// moran_perm.hip -- Moran's I or Geary's C of every gene under P relabellings of the spots: the permutation null of squidpy's
+// spatial_autocorr(..., n_perms=) / PySAL's Moran and Geary, in O(entries x K) per permutation and never forming D x N.
+// The kernels are templated on the statistic; the Moran entries are here, and spatial_stats.hip's entries, which take the
+// statistic as an argument, come in through the drivers declared in moran_perm.h.
 //
 // For a permutation pi of the N spots the permuted gene is x^pi[i] = x[pi[i]].  Relabelling the graph instead of the values,
 //   sum_i z[pi[i]] sum_{j in nbr(i)} z[pi[j]]  =  sum_a z[a] sum_m z[T_pi[a, m]],
@@ -23,7 +25,11 @@
 //                      (Welford) in permutation order, so nothing depends on perm_batch.
 // The line is in the scratch memory (line_mode 1) or in dynamic LDS (2) where 4 N plus the batch arrays fit a workgroup's
 // 160 KiB; the arithmetic is the same.  No floating-point atomics; every sum fp64 in a fixed order.
-#include "moran_expr.h"
+//
+// STAT_GEARY: the gene pass is ss_gene_kernel of geary_expr.h, the second sum per permutation is Q_in,pi = sum indeg_pi x^2
+// in the place of A_pi, the value is geary_value and "C_pi >= C" is decided on geary_order, Q_in - 2 C_s.  Everything else is
+// shared, and the STAT_MORAN instantiations add what they added before the statistic became a parameter.
+#include "moran_perm.h"
 
 namespace gpz {
 namespace grk {
@@ -78,7 +84,7 @@ struct MpBatch {
   int K, pb;
 };
 
-template <class Rows, bool LDS_LINE>
+template <class Rows, bool LDS_LINE, int STAT>
 __global__ __launch_bounds__(MP_THREADS) void mp_stat_kernel(Rows r, MpBatch b) {
   extern __shared__ __attribute__((aligned(16))) double mp_smem[];      // I_pi, t_pi of the batch, then the line
   double* const sI = mp_smem;
@@ -132,7 +138,8 @@ __global__ __launch_bounds__(MP_THREADS) void mp_stat_kernel(Rows r, MpBatch b) 
             lag += double(src[j]);
           }
           c[u] += x * lag;
-          a[u] += double(dg[spot]) * x;
+          if constexpr (STAT == STAT_GEARY) a[u] += double(dg[spot]) * (x * x);
+          else a[u] += double(dg[spot]) * x;
         }
       }
       // the tree of gr_moran_kernel over 256 partial sums: slots t and t + 128, then t and t + 64, then the lanes
@@ -142,8 +149,13 @@ __global__ __launch_bounds__(MP_THREADS) void mp_stat_kernel(Rows r, MpBatch b) 
         as += __shfl_down(as, h, 64);
       }
       if (lane == 0) {
-        sI[q] = moran_value(N, K, S, Q, cs, as, scored);
-        sT[q] = moran_order(N, S, cs, as);
+        if constexpr (STAT == STAT_GEARY) {
+          sI[q] = geary_value(N, K, S, Q, cs, as, scored);
+          sT[q] = geary_order(cs, as);
+        } else {
+          sI[q] = moran_value(N, K, S, Q, cs, as, scored);
+          sT[q] = moran_order(N, S, cs, as);
+        }
       }
     }
     __syncthreads();                                                    // every gather of the line is done
@@ -217,34 +229,24 @@ static int mp_plan(const char* who, int64_t N, int64_t D, int32_t K, int64_t P, 
   return 0;
 }
 
-struct MpOut {
-  double* I;
-  double* sims;
-  int32_t* n_ge;
-  int32_t* n_le;
-  double* sim_mean;
-  double* sim_m2;
-  int32_t* info;
-};
-
-template <class Rows, bool LDS_LINE>
+template <class Rows, bool LDS_LINE, int STAT>
 static int mp_launch_stat(const Rows& r, const MpBatch& b, int workgroups, size_t lds, hipStream_t s) {
   if (LDS_LINE) {
     static bool set[64] = {};
     int dev = 0;
     GPZ_HIP_OK(hipGetDevice(&dev));
     if (!set[dev & 63]) {
-      GPZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mp_stat_kernel<Rows, LDS_LINE>),
+      GPZ_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mp_stat_kernel<Rows, LDS_LINE, STAT>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(MP_LDS_MAX)));
       set[dev & 63] = true;
     }
   }
-  hipLaunchKernelGGL((mp_stat_kernel<Rows, LDS_LINE>), dim3(unsigned(workgroups)), dim3(MP_THREADS), lds, s, r, b);
+  hipLaunchKernelGGL((mp_stat_kernel<Rows, LDS_LINE, STAT>), dim3(unsigned(workgroups)), dim3(MP_THREADS), lds, s, r, b);
   GPZ_LAUNCH_OK();
   return 0;
 }
 
-template <class Rows>
+template <class Rows, int STAT>
 static int mp_run(const char* who, const Rows& r, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K, int64_t P,
                   int32_t perm_batch, int32_t line_mode, const MpOut& o, void* partials, size_t partials_bytes, void* stream) {
   GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "%s: partials must be 16-byte aligned", who);
@@ -261,8 +263,12 @@ static int mp_run(const char* who, const Rows& r, const int64_t* nbr, const int3
   hipLaunchKernelGGL(gr_indeg_kernel, dim3(unsigned((N * K + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, N, int(K),
                      p.indeg, o.info);
   GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(gr_moran_kernel<Rows>, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, nbr, int(K), p.indeg, p.lines, o.I,
-                     p.stats);
+  if constexpr (STAT == STAT_GEARY)
+    hipLaunchKernelGGL(ss_gene_kernel<Rows>, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, nbr, int(K), p.indeg, p.lines,
+                       SsOut{nullptr, o.I, nullptr, nullptr, nullptr}, p.stats);
+  else
+    hipLaunchKernelGGL(gr_moran_kernel<Rows>, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, nbr, int(K), p.indeg, p.lines, o.I,
+                       p.stats);
   GPZ_LAUNCH_OK();
   for (int64_t p0 = 0; p0 < P; p0 += p.perm_batch) {
     const int pb = int(P - p0 < p.perm_batch ? P - p0 : p.perm_batch);
@@ -272,8 +278,8 @@ static int mp_run(const char* who, const Rows& r, const int64_t* nbr, const int3
                        perms + p0 * N, N, int(K), pb, p.T, p.indeg_pi, p.written, o.info);
     GPZ_LAUNCH_OK();
     const MpBatch b{p.T, p.indeg_pi, p.stats, p.lines, o.sims, o.n_ge, o.n_le, o.sim_mean, o.sim_m2, P, p0, int(K), pb};
-    if (int rc = p.line_mode == 2 ? mp_launch_stat<Rows, true>(r, b, p.workgroups, p.lds, s)
-                                  : mp_launch_stat<Rows, false>(r, b, p.workgroups, p.lds, s))
+    if (int rc = p.line_mode == 2 ? mp_launch_stat<Rows, true, STAT>(r, b, p.workgroups, p.lds, s)
+                                  : mp_launch_stat<Rows, false, STAT>(r, b, p.workgroups, p.lds, s))
       return rc;
   }
   return 0;
@@ -287,6 +293,32 @@ static int mp_report(const MpPlan& p, int32_t* perm_batch, int32_t* line_mode, i
   return 0;
 }
 
+// moran_perm.h
+int mp_plan_query(const char* who, int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch_wanted, int32_t line_mode_wanted,
+                  bool staged, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups, int64_t* partials_bytes) {
+  MpPlan p;
+  if (int rc = mp_plan(who, N, D, K, P, perm_batch_wanted, line_mode_wanted, staged, nullptr, p)) return rc;
+  return mp_report(p, perm_batch, line_mode, workgroups, partials_bytes);
+}
+
+int mp_run_sparse(const char* who, int stat, const GrRows& rows, const int64_t* nbr, const int32_t* perms, int32_t K, int64_t P,
+                  int32_t perm_batch, int32_t line_mode, const MpOut& o, void* partials, size_t partials_bytes, void* stream) {
+  const SparseRows r{rows};
+  return stat == STAT_GEARY ? mp_run<SparseRows, STAT_GEARY>(who, r, nbr, perms, rows.N, rows.D, K, P, perm_batch, line_mode, o, partials,
+                                                             partials_bytes, stream)
+                            : mp_run<SparseRows, STAT_MORAN>(who, r, nbr, perms, rows.N, rows.D, K, P, perm_batch, line_mode, o, partials,
+                                                             partials_bytes, stream);
+}
+
+int mp_run_rows(const char* who, int stat, const float* values, int64_t N, int64_t D, const int64_t* nbr, const int32_t* perms, int32_t K,
+                int64_t P, int32_t perm_batch, int32_t line_mode, const MpOut& o, void* partials, size_t partials_bytes, void* stream) {
+  const DenseRows r{values, N, D};
+  return stat == STAT_GEARY ? mp_run<DenseRows, STAT_GEARY>(who, r, nbr, perms, N, D, K, P, perm_batch, line_mode, o, partials,
+                                                            partials_bytes, stream)
+                            : mp_run<DenseRows, STAT_MORAN>(who, r, nbr, perms, N, D, K, P, perm_batch, line_mode, o, partials,
+                                                            partials_bytes, stream);
+}
+
 }  // namespace grk
 }  // namespace gpz
 
@@ -297,9 +329,8 @@ extern "C" int gpz_gene_morans_perm_sparse_plan(int64_t N, int64_t D, int64_t nn
                                                 int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode,
                                                 int32_t* workgroups, int64_t* partials_bytes) {
   if (int rc = gr_check_shape("gpz_gene_morans_perm_sparse", N, D, nnz)) return rc;
-  MpPlan p;
-  if (int rc = mp_plan("gpz_gene_morans_perm_sparse", N, D, K, P, perm_batch_wanted, line_mode_wanted, true, nullptr, p)) return rc;
-  return mp_report(p, perm_batch, line_mode, workgroups, partials_bytes);
+  return mp_plan_query("gpz_gene_morans_perm_sparse", N, D, K, P, perm_batch_wanted, line_mode_wanted, true, perm_batch, line_mode,
+                       workgroups, partials_bytes);
 }
 
 extern "C" int gpz_gene_morans_perm_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
@@ -311,18 +342,16 @@ extern "C" int gpz_gene_morans_perm_sparse(const int64_t* row_ptr, const int32_t
   GPZ_REQUIRE(row_ptr && nbr && perms && I && n_ge && n_le && sim_mean && sim_m2 && info && partials, "%s: null pointer", who);
   if (int rc = gr_check_shape(who, N, D, nnz)) return rc;
   GPZ_REQUIRE(nnz == 0 || (row_spot && row_perm && col_val), "%s: null pointer (non-zeros)", who);
-  const SparseRows r{GrRows{row_ptr, row_spot, row_perm, col_val, N, D, nnz}};
-  return mp_run(who, r, nbr, perms, N, D, K, P, perm_batch, line_mode, MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials,
-                partials_bytes, stream);
+  return mp_run_sparse(who, STAT_MORAN, GrRows{row_ptr, row_spot, row_perm, col_val, N, D, nnz}, nbr, perms, K, P, perm_batch, line_mode,
+                       MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes, stream);
 }
 
 extern "C" int gpz_morans_perm_rows_plan(int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch_wanted,
                                          int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
                                          int64_t* partials_bytes) {
   if (int rc = gr_check_shape("gpz_morans_perm_rows", N, D, 0)) return rc;
-  MpPlan p;
-  if (int rc = mp_plan("gpz_morans_perm_rows", N, D, K, P, perm_batch_wanted, line_mode_wanted, false, nullptr, p)) return rc;
-  return mp_report(p, perm_batch, line_mode, workgroups, partials_bytes);
+  return mp_plan_query("gpz_morans_perm_rows", N, D, K, P, perm_batch_wanted, line_mode_wanted, false, perm_batch, line_mode, workgroups,
+                       partials_bytes);
 }
 
 extern "C" int gpz_morans_perm_rows(const float* values, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K,
@@ -332,7 +361,6 @@ extern "C" int gpz_morans_perm_rows(const float* values, const int64_t* nbr, con
   const char* who = "gpz_morans_perm_rows";
   GPZ_REQUIRE(values && nbr && perms && I && n_ge && n_le && sim_mean && sim_m2 && info && partials, "%s: null pointer", who);
   if (int rc = gr_check_shape(who, N, D, 0)) return rc;
-  const DenseRows r{values, N, D};
-  return mp_run(who, r, nbr, perms, N, D, K, P, perm_batch, line_mode, MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials,
-                partials_bytes, stream);
+  return mp_run_rows(who, STAT_MORAN, values, N, D, nbr, perms, K, P, perm_batch, line_mode,
+                     MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes, stream);
 }

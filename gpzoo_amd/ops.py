@@ -1617,7 +1617,9 @@ def morans_perm_plan(N: int, D: int, K: int, P: int, nnz: Optional[int] = None, 
     return dict(perm_batch=pb.value, line_mode=lm.value, workgroups=wg.value, partials_bytes=int(nb.value))
 
 
-def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, perms, return_sims, perm_batch, line_mode):
+def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, perms, return_sims, perm_batch, line_mode, stat=None):
+    """The call behind the four permutation entries; ``stat`` (0 Moran, 1 Geary) for those that take it, None for the
+    Moran-only ones.  Returns the tensors of a ``MoransPerm`` in its order."""
     if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
         raise ValueError(f"{who}: nbr must be an ({N}, K) integer table")
     if (not isinstance(perms, torch.Tensor) or perms.dim() != 2 or perms.shape[0] < 1 or perms.shape[1] != N
@@ -1630,7 +1632,10 @@ def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, pe
         perms = perms.to(device=dev, dtype=torch.int64).clamp(-1, N)                  # a wide entry stays out of range in 32 bits
     perms = perms.to(device=dev, dtype=torch.int32).contiguous()
     K, P = int(nbr.shape[1]), int(perms.shape[0])
-    plan = morans_perm_plan(N, D, K, P, nnz, perm_batch, _line_mode(who, line_mode))
+    if stat is None:
+        plan = morans_perm_plan(N, D, K, P, nnz, perm_batch, _line_mode(who, line_mode))
+    else:
+        plan = autocorr_perm_plan(N, D, K, P, nnz, _STATS[stat], perm_batch, _line_mode(who, line_mode))
     lib = _lib.load()
     I, mean, m2 = (torch.empty(D, dtype=torch.float64, device=dev) for _ in range(3))
     n_ge, n_le = (torch.empty(D, dtype=torch.int32, device=dev) for _ in range(2))
@@ -1638,8 +1643,8 @@ def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, pe
     info = torch.empty(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         ws = _workspace(dev, plan["partials_bytes"])
-        rc = getattr(lib, entry)(*inputs, _ptr(nbr), _ptr(perms), N, D, *(() if nnz is None else (nnz,)), K, P, plan["perm_batch"],
-                                 plan["line_mode"], _ptr(I), _ptr(sims), _ptr(n_ge), _ptr(n_le), _ptr(mean), _ptr(m2), _ptr(info),
+        rc = getattr(lib, entry)(*inputs, _ptr(nbr), _ptr(perms), N, D, *(() if nnz is None else (nnz,)), K, P,
+                                 *(() if stat is None else (stat,)), plan["perm_batch"], plan["line_mode"], _ptr(I), _ptr(sims), _ptr(n_ge), _ptr(n_le), _ptr(mean), _ptr(m2), _ptr(info),
                                  _ptr(ws), ws.numel(), _stream(dev))
     _lib.check(rc, entry)
     code = int(info.item())
@@ -1647,7 +1652,7 @@ def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, pe
         raise ValueError(f"{who}: the neighbour table has an entry outside [0, N) or naming its own row")
     if code != 0:
         raise ValueError(f"{who}: a row of perms is not a permutation of 0 .. N - 1 (an entry outside [0, N) or an index named twice)")
-    return MoransPerm(I, n_ge, n_le, mean, m2, sims)
+    return I, n_ge, n_le, mean, m2, sims
 
 
 @dataclass
@@ -1675,7 +1680,8 @@ def gene_morans_perm_sparse(values, nbr, perms, *, return_sims: bool = False, pe
     _need_cuda(v.col_val)
     D, N = v.shape
     inputs = (_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val))
-    return _morans_perm(who, "gpz_gene_morans_perm_sparse", N, D, v.nnz, v.device, inputs, nbr, perms, return_sims, perm_batch, line_mode)
+    return MoransPerm(*_morans_perm(who, "gpz_gene_morans_perm_sparse", N, D, v.nnz, v.device, inputs, nbr, perms, return_sims, perm_batch,
+                                    line_mode))
 
 
 def morans_perm_rows(values, nbr, perms, *, return_sims: bool = False, perm_batch: int = 0, line_mode=0) -> MoransPerm:
@@ -1688,7 +1694,166 @@ def morans_perm_rows(values, nbr, perms, *, return_sims: bool = False, perm_batc
     _need_cuda(values)
     V = values.detach().contiguous()
     D, N = V.shape
-    return _morans_perm(who, "gpz_morans_perm_rows", N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims, perm_batch, line_mode)
+    return MoransPerm(*_morans_perm(who, "gpz_morans_perm_rows", N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims, perm_batch,
+                                    line_mode))
+
+
+_STATS = {"moran": 0, "geary": 1, 0: "moran", 1: "geary"}
+
+
+def _stat(who: str, stat) -> int:
+    if not isinstance(stat, str) or stat not in ("moran", "geary"):
+        raise ValueError(f"{who}: stat {stat!r} unknown ('moran', 'geary')")
+    return _STATS[stat]
+
+
+@dataclass
+class SpatialStats:
+    """``gene_spatial_stats_sparse`` / ``spatial_stats``, fp64 per gene / column: Moran's ``I``, Geary's ``C``, ``mean``,
+    ``var`` (the population variance m2, zeros included) and ``kurtosis`` (b2 = m4 / m2^2)."""
+    I: torch.Tensor
+    C: torch.Tensor
+    mean: torch.Tensor
+    var: torch.Tensor
+    kurtosis: torch.Tensor
+
+
+def spatial_stats_plan(N: int, K: int, D: Optional[int] = None, nnz: Optional[int] = None, L: Optional[int] = None) -> dict:
+    """How ``gene_spatial_stats_sparse`` (``D`` genes, ``nnz`` stored entries) or ``spatial_stats`` (``L`` columns) covers a
+    shape (gpz_gene_spatial_stats_sparse_plan / gpz_spatial_stats_plan, host-only queries: no device needed):
+    ``gene_chunk``, ``workgroups``, ``partials_bytes``, or ``row_chunk``, ``chunks``, ``partials_bytes``."""
+    lib = _lib.load()
+    nb = C.c_int64()
+    if L is not None:
+        rc_, ch = C.c_int32(), C.c_int64()
+        if lib.gpz_spatial_stats_plan(int(N), int(L), int(K), C.byref(rc_), C.byref(ch), C.byref(nb)) != 0:
+            raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+        return dict(row_chunk=rc_.value, chunks=int(ch.value), partials_bytes=int(nb.value))
+    gc, wg = C.c_int32(), C.c_int32()
+    if lib.gpz_gene_spatial_stats_sparse_plan(int(N), int(D), int(nnz), int(K), C.byref(gc), C.byref(wg), C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, workgroups=wg.value, partials_bytes=int(nb.value))
+
+
+def gene_spatial_stats_sparse(values, nbr) -> SpatialStats:
+    """Moran's I, Geary's C, the mean, the variance and the kurtosis of every gene of a whole ``SparseCounts`` /
+    ``SparseExpression`` over the neighbour table nbr (N,K) int64 of distinct neighbours, 1 <= K <= 32
+    (gpz_gene_spatial_stats_sparse), from sums over the stored entries, zeros included: a ``SpatialStats`` of (D,) fp64
+    tensors.  ``I`` is ``gene_morans_i_sparse``'s, bit for bit.  The offset of a ``SparseExpression`` moves the mean and
+    nothing else.  I, C and the kurtosis are NaN for a gene without stored entries and for a constant one.  A table entry
+    outside [0, N) or naming its own row raises ValueError (checked on the device; one synchronisation)."""
+    from .likelihoods import SparseExpression
+    who = "gene_spatial_stats_sparse"
+    v = _whole_values(values, who)
+    _need_cuda(v.col_val)
+    D, N = v.shape
+    dev = v.device
+    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
+        raise ValueError(f"{who}: nbr must be an ({N}, K) integer table")
+    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
+    K = int(nbr.shape[1])
+    plan = spatial_stats_plan(N, K, D=D, nnz=v.nnz)
+    lib = _lib.load()
+    out = [torch.empty(D, dtype=torch.float64, device=dev) for _ in range(5)]
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, plan["partials_bytes"])
+        rc = lib.gpz_gene_spatial_stats_sparse(_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val), _ptr(nbr), N, D,
+                                               v.nnz, K, *(_ptr(t) for t in out), _ptr(info), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_gene_spatial_stats_sparse")
+    if int(info.item()) != 0:
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, N) or naming its own row")
+    if isinstance(values, SparseExpression):
+        out[2] = out[2] - values.offset.to(device=dev, dtype=torch.float64)
+    return SpatialStats(*out)
+
+
+@_on_device
+def spatial_stats(values, nbr) -> SpatialStats:
+    """``gene_spatial_stats_sparse`` for the columns of values (N,L), fp32 or fp64, as ``morans_i`` takes them
+    (gpz_spatial_stats): a ``SpatialStats`` of (L,) fp64 tensors from centred sums; ``I`` is ``morans_i``'s, bit for bit.  A
+    constant column gives NaN in I, C and the kurtosis."""
+    _need_cuda(values)
+    V = values.detach().contiguous()
+    if V.dim() != 2 or nbr.dim() != 2 or nbr.shape[0] != V.shape[0]:
+        raise ValueError(f"spatial_stats: values (N, L) and nbr (N, K) expected, got {tuple(V.shape)} and {tuple(nbr.shape)}")
+    nbr = nbr.to(device=V.device, dtype=torch.int64).contiguous()
+    N, L = V.shape
+    K = nbr.shape[1]
+    plan = spatial_stats_plan(N, K, L=L)
+    lib = _lib.load()
+    out = [torch.empty(L, dtype=torch.float64, device=V.device) for _ in range(5)]
+    info = torch.empty(1, dtype=torch.int32, device=V.device)
+    ws = _workspace(V.device, plan["partials_bytes"])
+    rc = lib.gpz_spatial_stats(_ptr(V), N, L, _dt(V), _ptr(nbr), K, *(_ptr(t) for t in out), _ptr(info), _ptr(ws), ws.numel(),
+                               _stream(V.device))
+    _lib.check(rc, "gpz_spatial_stats")
+    if int(info.item()) != 0:
+        raise ValueError("spatial_stats: the neighbour table has an entry outside [0, N) or naming its own row")
+    return SpatialStats(*out)
+
+
+def autocorr_perm_plan(N: int, D: int, K: int, P: int, nnz: Optional[int] = None, stat: str = "moran", perm_batch: int = 0,
+                       line_mode=0) -> dict:
+    """``morans_perm_plan`` for ``gene_autocorr_perm_sparse`` (``nnz`` stored entries) or ``autocorr_perm_rows``
+    (``nnz=None``) (gpz_gene_autocorr_perm_sparse_plan / gpz_autocorr_perm_rows_plan, host-only queries)."""
+    lib = _lib.load()
+    st = _stat("autocorr_perm_plan", stat)
+    pb, lm, wg, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    mode = _line_mode("autocorr_perm_plan", line_mode)
+    outs = (C.byref(pb), C.byref(lm), C.byref(wg), C.byref(nb))
+    if nnz is None:
+        rc = lib.gpz_autocorr_perm_rows_plan(int(N), int(D), int(K), int(P), st, int(perm_batch), mode, *outs)
+    else:
+        rc = lib.gpz_gene_autocorr_perm_sparse_plan(int(N), int(D), int(nnz), int(K), int(P), st, int(perm_batch), mode, *outs)
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(perm_batch=pb.value, line_mode=lm.value, workgroups=wg.value, partials_bytes=int(nb.value))
+
+
+@dataclass
+class AutocorrPerm:
+    """``gene_autocorr_perm_sparse`` / ``autocorr_perm_rows``: ``stat`` ("moran" or "geary"); ``value`` (D,) fp64, the
+    observed I or C; ``n_ge`` / ``n_le`` (D,) int32, the permutations whose statistic is >= / <= the observed one;
+    ``sim_mean`` and ``sim_m2`` (D,) fp64, the mean of the simulated statistic and the sum of its squared deviations;
+    ``sims`` (D, P) fp64 or None."""
+    stat: str
+    value: torch.Tensor
+    n_ge: torch.Tensor
+    n_le: torch.Tensor
+    sim_mean: torch.Tensor
+    sim_m2: torch.Tensor
+    sims: Optional[torch.Tensor]
+
+
+def gene_autocorr_perm_sparse(values, nbr, perms, *, stat: str = "moran", return_sims: bool = False, perm_batch: int = 0,
+                              line_mode=0) -> AutocorrPerm:
+    """``gene_morans_perm_sparse`` with the statistic as an argument (gpz_gene_autocorr_perm_sparse): ``stat="moran"`` gives
+    its bits; ``stat="geary"`` Geary's C of every gene (``gene_spatial_stats_sparse``'s, bit for bit) and of its P
+    relabellings, compared on Q_in - 2 C_s in fp64, exact for integer-valued data.  An ``AutocorrPerm``."""
+    who = "gene_autocorr_perm_sparse"
+    st = _stat(who, stat)
+    v = _whole_values(values, who)
+    _need_cuda(v.col_val)
+    D, N = v.shape
+    inputs = (_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val))
+    return AutocorrPerm(stat, *_morans_perm(who, "gpz_gene_autocorr_perm_sparse", N, D, v.nnz, v.device, inputs, nbr, perms, return_sims,
+                                            perm_batch, line_mode, st))
+
+
+def autocorr_perm_rows(values, nbr, perms, *, stat: str = "moran", return_sims: bool = False, perm_batch: int = 0,
+                       line_mode=0) -> AutocorrPerm:
+    """``gene_autocorr_perm_sparse`` for a dense fp32 (D, N) tensor, one gene per row (gpz_autocorr_perm_rows): every spot is
+    an entry, zeros included; ``stat="moran"`` gives the bits of ``morans_perm_rows``."""
+    who = "autocorr_perm_rows"
+    st = _stat(who, stat)
+    if not isinstance(values, torch.Tensor) or values.dim() != 2 or values.dtype != torch.float32:
+        raise ValueError(f"{who}: a dense (D, N) float32 tensor expected")
+    _need_cuda(values)
+    V = values.detach().contiguous()
+    D, N = V.shape
+    return AutocorrPerm(stat, *_morans_perm(who, "gpz_autocorr_perm_rows", N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims,
+                                            perm_batch, line_mode, st))
 
 
 def gene_dispersion_plan(N: int, D: int, nnz: int) -> dict:

@@ -333,7 +333,7 @@ def train_closure_batched(model, optimizer, X, groupsX, y, device=None, steps=20
     return losses
 
 
-def dims_autocorr(factors, coords, sort=True, *, n_neighs=6):
+def dims_autocorr(factors, coords, sort=True, *, n_neighs=6, mode="moran"):
     """Moran's I of every column of ``factors`` (N,L) over the directed ``n_neighs``-nearest-neighbour graph of
     ``coords`` (N,d), d <= 4 -- the reference's dims_autocorr (utilities.py:131-156), which builds that graph with
     squidpy's ``spatial_neighbors`` (generic coordinates, 6 neighbours, self excluded) and scores it with
@@ -347,9 +347,14 @@ def dims_autocorr(factors, coords, sort=True, *, n_neighs=6):
     reference's ``df.sort_index()`` over AnnData's default names "0" ... "L-1", which is a STRING sort -- for L >= 11 the
     order is 0, 1, 10, 11, ..., 19, 2, 20, ...; idx and I stay aligned either way.  The reference's
     ``print('here_andata')`` is not reproduced.  For permutation p-values of the factors, score them as genes:
-    ``gene_autocorr(factors.T, coords, n_perms=...)``."""
+    ``gene_autocorr(factors.T, coords, n_perms=...)``.
+
+    ``mode="geary"`` scores Geary's C instead (``ops.spatial_stats``; squidpy's ``mode="geary"``) and returns ``(idx, C)``;
+    ``sort=True`` is then by increasing C -- the most autocorrelated factor first, as with I -- NaN last."""
     import numpy as np
     from . import ops
+    if mode not in ("moran", "geary"):
+        raise ValueError(f"dims_autocorr: mode={mode!r} unknown ('moran', 'geary')")
 
     def as_tensor(a):
         return a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
@@ -377,9 +382,12 @@ def dims_autocorr(factors, coords, sort=True, *, n_neighs=6):
     X, F = X.to(dev), F.to(dev)
     if not bool(torch.isfinite(X).all()):
         raise ValueError("dims_autocorr: coords hold a non-finite value")
-    I = ops.morans_i(F, ops.spatial_knn(X, k)).cpu().numpy()
+    if mode == "geary":
+        I = ops.spatial_stats(F, ops.spatial_knn(X, k)).C.cpu().numpy()
+    else:
+        I = ops.morans_i(F, ops.spatial_knn(X, k)).cpu().numpy()
     if sort:
-        order = np.argsort(-I, kind="stable")                 # NaN (-NaN) sorts last; ties keep column order
+        order = np.argsort(I if mode == "geary" else -I, kind="stable")      # NaN (-NaN) sorts last; ties keep column order
     else:
         order = np.array(sorted(range(L), key=str), dtype=np.int64)
     return order.astype(np.int64), I[order]
@@ -736,6 +744,97 @@ class GeneAutocorrPerm(NamedTuple):
     sims: Optional[torch.Tensor]
 
 
+class GeneGeary(NamedTuple):
+    """``gene_autocorr(mode="geary")``: Geary's C per gene and its moments, fp64 tensors: ``C`` (D,), ``expected`` = 1,
+    ``variance`` (a scalar under normality, (D,) under randomisation) and ``z`` = (C - 1) / sqrt(variance) (D,).  Mind the
+    sign: C < 1, a NEGATIVE z, is positive spatial autocorrelation (neighbours are alike); C > 1 is negative."""
+    C: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+
+
+class GeneGearyPerm(NamedTuple):
+    """``gene_autocorr(mode="geary", n_perms=)``: the fields of ``GeneAutocorrPerm`` with ``C`` for ``I``.  ``n_ge`` /
+    ``n_le`` count the permutations whose C is >= / <= the observed one, so ``pval_less`` = (n_le + 1) / (P + 1) is the one
+    for positive autocorrelation (a small C), ``pval_greater`` the one for negative; ``pval_sim`` is the smaller of the two."""
+    C: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+    n_perms: int
+    n_ge: torch.Tensor
+    n_le: torch.Tensor
+    pval_greater: torch.Tensor
+    pval_less: torch.Tensor
+    pval_sim: torch.Tensor
+    mean_sim: torch.Tensor
+    var_sim: torch.Tensor
+    z_sim: torch.Tensor
+    pval_z_sim: torch.Tensor
+    sims: Optional[torch.Tensor]
+
+
+def _autocorr_moments(nbr, kurtosis=None):
+    """The moments of Moran's I and Geary's C over the table nbr (N, K) of distinct neighbours without self edges, the
+    sibling of ``_moran_moments``: a dict of fp64 tensors on the table's device with ``EI`` = -1 / (N - 1), ``EC`` = 1, the
+    normality variances ``VI_norm`` and ``VC_norm`` (scalars) and, with ``kurtosis`` (the (D,) b2 of the genes; N >= 4), the
+    randomisation variances ``VI_rand`` and ``VC_rand`` (D,) -- the exact variances over all N! relabellings of the spots
+    (Cliff & Ord; PySAL's VI_rand, VC_rand).  Binary weights (both ratios are the same for weights 1 / K):
+    S0 = N K, S1 = N K + m2 with m2 directed edges whose reverse is an edge, S2 = sum_i (K + indeg_i)^2, counted once as
+    integers; every variance is a - b2 b with a and b exact rationals of those, rounded once."""
+    from fractions import Fraction as Fr
+    n, K = (int(v) for v in nbr.shape)
+    rows = torch.arange(n, dtype=torch.int64, device=nbr.device)[:, None]
+    forward, backward = (rows * n + nbr).reshape(-1), (nbr * n + rows).reshape(-1)
+    indeg = torch.bincount(nbr.reshape(-1), minlength=n)
+    S0, S1, S2 = n * K, n * K + int(torch.isin(forward, backward).sum()), int(((K + indeg) ** 2).sum())
+
+    def t(v):
+        return torch.tensor(float(v), dtype=torch.float64, device=nbr.device)
+
+    EI2 = Fr(1, (n - 1) ** 2)
+    out = dict(EI=t(Fr(-1, n - 1)), EC=t(1), S0=S0, S1=S1, S2=S2,
+               VI_norm=t(Fr(n * n * S1 - n * S2 + 3 * S0 * S0, (n * n - 1) * S0 * S0) - EI2),
+               VC_norm=t(Fr((2 * S1 + S2) * (n - 1) - 4 * S0 * S0, 2 * (n + 1) * S0 * S0)))
+    if kurtosis is not None:
+        if n < 4:
+            raise ValueError(f"the randomisation variance needs N >= 4 spots, got {n}")
+        b2 = kurtosis.to(torch.float64)
+        dI, dC = (n - 1) * (n - 2) * (n - 3) * S0 * S0, n * (n - 2) * (n - 3) * S0 * S0
+        aI = Fr(n * ((n * n - 3 * n + 3) * S1 - n * S2 + 3 * S0 * S0), dI) - EI2
+        bI = Fr((n * n - n) * S1 - 2 * n * S2 + 6 * S0 * S0, dI)
+        aC = Fr(4 * (n - 1) * S1 * (n * n - 3 * n + 3) - (n - 1) * S2 * (n * n + 3 * n - 6) + 4 * S0 * S0 * (n * n - 3), 4 * dC)
+        bC = Fr(4 * (n - 1) ** 2 * S1 - (n - 1) * S2 * (n * n - n + 2) + 4 * S0 * S0 * (n - 1) ** 2, 4 * dC)
+        out["VI_rand"] = t(aI) - b2 * t(bI)
+        out["VC_rand"] = t(aC) - b2 * t(bC)
+    return out
+
+
+def _ring(N, device):
+    """The (N, 1) table i -> i + 1 mod N: a valid graph for a call that wants the moments of the values alone."""
+    return ((torch.arange(N, dtype=torch.int64, device=device) + 1) % N)[:, None].contiguous()
+
+
+def gene_kurtosis(values):
+    """(D,) fp64 kurtosis b2 = m4 / m2^2 of every gene, zeros included (m_k = sum (x - mean)^k / N; 3 for a normal sample):
+    what the randomisation variance of ``gene_autocorr(assumption="randomisation")`` depends on beside the graph.
+    ``values`` as for ``gene_autocorr``: a whole ``SparseCounts`` / ``SparseExpression``, swept twice over its stored entries
+    (``ops.gene_spatial_stats_sparse``), or a dense (D, N) tensor (``ops.spatial_stats``).  NaN for a constant gene."""
+    from . import ops
+    from .likelihoods import SparseCounts, SparseExpression
+    if isinstance(values, (SparseCounts, SparseExpression)):
+        v = ops._whole_values(values, "gene_kurtosis")
+        if v.shape[1] < 2:
+            raise ValueError("gene_kurtosis: at least 2 spots needed")
+        return ops.gene_spatial_stats_sparse(values, _ring(v.shape[1], v.device)).kurtosis
+    if not isinstance(values, torch.Tensor) or values.dim() != 2 or not values.is_floating_point() or values.shape[1] < 2:
+        raise ValueError("gene_kurtosis: a SparseCounts, a SparseExpression or a dense (D, N >= 2) floating-point tensor expected")
+    V = values.detach()
+    V = (V if V.dtype in (torch.float32, torch.float64) else V.float()).T.contiguous()
+    return ops.spatial_stats(V, _ring(V.shape[0], V.device)).kurtosis
+
+
 def _autocorr_perms(who, N, n_perms, perms):
     """The checked arguments of the permutation null: (P, perms or None)."""
     import numpy as np
@@ -751,7 +850,8 @@ def _autocorr_perms(who, N, n_perms, perms):
     return n_perms, None
 
 
-def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, seed=0, perms=None, return_sims=False):
+def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, seed=0, perms=None, return_sims=False,
+                  mode="moran", assumption="normality"):
     """Moran's I of every gene over the spots' directed ``n_neighs``-nearest-neighbour graph -- squidpy's
     ``spatial_autocorr(mode="moran")`` with one gene per column, the other standard ranking of spatial data.  ``values``: a
     whole ``SparseCounts`` or ``SparseExpression`` (the offset does not change I), scored from its stored entries
@@ -768,11 +868,26 @@ def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, 
     (D, P) simulated values.  This permutes the spot labels against a fixed graph, which is PySAL's definition; squidpy
     shuffles the rows of its adjacency matrix instead -- both are null models of exchangeable spots, but the numbers differ
     draw by draw.  The smallest attainable p-value is 1 / (P + 1).  The comparisons I_pi >= I are exact for integer-valued
-    data (counts), ties included; for other values a mathematical tie may fall either way in the last bit."""
+    data (counts), ties included; for other values a mathematical tie may fall either way in the last bit.
+
+    ``mode="geary"`` scores Geary's C instead, squidpy's ``spatial_autocorr(mode="geary")``: squared differences along the
+    edges over the variance, 1 in expectation and BELOW 1 for positive autocorrelation, more sensitive to local structure
+    than I.  It returns a ``GeneGeary`` -- ``z`` = (C - 1) / sqrt(variance), negative for positive autocorrelation -- or with
+    permutations a ``GeneGearyPerm``, whose ``pval_less`` is the one for positive autocorrelation
+    (``ops.gene_spatial_stats_sparse`` / ``ops.spatial_stats``, ``ops.gene_autocorr_perm_sparse`` /
+    ``ops.autocorr_perm_rows``).  ``assumption="randomisation"`` replaces the normality moments, which depend on the graph
+    alone, by the randomisation moments of Cliff & Ord (PySAL's ``VI_rand`` / ``VC_rand``): ``variance`` and ``z`` become
+    (D,) tensors that depend on each gene's kurtosis (``gene_kurtosis``).  They are the exact mean and variance of the
+    statistic over all N! relabellings of the spots -- what the permutation null samples -- and for counts, which are far
+    from normal, the ones to use; N >= 4 is needed.  Both defaults give the call without these keywords, bit for bit."""
     import numpy as np
     from . import ops
     from .likelihoods import SparseCounts, SparseExpression, TransposedCounts
     who = "gene_autocorr"
+    if mode not in ("moran", "geary"):
+        raise ValueError(f"{who}: mode={mode!r} unknown ('moran', 'geary')")
+    if assumption not in ("normality", "randomisation"):
+        raise ValueError(f"{who}: assumption={assumption!r} unknown ('normality', 'randomisation')")
     if isinstance(values, TransposedCounts):
         raise TypeError(f"{who}: values is the .T (obs x feat) of a SparseCounts; pass the SparseCounts itself (genes x spots)")
     sparse = isinstance(values, (SparseCounts, SparseExpression))
@@ -784,6 +899,8 @@ def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, 
         raise ValueError(f"{who}: a dense (D, N) floating-point tensor expected, got {tuple(values.shape)} of {values.dtype}")
     D, N = values.shape
     dev = values.device
+    if assumption == "randomisation" and N < 4:
+        raise ValueError(f"{who}: assumption='randomisation' needs N >= 4 spots, got {N}")
     permute = n_perms is not None or perms is not None
     if permute:
         P, perms = _autocorr_perms(who, N, n_perms, perms)
@@ -813,6 +930,8 @@ def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, 
         perms = torch.empty((P, N), dtype=torch.int32, device=dev)
         for p in range(P):
             perms[p] = torch.randperm(N, generator=g, device=dev)
+    if mode == "geary" or assumption == "randomisation":
+        return _gene_autocorr_stats(values, sparse, nbr, perms if permute else None, return_sims, mode, assumption)
     if sparse and permute:
         r = ops.gene_morans_perm_sparse(values, nbr, perms, return_sims=return_sims)
         I = r.I
@@ -827,6 +946,12 @@ def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, 
     base = GeneAutocorr(I, expected, variance, (I - expected) / torch.sqrt(variance))
     if not permute:
         return base
+    return GeneAutocorrPerm(*base, *_perm_fields(I, r, P))
+
+
+def _perm_fields(I, r, P):
+    """The fields of ``GeneAutocorrPerm`` / ``GeneGearyPerm`` after ``z``, from the observed statistic and the permutation
+    entry's result."""
     nan = torch.isnan(I) | torch.isnan(r.sim_mean)
     quiet = torch.full_like(I, float("nan"))
     n_ge, n_le = (torch.where(nan, torch.zeros_like(n), n) for n in (r.n_ge, r.n_le))
@@ -835,7 +960,32 @@ def gene_autocorr(values, coords=None, *, n_neighs=6, graph=None, n_perms=None, 
     var_sim = torch.where(nan, quiet, r.sim_m2 / P)
     z_sim = torch.where(var_sim > 0, (I - mean_sim) / torch.sqrt(var_sim), quiet)
     pval_z = 0.5 * torch.erfc(z_sim.abs() / 2.0 ** 0.5)
-    return GeneAutocorrPerm(*base, P, n_ge, n_le, pg, pl, torch.minimum(pg, pl), mean_sim, var_sim, z_sim, pval_z, r.sims)
+    return P, n_ge, n_le, pg, pl, torch.minimum(pg, pl), mean_sim, var_sim, z_sim, pval_z, r.sims
+
+
+def _gene_autocorr_stats(values, sparse, nbr, perms, return_sims, mode, assumption):
+    """``gene_autocorr`` beyond its defaults: Geary's C and / or the randomisation moments, through the entries that give C
+    and the kurtosis beside I."""
+    from . import ops
+    if sparse:
+        st = ops.gene_spatial_stats_sparse(values, nbr)
+    else:
+        V = values.detach()
+        st = ops.spatial_stats((V if V.dtype in (torch.float32, torch.float64) else V.float()).T.contiguous(), nbr)
+    stat = st.C if mode == "geary" else st.I
+    if perms is not None and sparse:
+        r = ops.gene_autocorr_perm_sparse(values, nbr, perms, stat=mode, return_sims=return_sims)
+        stat = r.value                                   # st's, bit for bit
+    elif perms is not None:
+        r = ops.autocorr_perm_rows(values.detach().float(), nbr, perms, stat=mode, return_sims=return_sims)
+    m = _autocorr_moments(nbr, st.kurtosis if assumption == "randomisation" else None)
+    key = ("VC" if mode == "geary" else "VI") + ("_rand" if assumption == "randomisation" else "_norm")
+    expected, variance = m["EC" if mode == "geary" else "EI"], m[key]
+    kinds = (GeneGeary, GeneGearyPerm) if mode == "geary" else (GeneAutocorr, GeneAutocorrPerm)
+    base = kinds[0](stat, expected, variance, (stat - expected) / torch.sqrt(variance))
+    if perms is None:
+        return base
+    return kinds[1](*base, *_perm_fields(stat, r, int(perms.shape[0])))
 
 
 def fdr_bh(p):
@@ -878,7 +1028,8 @@ def rank_genes(counts, by="deviance", *, coords=None, nfeat=None, **kw):
     """``(order, score)`` of the genes of a whole ``SparseCounts``: ``order`` int64 (D,), or (nfeat,), in decreasing score
     (NaN last, ties in gene order), ``score`` fp64 aligned with it; ``counts.select_genes(order)`` is then the reference's
     ``ad[:, :nfeat]`` of a data set sorted by importance.  ``by``: "deviance" (``gene_deviance``, Poisson),
-    "binomial_deviance", "moran" (``gene_autocorr`` of ``log_normalize(counts, center=False)`` over ``coords``), or
+    "binomial_deviance", "moran" (``gene_autocorr`` of ``log_normalize(counts, center=False)`` over ``coords``), "geary"
+    (1 - C of the same values, ``gene_autocorr(mode="geary")``: larger is more autocorrelated, as with every score), or
     "overdispersion" (``gene_dispersion(counts).lr``, the likelihood-ratio statistic of NB against Poisson).  Extra
     keywords go to the scorer."""
     if by == "deviance":
@@ -890,10 +1041,15 @@ def rank_genes(counts, by="deviance", *, coords=None, nfeat=None, **kw):
         if coords is None and kw.get("graph") is None:
             raise ValueError("rank_genes: by='moran' needs coords (or graph=)")
         score = gene_autocorr(log_normalize(counts, center=False), coords, **kw).I
+    elif by == "geary":
+        _whole_counts_only(counts, "rank_genes")
+        if coords is None and kw.get("graph") is None:
+            raise ValueError("rank_genes: by='geary' needs coords (or graph=)")
+        score = 1.0 - gene_autocorr(log_normalize(counts, center=False), coords, mode="geary", **kw).C
     elif by == "overdispersion":
         score = gene_dispersion(counts, **kw).lr
     else:
-        raise ValueError(f"rank_genes: by={by!r} unknown ('deviance', 'binomial_deviance', 'moran', 'overdispersion')")
+        raise ValueError(f"rank_genes: by={by!r} unknown ('deviance', 'binomial_deviance', 'moran', 'geary', 'overdispersion')")
     order = _rank_order(score, nfeat)
     return order, score[order]
 

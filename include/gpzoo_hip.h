@@ -72,7 +72,11 @@
  * model did not explain, and in which genes), dense counts or counts stored as their non-zeros; scratch `partials` again;
  * gpz_gene_morans_perm_sparse, gpz_morans_perm_rows and their host-only *_plan queries -- Moran's I of every gene under P
  * relabellings of the spots (the permutation null of squidpy's spatial_autocorr(n_perms=)): the simulated values, the counts
- * behind the pseudo p-value and the simulated mean and variance, from stored non-zeros or dense rows; scratch `partials`.
+ * behind the pseudo p-value and the simulated mean and variance, from stored non-zeros or dense rows; scratch `partials`;
+ * gpz_gene_spatial_stats_sparse, gpz_spatial_stats, gpz_gene_autocorr_perm_sparse, gpz_autocorr_perm_rows and their host-only
+ * *_plan queries -- Moran's I and Geary's C (squidpy's spatial_autocorr(mode="geary")) of every gene with its mean, variance and
+ * kurtosis, which the randomisation variances of both statistics need, and the permutation entries with the statistic as an
+ * argument; scratch `partials`.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -537,6 +541,66 @@ int gpz_morans_perm_rows_plan(int64_t N, int64_t D, int32_t K, int64_t P, int32_
 int gpz_morans_perm_rows(const float* values, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K, int64_t P,
                          int32_t perm_batch, int32_t line_mode, double* I, double* sims, int32_t* n_ge, int32_t* n_le,
                          double* sim_mean, double* sim_m2, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+
+/* Moran's I, Geary's C and the moments of every gene (csrc/spatial_stats.hip, csrc/geary_expr.h).  Over the table nbr (N, K) int64
+ * of distinct neighbours without self edges, with binary weights (both ratios are the same for weights 1 / K):
+ *   C = (N - 1) G / ( 2 N K sum_i (x_i - xbar)^2 ),   G = sum_i sum_{j in nbr(i)} (x_i - x_j)^2,
+ * 1 in expectation, below 1 for positive autocorrelation.  Outputs, fp64, one value per gene / column; each of the five may be
+ * NULL and is then not computed:
+ *   I          gpz_gene_morans_i_sparse's / gpz_morans_i's, bit for bit
+ *   C          Geary's C
+ *   mean, var  xbar and m2 = sum (x - xbar)^2 / N (zeros included)
+ *   kurtosis   b2 = m4 / m2^2, m4 = sum (x - xbar)^4 / N: what the randomisation variances of I and C (Cliff & Ord; PySAL's
+ *              VI_rand, VC_rand) depend on beside the graph
+ * gpz_gene_spatial_stats_sparse: the by-gene arrays of a WHOLE data set stored as its non-zeros and 1 <= K <= 32, K < N, as
+ * gpz_gene_morans_i_sparse, one workgroup per gene at a time over the same line of N floats.  With its sums S, Q, C_s and
+ *   Q_in = sum_{i stored} indeg(i) x_i^2:   G = K Q + Q_in - 2 C_s,   C = (N - 1) G / ( 2 N K (Q - N xbar^2) );
+ * a constant added to every spot of a gene leaves G as it is.  A nearly constant gene loses digits in proportion to
+ * mean^2 / variance, in G as in the denominator.  mean = S / N; var and kurtosis come from a second sweep of the row,
+ *   m_k = [ sum_{stored} (x - xbar)^k + (N - stored) xbar^k ] / N, sums of non-negative terms.  I, C and kurtosis are NaN for
+ * a gene without stored entries and for a gene stored at every spot with one single value, and I and C wherever the
+ * denominator is <= 0 (gpz_gene_morans_i_sparse's rule); mean and var are 0 and the value for those.
+ * gpz_spatial_stats: the first L columns of values (N, L), fp32 or fp64 (dtype), 1 <= K < N, as gpz_morans_i takes them, in its
+ * arithmetic: z = v - mean, G = sum_i sum_j (z_i - z_j)^2 a sum of non-negative terms, var = sum z^2 / N, m4 = sum z^4 / N.  A
+ * constant column gives NaN in I, C and kurtosis (0 / 0).
+ * info[0] (device int32) is set to 1 by an entry of nbr outside [0, N) or naming its own row, which is not read and not
+ * counted.  Every accumulation is fp64 in a fixed order with no atomics on values: two calls agree bit for bit.  The scratch is
+ * `partials`, sized by the host-only plan query (any out pointer may be NULL), and need not be cleared: workgroups x N x 4 + N x 4
+ * bytes for the sparse entry (gene_chunk, workgroups as gpz_gene_morans_i_sparse_plan), 40 bytes per chunk of row_chunk rows
+ * and column plus 8 per column for the other.  Nothing of D x N or nnz elements is allocated.  partials 16-byte aligned.
+ * Argument errors return -1 before any launch with the reason in gpz_last_error. */
+int gpz_gene_spatial_stats_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int32_t* gene_chunk, int32_t* workgroups,
+                                       int64_t* partials_bytes);
+int gpz_gene_spatial_stats_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                  const int64_t* nbr, int64_t N, int64_t D, int64_t nnz, int32_t K, double* I, double* C, double* mean,
+                                  double* var, double* kurtosis, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+int gpz_spatial_stats_plan(int64_t N, int64_t L, int32_t K, int32_t* row_chunk, int64_t* chunks, int64_t* partials_bytes);
+int gpz_spatial_stats(const void* values, int64_t N, int64_t L, int32_t dtype, const int64_t* nbr, int32_t K, double* I, double* C,
+                      double* mean, double* var, double* kurtosis, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+
+/* gpz_gene_morans_perm_sparse / gpz_morans_perm_rows with the statistic as an argument: stat 0 Moran's I, 1 Geary's C.  With
+ * stat = 0 every output has the bits of those entries.  With stat = 1: value = the C of gpz_gene_spatial_stats_sparse, bit for
+ * bit (the rows entry: the same expansion over all N spots); sims (D, P), may be NULL, C_pi -- under a relabelling only
+ * Q_in,pi = sum_{i stored} indeg_pi(i) x_i^2 and C_s,pi change; n_ge / n_le the permutations with C_pi >= C and C_pi <= C,
+ * decided on Q_in - 2 C_s in fp64, exact for integer-valued data below 2^53 (n_le counts towards positive autocorrelation);
+ * sim_mean, sim_m2 of C_pi.  Everything else -- the arguments, info (1 a bad entry of nbr, 2 a row of perms that is no
+ * permutation), line_mode, perm_batch, the plan query, reproducibility, independence of perm_batch and line_mode, an identity
+ * row of perms giving the observed bits -- is as described there. */
+int gpz_gene_autocorr_perm_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int64_t P, int32_t stat, int32_t perm_batch_wanted,
+                                       int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
+                                       int64_t* partials_bytes);
+int gpz_gene_autocorr_perm_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                  const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int64_t nnz, int32_t K, int64_t P,
+                                  int32_t stat, int32_t perm_batch, int32_t line_mode, double* value, double* sims, int32_t* n_ge,
+                                  int32_t* n_le, double* sim_mean, double* sim_m2, int32_t* info, void* partials, size_t partials_bytes,
+                                  void* stream);
+int gpz_autocorr_perm_rows_plan(int64_t N, int64_t D, int32_t K, int64_t P, int32_t stat, int32_t perm_batch_wanted,
+                                int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
+                                int64_t* partials_bytes);
+int gpz_autocorr_perm_rows(const float* values, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K, int64_t P,
+                           int32_t stat, int32_t perm_batch, int32_t line_mode, double* value, double* sims, int32_t* n_ge,
+                           int32_t* n_le, double* sim_mean, double* sim_m2, int32_t* info, void* partials, size_t partials_bytes,
+                           void* stream);
 
 /* Residuals of counts under the predictive mean rate of a fitted count model, and Moran's I of every gene's residuals
  * (csrc/residual.hip).  With m = exp(mean + scale^2 / 2) (lognormal_mean != 0; exp(mean) otherwise) the rate is
