@@ -25,8 +25,9 @@
 // itself at the start of the launch.  Per gene it scatters the row into the line, gathers the K neighbours of every stored
 // entry from it, and then clears exactly the words it scattered: O(nnz (K + 2)) memory operations, no search, and a
 // scratch of workgroups x N x 4 bytes whatever D is.  The in-degree of the table is counted once per call with integer
-// atomics (a histogram; no atomics on values); that pass also checks every entry of the table and raises info.  The Moran
-// kernels and the closing expression live in moran_expr.h, which moran_perm.hip (the permutation null) includes too.
+// atomics (a histogram; no atomics on values); that pass also checks every entry of the table and raises info.  The gene
+// pass, its host driver and the closing expressions live in moran_expr.h, which spatial_stats.hip (Geary's C and the moments
+// beside I: the same kernel, instantiated wide) and moran_perm.hip (the permutation null) include too.
 //
 // Built with -ffp-contract=off: every product and sum of the closing formulas is rounded on its own, so the numbers are
 // those of the same expressions written in numpy (the CPU tests evaluate them that way), not of a compiler's choice of fma.
@@ -94,25 +95,17 @@ __global__ __launch_bounds__(GR_THREADS) void gr_deviance_kernel(GrRows r, const
   }
 }
 
-struct GrPlan {
-  double* total;      // deviance: S
-  int32_t* indeg;     // Moran: (N,)
-  float* lines;       // Moran: (workgroups, N)
+struct GrPlan {        // the deviance pass; the Moran pass has GenePass of moran_expr.h
+  double* total;      // S
   int workgroups;
   size_t bytes;
 };
 
-static GrPlan gr_plan(int64_t N, int64_t D, bool moran, void* scratch) {
+static GrPlan gr_plan(int64_t D, void* scratch) {
   Carver c(scratch);
   GrPlan p{};
-  const int cap = moran ? GR_MAX_WG : GR_DEV_WG;
-  p.workgroups = int(D < cap ? D : cap);
-  if (moran) {
-    p.indeg = c.take<int32_t>(size_t(N));
-    p.lines = c.take<float>(size_t(p.workgroups) * size_t(N));
-  } else {
-    p.total = c.take<double>(1);
-  }
+  p.workgroups = int(D < GR_DEV_WG ? D : GR_DEV_WG);
+  p.total = c.take<double>(1);
   p.bytes = c.used();
   return p;
 }
@@ -126,7 +119,7 @@ using namespace gpz::grk;
 extern "C" int gpz_gene_deviance_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t* gene_chunk, int32_t* workgroups,
                                              int64_t* partials_bytes) {
   if (int rc = gr_check_shape("gpz_gene_deviance_sparse", N, D, nnz)) return rc;
-  const GrPlan p = gr_plan(N, D, false, nullptr);
+  const GrPlan p = gr_plan(D, nullptr);
   if (gene_chunk) *gene_chunk = GR_THREADS;
   if (workgroups) *workgroups = p.workgroups;
   if (partials_bytes) *partials_bytes = int64_t(p.bytes);
@@ -142,7 +135,7 @@ extern "C" int gpz_gene_deviance_sparse(const int64_t* row_ptr, const int32_t* r
   GPZ_REQUIRE(nnz == 0 || (row_spot && row_perm && col_val), "gpz_gene_deviance_sparse: null pointer (non-zeros)");
   GPZ_REQUIRE(family == 0 || family == 1, "gpz_gene_deviance_sparse: family %d unknown (0 Poisson, 1 binomial)", family);
   GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "gpz_gene_deviance_sparse: partials must be 16-byte aligned");
-  const GrPlan p = gr_plan(N, D, false, partials);
+  const GrPlan p = gr_plan(D, partials);
   GPZ_REQUIRE(partials_bytes >= p.bytes, "gpz_gene_deviance_sparse: partials too small (%zu bytes, %zu needed)", partials_bytes,
               p.bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -157,35 +150,13 @@ extern "C" int gpz_gene_deviance_sparse(const int64_t* row_ptr, const int32_t* r
 
 extern "C" int gpz_gene_morans_i_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int32_t* gene_chunk,
                                              int32_t* workgroups, int64_t* partials_bytes) {
-  if (int rc = gr_check_shape("gpz_gene_morans_i_sparse", N, D, nnz)) return rc;
-  if (int rc = gr_check_k("gpz_gene_morans_i_sparse", N, K)) return rc;
-  const GrPlan p = gr_plan(N, D, true, nullptr);
-  if (gene_chunk) *gene_chunk = GR_THREADS;
-  if (workgroups) *workgroups = p.workgroups;
-  if (partials_bytes) *partials_bytes = int64_t(p.bytes);
-  return 0;
+  return gene_pass_query("gpz_gene_morans_i_sparse", N, D, nnz, K, gene_chunk, workgroups, partials_bytes);
 }
 
 extern "C" int gpz_gene_morans_i_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
                                         const float* col_val, const int64_t* nbr, int64_t N, int64_t D, int64_t nnz, int32_t K,
                                         double* I, int32_t* info, void* partials, size_t partials_bytes, void* stream) {
-  GPZ_REQUIRE(row_ptr && nbr && I && info && partials, "gpz_gene_morans_i_sparse: null pointer");
-  if (int rc = gr_check_shape("gpz_gene_morans_i_sparse", N, D, nnz)) return rc;
-  if (int rc = gr_check_k("gpz_gene_morans_i_sparse", N, K)) return rc;
-  GPZ_REQUIRE(nnz == 0 || (row_spot && row_perm && col_val), "gpz_gene_morans_i_sparse: null pointer (non-zeros)");
-  GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "gpz_gene_morans_i_sparse: partials must be 16-byte aligned");
-  const GrPlan p = gr_plan(N, D, true, partials);
-  GPZ_REQUIRE(partials_bytes >= p.bytes, "gpz_gene_morans_i_sparse: partials too small (%zu bytes, %zu needed)", partials_bytes,
-              p.bytes);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const GrRows r{row_ptr, row_spot, row_perm, col_val, N, D, nnz};
-  GPZ_HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t), s));
-  GPZ_HIP_OK(hipMemsetAsync(p.indeg, 0, size_t(N) * sizeof(int32_t), s));
-  hipLaunchKernelGGL(gr_indeg_kernel, dim3(unsigned((N * K + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, N, int(K),
-                     p.indeg, info);
-  GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL(gr_moran_kernel<SparseRows>, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, SparseRows{r}, nbr, int(K), p.indeg,
-                     p.lines, I, static_cast<double*>(nullptr));
-  GPZ_LAUNCH_OK();
-  return 0;
+  GPZ_REQUIRE(I, "gpz_gene_morans_i_sparse: null pointer");
+  return gene_pass_entry<false>("gpz_gene_morans_i_sparse", GrRows{row_ptr, row_spot, row_perm, col_val, N, D, nnz}, nbr, K,
+                                SsOut{I, nullptr, nullptr, nullptr, nullptr}, info, partials, partials_bytes, stream);
 }

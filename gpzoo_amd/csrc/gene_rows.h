@@ -1,5 +1,5 @@
 // gene_rows.h -- what the per-gene kernels over a whole data set stored as its non-zeros share (gene_rank.hip,
-// gene_dispersion.hip, moran_perm.hip): the by-gene arrays of gpzoo_amd.likelihoods.SparseCounts, the clamped row of a gene,
+// gene_dispersion.hip, spatial_stats.hip, moran_perm.hip): the by-gene arrays of gpzoo_amd.likelihoods.SparseCounts, the clamped row of a gene,
 // the checked read of one stored entry, the fixed binary tree that closes a workgroup's partial sums, the row accessors of
 // the Moran passes, and the check of the extents.
 //

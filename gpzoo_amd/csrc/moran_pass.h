@@ -1,5 +1,5 @@
 // moran_pass.h -- Moran's I of the columns of an fp32 slab, for callers inside the library (residual.hip).  The kernels are
-// mi_rows / mi_final of spatial.hip, which is built with fp contraction off; gpz_morans_i runs the same ones.
+// narrow mi_rows / mi_final of spatial_stats.hip, which is built with fp contraction off; gpz_morans_i runs the same ones.
 #pragma once
 #include "common.h"
 

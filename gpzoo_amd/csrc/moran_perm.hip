@@ -1,7 +1,6 @@
 // moran_perm.hip -- Moran's I or Geary's C of every gene under P relabellings of the spots: the permutation null of squidpy's
 // spatial_autocorr(..., n_perms=) / PySAL's Moran and Geary, in O(entries x K) per permutation and never forming D x N.
-// The kernels are templated on the statistic; the Moran entries are here, and spatial_stats.hip's entries, which take the
-// statistic as an argument, come in through the drivers declared in moran_perm.h.
+// The kernels are templated on the statistic; all four entries, Moran-only or with the statistic as an argument, are here.
 //
 // For a permutation pi of the N spots the permuted gene is x^pi[i] = x[pi[i]].  Relabelling the graph instead of the values,
 //   sum_i z[pi[i]] sum_{j in nbr(i)} z[pi[j]]  =  sum_a z[a] sum_m z[T_pi[a, m]],
@@ -18,7 +17,7 @@
 //   mp_stat_kernel     one workgroup of MP_THREADS per gene at a time.  The gene's row is made available once -- scattered
 //                      into a line of N floats (SparseRows), or it is its own line (DenseRows) -- and every wave then takes
 //                      permutations of the batch: lane l adds the entries l + 64 u + 256 v (u < 4) of the row into its
-//                      slot u, the slots and lanes are folded in the order of gr_moran_kernel's binary tree over 256
+//                      slot u, the slots and lanes are folded in the order of gr_gene_kernel's binary tree over 256
 //                      partial sums, by register adds and a fixed shuffle tree.  No barrier per permutation, and with the
 //                      identity for pi the sums are those of the gene pass, bit for bit.  The wave leaves I_pi and t_pi in
 //                      LDS; after the batch one thread folds them into the gene's running n_ge, n_le, mean and M2
@@ -26,13 +25,27 @@
 // The line is in the scratch memory (line_mode 1) or in dynamic LDS (2) where 4 N plus the batch arrays fit a workgroup's
 // 160 KiB; the arithmetic is the same.  No floating-point atomics; every sum fp64 in a fixed order.
 //
-// STAT_GEARY: the gene pass is ss_gene_kernel of geary_expr.h, the second sum per permutation is Q_in,pi = sum indeg_pi x^2
-// in the place of A_pi, the value is geary_value and "C_pi >= C" is decided on geary_order, Q_in - 2 C_s.  Everything else is
-// shared, and the STAT_MORAN instantiations add what they added before the statistic became a parameter.
-#include "moran_perm.h"
+// STAT_GEARY: the gene pass is the wide instantiation of moran_expr.h's, the second sum per permutation is
+// Q_in,pi = sum indeg_pi x^2 in the place of A_pi, the value is geary_value and "C_pi >= C" is decided on geary_order,
+// Q_in - 2 C_s.  Everything else is shared.  The Moran-only entries (gpz_gene_morans_perm_sparse, gpz_morans_perm_rows) are the
+// entries that take the statistic (gpz_gene_autocorr_perm_sparse, gpz_autocorr_perm_rows) with STAT_MORAN and their own name
+// in the messages.
+#include "moran_expr.h"
 
 namespace gpz {
 namespace grk {
+
+constexpr int STAT_MORAN = 0, STAT_GEARY = 1;
+
+struct MpOut {
+  double* I;          // the observed statistic: I, or C
+  double* sims;
+  int32_t* n_ge;
+  int32_t* n_le;
+  double* sim_mean;
+  double* sim_m2;
+  int32_t* info;
+};
 
 constexpr int MP_THREADS = 1024;              // 16 waves: permutations in flight per gene
 constexpr int MP_WAVES = MP_THREADS / 64;
@@ -142,7 +155,7 @@ __global__ __launch_bounds__(MP_THREADS) void mp_stat_kernel(Rows r, MpBatch b) 
           else a[u] += double(dg[spot]) * x;
         }
       }
-      // the tree of gr_moran_kernel over 256 partial sums: slots t and t + 128, then t and t + 64, then the lanes
+      // the tree of gr_gene_kernel over 256 partial sums: slots t and t + 128, then t and t + 64, then the lanes
       double cs = (c[0] + c[2]) + (c[1] + c[3]), as = (a[0] + a[2]) + (a[1] + a[3]);
       for (int h = 32; h >= 1; h >>= 1) {
         cs += __shfl_down(cs, h, 64);
@@ -188,18 +201,22 @@ __global__ __launch_bounds__(MP_THREADS) void mp_stat_kernel(Rows r, MpBatch b) 
 }
 
 struct MpPlan {
-  int32_t* indeg;     // (N,)
-  float* lines;       // (workgroups, N): staged rows only
   double* stats;      // (D, GR_STATS)
   int32_t* T;         // (perm_batch, N, K)
   int32_t* indeg_pi;  // (perm_batch, N)
   int32_t* written;   // (perm_batch, N)
-  int workgroups, perm_batch, line_mode;
+  int perm_batch, line_mode;
   size_t lds, bytes;
 };
 
-static int mp_plan(const char* who, int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch, int32_t line_mode, bool staged,
-                   void* scratch, MpPlan& p) {
+static int mp_check_stat(const char* who, int32_t stat) {
+  GPZ_REQUIRE(stat == STAT_MORAN || stat == STAT_GEARY, "%s: stat %d unknown (0 Moran's I, 1 Geary's C)", who, stat);
+  return 0;
+}
+
+// c has given the gene pass its share of the scratch memory (GenePass); the batch arrays follow it
+static int mp_plan(const char* who, int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch, int32_t line_mode, Carver& c,
+                   MpPlan& p) {
   if (int rc = gr_check_k(who, N, K)) return rc;
   GPZ_REQUIRE(P >= 1 && P < (1ll << 31), "%s: P = %lld permutations unsupported (1 <= P < 2^31)", who, (long long)P);
   GPZ_REQUIRE(perm_batch >= 0 && perm_batch <= MP_BATCH_MAX, "%s: perm_batch = %d unsupported (0 = chosen here, at most %d)", who,
@@ -217,10 +234,6 @@ static int mp_plan(const char* who, int64_t N, int64_t D, int32_t K, int64_t P, 
     perm_batch = int32_t(fit < 1 ? 1 : (fit > cap ? cap : fit));
   }
   p.perm_batch = int(perm_batch < P ? perm_batch : P);
-  p.workgroups = int(D < GR_MAX_WG ? D : GR_MAX_WG);
-  Carver c(scratch);
-  p.indeg = c.take<int32_t>(size_t(N));
-  if (staged) p.lines = c.take<float>(size_t(p.workgroups) * size_t(N));
   p.stats = c.take<double>(size_t(D) * GR_STATS);
   p.T = c.take<int32_t>(size_t(p.perm_batch) * size_t(N) * size_t(K));
   p.indeg_pi = c.take<int32_t>(size_t(p.perm_batch) * size_t(N));
@@ -250,73 +263,69 @@ template <class Rows, int STAT>
 static int mp_run(const char* who, const Rows& r, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K, int64_t P,
                   int32_t perm_batch, int32_t line_mode, const MpOut& o, void* partials, size_t partials_bytes, void* stream) {
   GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "%s: partials must be 16-byte aligned", who);
+  Carver c(partials);
+  const GenePass gene(c, N, D, Rows::STAGED);
   MpPlan p;
-  if (int rc = mp_plan(who, N, D, K, P, perm_batch, line_mode, Rows::STAGED, partials, p)) return rc;
+  if (int rc = mp_plan(who, N, D, K, P, perm_batch, line_mode, c, p)) return rc;
   GPZ_REQUIRE(partials_bytes >= p.bytes, "%s: partials too small (%zu bytes, %zu needed)", who, partials_bytes, p.bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  GPZ_HIP_OK(hipMemsetAsync(o.info, 0, sizeof(int32_t), s));
-  GPZ_HIP_OK(hipMemsetAsync(p.indeg, 0, size_t(N) * sizeof(int32_t), s));
   GPZ_HIP_OK(hipMemsetAsync(o.n_ge, 0, size_t(D) * sizeof(int32_t), s));
   GPZ_HIP_OK(hipMemsetAsync(o.n_le, 0, size_t(D) * sizeof(int32_t), s));
   GPZ_HIP_OK(hipMemsetAsync(o.sim_mean, 0, size_t(D) * sizeof(double), s));
   GPZ_HIP_OK(hipMemsetAsync(o.sim_m2, 0, size_t(D) * sizeof(double), s));
-  hipLaunchKernelGGL(gr_indeg_kernel, dim3(unsigned((N * K + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, N, int(K),
-                     p.indeg, o.info);
-  GPZ_LAUNCH_OK();
-  if constexpr (STAT == STAT_GEARY)
-    hipLaunchKernelGGL(ss_gene_kernel<Rows>, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, nbr, int(K), p.indeg, p.lines,
-                       SsOut{nullptr, o.I, nullptr, nullptr, nullptr}, p.stats);
-  else
-    hipLaunchKernelGGL(gr_moran_kernel<Rows>, dim3(unsigned(p.workgroups)), dim3(GR_THREADS), 0, s, r, nbr, int(K), p.indeg, p.lines, o.I,
-                       p.stats);
-  GPZ_LAUNCH_OK();
+  constexpr bool WIDE = STAT == STAT_GEARY;
+  const SsOut observed{WIDE ? nullptr : o.I, WIDE ? o.I : nullptr, nullptr, nullptr, nullptr};
+  if (int rc = gene.template run<WIDE>(r, nbr, N, int(K), observed, p.stats, o.info, s)) return rc;
   for (int64_t p0 = 0; p0 < P; p0 += p.perm_batch) {
     const int pb = int(P - p0 < p.perm_batch ? P - p0 : p.perm_batch);
     const int64_t rows = int64_t(pb) * N;
     GPZ_HIP_OK(hipMemsetAsync(p.written, 0, size_t(rows) * sizeof(int32_t), s));
-    hipLaunchKernelGGL(mp_relabel_kernel, dim3(unsigned((rows + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, p.indeg,
+    hipLaunchKernelGGL(mp_relabel_kernel, dim3(unsigned((rows + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, gene.indeg,
                        perms + p0 * N, N, int(K), pb, p.T, p.indeg_pi, p.written, o.info);
     GPZ_LAUNCH_OK();
-    const MpBatch b{p.T, p.indeg_pi, p.stats, p.lines, o.sims, o.n_ge, o.n_le, o.sim_mean, o.sim_m2, P, p0, int(K), pb};
-    if (int rc = p.line_mode == 2 ? mp_launch_stat<Rows, true, STAT>(r, b, p.workgroups, p.lds, s)
-                                  : mp_launch_stat<Rows, false, STAT>(r, b, p.workgroups, p.lds, s))
+    const MpBatch b{p.T, p.indeg_pi, p.stats, gene.lines, o.sims, o.n_ge, o.n_le, o.sim_mean, o.sim_m2, P, p0, int(K), pb};
+    if (int rc = p.line_mode == 2 ? mp_launch_stat<Rows, true, STAT>(r, b, gene.workgroups, p.lds, s)
+                                  : mp_launch_stat<Rows, false, STAT>(r, b, gene.workgroups, p.lds, s))
       return rc;
   }
   return 0;
 }
 
-static int mp_report(const MpPlan& p, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups, int64_t* partials_bytes) {
+// The four plan queries; staged = rows stored as their non-zeros (dense rows pass nnz = 0).
+static int mp_query(const char* who, int64_t N, int64_t D, int64_t nnz, bool staged, int32_t K, int64_t P, int32_t stat,
+                    int32_t perm_batch_wanted, int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
+                    int64_t* partials_bytes) {
+  if (int rc = gr_check_shape(who, N, D, nnz)) return rc;
+  if (int rc = mp_check_stat(who, stat)) return rc;
+  Carver c(nullptr);
+  const GenePass gene(c, N, D, staged);
+  MpPlan p;
+  if (int rc = mp_plan(who, N, D, K, P, perm_batch_wanted, line_mode_wanted, c, p)) return rc;
   if (perm_batch) *perm_batch = p.perm_batch;
   if (line_mode) *line_mode = p.line_mode;
-  if (workgroups) *workgroups = p.workgroups;
+  if (workgroups) *workgroups = gene.workgroups;
   if (partials_bytes) *partials_bytes = int64_t(p.bytes);
   return 0;
 }
 
-// moran_perm.h
-int mp_plan_query(const char* who, int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch_wanted, int32_t line_mode_wanted,
-                  bool staged, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups, int64_t* partials_bytes) {
-  MpPlan p;
-  if (int rc = mp_plan(who, N, D, K, P, perm_batch_wanted, line_mode_wanted, staged, nullptr, p)) return rc;
-  return mp_report(p, perm_batch, line_mode, workgroups, partials_bytes);
-}
-
-int mp_run_sparse(const char* who, int stat, const GrRows& rows, const int64_t* nbr, const int32_t* perms, int32_t K, int64_t P,
-                  int32_t perm_batch, int32_t line_mode, const MpOut& o, void* partials, size_t partials_bytes, void* stream) {
-  const SparseRows r{rows};
-  return stat == STAT_GEARY ? mp_run<SparseRows, STAT_GEARY>(who, r, nbr, perms, rows.N, rows.D, K, P, perm_batch, line_mode, o, partials,
-                                                             partials_bytes, stream)
-                            : mp_run<SparseRows, STAT_MORAN>(who, r, nbr, perms, rows.N, rows.D, K, P, perm_batch, line_mode, o, partials,
-                                                             partials_bytes, stream);
-}
-
-int mp_run_rows(const char* who, int stat, const float* values, int64_t N, int64_t D, const int64_t* nbr, const int32_t* perms, int32_t K,
-                int64_t P, int32_t perm_batch, int32_t line_mode, const MpOut& o, void* partials, size_t partials_bytes, void* stream) {
-  const DenseRows r{values, N, D};
-  return stat == STAT_GEARY ? mp_run<DenseRows, STAT_GEARY>(who, r, nbr, perms, N, D, K, P, perm_batch, line_mode, o, partials,
-                                                            partials_bytes, stream)
-                            : mp_run<DenseRows, STAT_MORAN>(who, r, nbr, perms, N, D, K, P, perm_batch, line_mode, o, partials,
-                                                            partials_bytes, stream);
+// The four entries: the rows stored as their non-zeros (rows), or dense (values (D, N), and of rows the extents alone).
+static int mp_entry(const char* who, int32_t stat, const GrRows& rows, const float* values, const int64_t* nbr, const int32_t* perms,
+                    int32_t K, int64_t P, int32_t perm_batch, int32_t line_mode, const MpOut& o, void* partials, size_t partials_bytes,
+                    void* stream) {
+  const bool sparse = values == nullptr;
+  GPZ_REQUIRE((!sparse || rows.row_ptr) && nbr && perms && o.I && o.n_ge && o.n_le && o.sim_mean && o.sim_m2 && o.info && partials,
+              "%s: null pointer", who);
+  if (int rc = gr_check_shape(who, rows.N, rows.D, rows.nnz)) return rc;
+  if (int rc = mp_check_stat(who, stat)) return rc;
+  GPZ_REQUIRE(!sparse || rows.nnz == 0 || (rows.row_spot && rows.row_perm && rows.col_val), "%s: null pointer (non-zeros)", who);
+  auto run = [&](const auto& r) {
+    using Rows = std::decay_t<decltype(r)>;
+    return stat == STAT_GEARY ? mp_run<Rows, STAT_GEARY>(who, r, nbr, perms, rows.N, rows.D, K, P, perm_batch, line_mode, o, partials,
+                                                         partials_bytes, stream)
+                              : mp_run<Rows, STAT_MORAN>(who, r, nbr, perms, rows.N, rows.D, K, P, perm_batch, line_mode, o, partials,
+                                                         partials_bytes, stream);
+  };
+  return sparse ? run(SparseRows{rows}) : run(DenseRows{values, rows.N, rows.D});
 }
 
 }  // namespace grk
@@ -325,12 +334,41 @@ int mp_run_rows(const char* who, int stat, const float* values, int64_t N, int64
 using namespace gpz;
 using namespace gpz::grk;
 
+extern "C" int gpz_gene_autocorr_perm_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int64_t P, int32_t stat,
+                                                  int32_t perm_batch_wanted, int32_t line_mode_wanted, int32_t* perm_batch,
+                                                  int32_t* line_mode, int32_t* workgroups, int64_t* partials_bytes) {
+  return mp_query("gpz_gene_autocorr_perm_sparse", N, D, nnz, true, K, P, stat, perm_batch_wanted, line_mode_wanted, perm_batch,
+                  line_mode, workgroups, partials_bytes);
+}
+
 extern "C" int gpz_gene_morans_perm_sparse_plan(int64_t N, int64_t D, int64_t nnz, int32_t K, int64_t P, int32_t perm_batch_wanted,
                                                 int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode,
                                                 int32_t* workgroups, int64_t* partials_bytes) {
-  if (int rc = gr_check_shape("gpz_gene_morans_perm_sparse", N, D, nnz)) return rc;
-  return mp_plan_query("gpz_gene_morans_perm_sparse", N, D, K, P, perm_batch_wanted, line_mode_wanted, true, perm_batch, line_mode,
-                       workgroups, partials_bytes);
+  return mp_query("gpz_gene_morans_perm_sparse", N, D, nnz, true, K, P, STAT_MORAN, perm_batch_wanted, line_mode_wanted, perm_batch,
+                  line_mode, workgroups, partials_bytes);
+}
+
+extern "C" int gpz_autocorr_perm_rows_plan(int64_t N, int64_t D, int32_t K, int64_t P, int32_t stat, int32_t perm_batch_wanted,
+                                           int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
+                                           int64_t* partials_bytes) {
+  return mp_query("gpz_autocorr_perm_rows", N, D, 0, false, K, P, stat, perm_batch_wanted, line_mode_wanted, perm_batch, line_mode,
+                  workgroups, partials_bytes);
+}
+
+extern "C" int gpz_morans_perm_rows_plan(int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch_wanted,
+                                         int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
+                                         int64_t* partials_bytes) {
+  return mp_query("gpz_morans_perm_rows", N, D, 0, false, K, P, STAT_MORAN, perm_batch_wanted, line_mode_wanted, perm_batch, line_mode,
+                  workgroups, partials_bytes);
+}
+
+extern "C" int gpz_gene_autocorr_perm_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
+                                             const float* col_val, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D,
+                                             int64_t nnz, int32_t K, int64_t P, int32_t stat, int32_t perm_batch, int32_t line_mode,
+                                             double* value, double* sims, int32_t* n_ge, int32_t* n_le, double* sim_mean,
+                                             double* sim_m2, int32_t* info, void* partials, size_t partials_bytes, void* stream) {
+  return mp_entry("gpz_gene_autocorr_perm_sparse", stat, GrRows{row_ptr, row_spot, row_perm, col_val, N, D, nnz}, nullptr, nbr, perms, K,
+                  P, perm_batch, line_mode, MpOut{value, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes, stream);
 }
 
 extern "C" int gpz_gene_morans_perm_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
@@ -338,29 +376,26 @@ extern "C" int gpz_gene_morans_perm_sparse(const int64_t* row_ptr, const int32_t
                                            int64_t nnz, int32_t K, int64_t P, int32_t perm_batch, int32_t line_mode, double* I,
                                            double* sims, int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2,
                                            int32_t* info, void* partials, size_t partials_bytes, void* stream) {
-  const char* who = "gpz_gene_morans_perm_sparse";
-  GPZ_REQUIRE(row_ptr && nbr && perms && I && n_ge && n_le && sim_mean && sim_m2 && info && partials, "%s: null pointer", who);
-  if (int rc = gr_check_shape(who, N, D, nnz)) return rc;
-  GPZ_REQUIRE(nnz == 0 || (row_spot && row_perm && col_val), "%s: null pointer (non-zeros)", who);
-  return mp_run_sparse(who, STAT_MORAN, GrRows{row_ptr, row_spot, row_perm, col_val, N, D, nnz}, nbr, perms, K, P, perm_batch, line_mode,
-                       MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes, stream);
+  return mp_entry("gpz_gene_morans_perm_sparse", STAT_MORAN, GrRows{row_ptr, row_spot, row_perm, col_val, N, D, nnz}, nullptr, nbr,
+                  perms, K, P, perm_batch, line_mode, MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes,
+                  stream);
 }
 
-extern "C" int gpz_morans_perm_rows_plan(int64_t N, int64_t D, int32_t K, int64_t P, int32_t perm_batch_wanted,
-                                         int32_t line_mode_wanted, int32_t* perm_batch, int32_t* line_mode, int32_t* workgroups,
-                                         int64_t* partials_bytes) {
-  if (int rc = gr_check_shape("gpz_morans_perm_rows", N, D, 0)) return rc;
-  return mp_plan_query("gpz_morans_perm_rows", N, D, K, P, perm_batch_wanted, line_mode_wanted, false, perm_batch, line_mode, workgroups,
-                       partials_bytes);
+extern "C" int gpz_autocorr_perm_rows(const float* values, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K,
+                                      int64_t P, int32_t stat, int32_t perm_batch, int32_t line_mode, double* value, double* sims,
+                                      int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2, int32_t* info, void* partials,
+                                      size_t partials_bytes, void* stream) {
+  GPZ_REQUIRE(values, "gpz_autocorr_perm_rows: null pointer");
+  return mp_entry("gpz_autocorr_perm_rows", stat, GrRows{nullptr, nullptr, nullptr, nullptr, N, D, 0}, values, nbr, perms, K, P,
+                  perm_batch, line_mode, MpOut{value, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes, stream);
 }
 
 extern "C" int gpz_morans_perm_rows(const float* values, const int64_t* nbr, const int32_t* perms, int64_t N, int64_t D, int32_t K,
                                     int64_t P, int32_t perm_batch, int32_t line_mode, double* I, double* sims, int32_t* n_ge,
                                     int32_t* n_le, double* sim_mean, double* sim_m2, int32_t* info, void* partials,
                                     size_t partials_bytes, void* stream) {
-  const char* who = "gpz_morans_perm_rows";
-  GPZ_REQUIRE(values && nbr && perms && I && n_ge && n_le && sim_mean && sim_m2 && info && partials, "%s: null pointer", who);
-  if (int rc = gr_check_shape(who, N, D, 0)) return rc;
-  return mp_run_rows(who, STAT_MORAN, values, N, D, nbr, perms, K, P, perm_batch, line_mode,
-                     MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes, stream);
+  GPZ_REQUIRE(values, "gpz_morans_perm_rows: null pointer");
+  return mp_entry("gpz_morans_perm_rows", STAT_MORAN, GrRows{nullptr, nullptr, nullptr, nullptr, N, D, 0}, values, nbr, perms, K, P,
+                  perm_batch, line_mode, MpOut{I, sims, n_ge, n_le, sim_mean, sim_m2, info}, partials, partials_bytes, stream);
 }
+

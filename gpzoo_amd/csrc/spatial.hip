@@ -1,6 +1,6 @@
-// spatial.hip -- the spatial statistics after a fit: the self-kNN graph of the spots and Moran's I of the fitted
-// factors over it (gpzoo.utilities.dims_autocorr, reference utilities.py:131-156, which goes through squidpy's
-// spatial_neighbors + spatial_autocorr(mode="moran")).
+// spatial.hip -- the self-kNN graph of the spots, over which the spatial statistics after a fit are taken
+// (gpzoo.utilities.dims_autocorr, reference utilities.py:131-156, which goes through squidpy's spatial_neighbors +
+// spatial_autocorr(mode="moran"); Moran's I itself is spatial_stats.hip's).
 //
 //   sk_mark / sk_check   a caller-supplied point order is checked on the device: every entry in [0, N) and every
 //                        point named once; anything else is replaced by the identity (same graph, slower search)
@@ -11,18 +11,12 @@
 //                        registers.  Its own tile is searched first, then every super-tile / tile whose box can still
 //                        hold a better candidate for SOME lane; one that cannot is skipped.  The candidate loop reads
 //                        uniform addresses (scalar loads) and costs 3d - 1 fp64 VALU + one compare per pair.
-//   mi_rows<false>       per chunk of 256 rows: column sums of v - v[0] (shifted by the column's first value, so a
-//                        constant column has a mean equal to its value and gives 0 / 0 = NaN)
-//   mi_rows<true>        per chunk: sum_i z_i * (mean of z over i's neighbours) and sum_i z_i^2, z = v - mean
-//   mi_final             per column: the chunks' partials in a fixed order -> the mean, then I = numerator / denominator
 //
 // Distances are sklearn's: fp64, (x_k - y_k)^2 rounded on its own, added in coordinate order -- this file is built with
 // fp contraction off (gpzoo_amd/build.py) so no fma fuses a square into the sum.  The tile-skip bound uses the same
 // rounded operations on the box's nearest face: rounding is monotone, so bound <= d^2 of every point in the box, and a
 // tile is skipped only when the bound is STRICTLY above the lane's K-th best (an equal d^2 with a lower index can enter).
-// Every sum of the Moran statistic is taken in a fixed order (no floating-point atomics): two calls agree bit for bit.
 #include "common.h"
-#include "moran_pass.h"
 
 #include <math.h>
 
@@ -32,8 +26,6 @@ namespace {
 constexpr int SK_KMAX = 32;
 constexpr int SK_TILE = 64;          // points per tile = queries per wave
 constexpr int SK_BOX = 8;            // lo[4], hi[4]
-constexpr int MI_THREADS = 256;
-constexpr int MI_ROWS = 256;         // rows per partial sum of the Moran terms
 
 struct SkPlan {
   double* P;          // (N, 4) points in search order
@@ -301,137 +293,6 @@ int sk_launch_d(const SkPlan& pl, int64_t N, int K, int64_t* idx, hipStream_t s)
   return 0;
 }
 
-// ---- Moran's I ------------------------------------------------------------------------------------------------------
-
-// Threads of a block: CW columns x (MI_THREADS / CW) row slots; CW = the power of two >= L, at most 64.
-inline int mi_cw(int64_t L) {
-  int cw = 1;
-  while (cw < L && cw < 64) cw <<= 1;
-  return cw;
-}
-
-struct MiPlan {
-  double* part;       // (chunks, L, 3): shifted sum, numerator, denominator
-  double* mean;       // (L,)
-  int64_t chunks;
-  size_t bytes;
-};
-
-MiPlan mi_plan(int64_t N, int64_t L, void* ws) {
-  Carver c(ws);
-  MiPlan p;
-  p.chunks = (N + MI_ROWS - 1) / MI_ROWS;
-  p.part = c.take<double>(size_t(p.chunks) * L * 3);
-  p.mean = c.take<double>(size_t(L));
-  p.bytes = c.used();
-  return p;
-}
-
-// Block (chunk, column tile): each thread sums its rows in order, then row slot 0 adds the slots in order.  V holds N rows
-// of ld values each, of which the first L are the columns (ld = L for gpz_morans_i; a residual slab is wider).
-template <typename T, bool TERMS>
-__global__ __launch_bounds__(MI_THREADS) void mi_rows(const T* __restrict__ V, int64_t N, int64_t L, int64_t ld, int cw,
-                                                      const int64_t* __restrict__ nbr, int K, const double* __restrict__ mean,
-                                                      double* __restrict__ part, int32_t* __restrict__ info) {
-  __shared__ double red[2][MI_THREADS];
-  const int c = threadIdx.x % cw, slot = threadIdx.x / cw, slots = MI_THREADS / cw;
-  const int64_t l = int64_t(blockIdx.y) * cw + c;
-  const int64_t r0 = int64_t(blockIdx.x) * MI_ROWS, r1 = r0 + MI_ROWS < N ? r0 + MI_ROWS : N;
-  double a = 0.0, b = 0.0;
-  if (l < L) {
-    const double ref = TERMS ? mean[l] : double(V[l]);
-    const double w = 1.0 / K;
-    for (int64_t i = r0 + slot; i < r1; i += slots) {
-      const double z = double(V[i * ld + l]) - ref;
-      if (!TERMS) {
-        a += z;
-        continue;
-      }
-      double lag = 0.0;
-      for (int k = 0; k < K; ++k) {
-        const int64_t j = nbr[i * K + k];
-        if (j < 0 || j >= N || j == i) {     // never read outside the values; the caller is told through info
-          *info = 1;
-          continue;
-        }
-        lag += double(V[j * ld + l]) - ref;
-      }
-      a += z * (lag * w);
-      b += z * z;
-    }
-  }
-  red[0][threadIdx.x] = a;
-  red[1][threadIdx.x] = b;
-  __syncthreads();
-  if (slot == 0 && l < L) {
-    for (int r = 1; r < slots; ++r) {
-      a += red[0][r * cw + c];
-      b += red[1][r * cw + c];
-    }
-    double* o = part + (int64_t(blockIdx.x) * L + l) * 3;
-    if (TERMS) {
-      o[1] = a;
-      o[2] = b;
-    } else {
-      o[0] = a;
-    }
-  }
-}
-
-// Block = column: the chunks' partials in a fixed order (strided per thread, then a fixed tree).  TERMS == false: the
-// mean (first value + shifted sum / N); TERMS == true: I = numerator / denominator (0 / 0 = NaN: a constant column), and
-// the column's variance, denominator / N, where the caller asks for it (var, nullable).
-template <typename T, bool TERMS>
-__global__ __launch_bounds__(MI_THREADS) void mi_final(const double* __restrict__ part, int64_t chunks, int64_t L, int64_t N,
-                                                       const T* __restrict__ V, double* __restrict__ out,
-                                                       double* __restrict__ var) {
-  __shared__ double red[2][MI_THREADS];
-  const int64_t l = blockIdx.x;
-  double a = 0.0, b = 0.0;
-  for (int64_t ch = threadIdx.x; ch < chunks; ch += MI_THREADS) {
-    const double* o = part + (ch * L + l) * 3;
-    if (TERMS) {
-      a += o[1];
-      b += o[2];
-    } else {
-      a += o[0];
-    }
-  }
-  red[0][threadIdx.x] = a;
-  red[1][threadIdx.x] = b;
-  __syncthreads();
-  for (int h = MI_THREADS / 2; h >= 1; h >>= 1) {
-    if (threadIdx.x < h) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + h];
-      red[1][threadIdx.x] += red[1][threadIdx.x + h];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[l] = TERMS ? red[0][0] / red[1][0] : double(V[l]) + red[0][0] / double(N);
-    if (TERMS && var) var[l] = red[1][0] / double(N);
-  }
-}
-
-// The four launches over the first L columns of V (N rows of ld values); the means are left in pl.mean.
-template <typename T>
-int mi_run(const void* values, int64_t N, int64_t L, int64_t ld, const int64_t* nbr, int K, double* I, double* var,
-           int32_t* info, const MiPlan& pl, hipStream_t s) {
-  const T* V = static_cast<const T*>(values);
-  const int cw = mi_cw(L);
-  const dim3 rows(unsigned(pl.chunks), unsigned((L + cw - 1) / cw)), block(MI_THREADS);
-  hipLaunchKernelGGL((mi_rows<T, false>), rows, block, 0, s, V, N, L, ld, cw, nbr, K, pl.mean, pl.part, info);
-  GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((mi_final<T, false>), dim3(unsigned(L)), block, 0, s, pl.part, pl.chunks, L, N, V, pl.mean,
-                     static_cast<double*>(nullptr));
-  GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((mi_rows<T, true>), rows, block, 0, s, V, N, L, ld, cw, nbr, K, pl.mean, pl.part, info);
-  GPZ_LAUNCH_OK();
-  hipLaunchKernelGGL((mi_final<T, true>), dim3(unsigned(L)), block, 0, s, pl.part, pl.chunks, L, N, V, I, var);
-  GPZ_LAUNCH_OK();
-  return 0;
-}
-
 int sk_check_args(const char* who, int64_t N, int32_t d, int32_t K, int32_t dtype) {
   GPZ_REQUIRE(dtype == GPZ_F32 || dtype == GPZ_F64, "%s: unknown dtype %d", who, dtype);
   GPZ_REQUIRE(d >= 1 && d <= 4, "%s: d=%d unsupported (1..4)", who, d);
@@ -440,25 +301,7 @@ int sk_check_args(const char* who, int64_t N, int32_t d, int32_t K, int32_t dtyp
   return 0;
 }
 
-int mi_check_args(int64_t N, int64_t L, int32_t K, int32_t dtype) {
-  GPZ_REQUIRE(dtype == GPZ_F32 || dtype == GPZ_F64, "gpz_morans_i: unknown dtype %d", dtype);
-  GPZ_REQUIRE(K >= 1 && N > K && N < (int64_t(1) << 31), "gpz_morans_i: N=%lld, K=%d unsupported (1 <= K < N < 2^31)",
-              (long long)N, K);
-  GPZ_REQUIRE(L >= 1 && L <= (int64_t(1) << 20), "gpz_morans_i: L=%lld unsupported (1..2^20)", (long long)L);
-  return 0;
-}
-
 }  // namespace
-
-// moran_pass.h: the same four launches over a residual slab, with the column means and variances as outputs
-size_t moran_slab_bytes(int64_t B, int64_t cols) { return mi_plan(B, cols, nullptr).bytes; }
-
-int moran_slab_run(const float* slab, int64_t B, int64_t cols, int64_t ld, const int64_t* nbr, int K, double* I, double* mean,
-                   double* var, int32_t* info, void* scratch, hipStream_t s) {
-  MiPlan pl = mi_plan(B, cols, scratch);
-  pl.mean = mean;
-  return mi_run<float>(slab, B, cols, ld, nbr, K, I, var, info, pl, s);
-}
 
 }  // namespace gpz
 
@@ -501,21 +344,4 @@ extern "C" int gpz_spatial_knn(const void* X, int64_t N, int32_t d, int32_t K, i
     case 3: return sk_launch_d<3>(pl, N, K, idx, s);
     default: return sk_launch_d<4>(pl, N, K, idx, s);
   }
-}
-
-extern "C" size_t gpz_morans_i_workspace_bytes(int64_t N, int64_t L, int32_t K) {
-  if (mi_check_args(N, L, K, GPZ_F64)) return 0;
-  return mi_plan(N, L, nullptr).bytes;
-}
-
-extern "C" int gpz_morans_i(const void* values, int64_t N, int64_t L, int32_t dtype, const int64_t* nbr, int32_t K,
-                            double* I, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
-  GPZ_REQUIRE(values && nbr && I && info && ws, "gpz_morans_i: null pointer");
-  if (int rc = mi_check_args(N, L, K, dtype)) return rc;
-  const MiPlan pl = mi_plan(N, L, ws);
-  GPZ_REQUIRE(ws_bytes >= pl.bytes, "gpz_morans_i: workspace of %zu bytes, %zu needed", ws_bytes, pl.bytes);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  GPZ_HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t), s));
-  return dtype == GPZ_F32 ? mi_run<float>(values, N, L, L, nbr, K, I, nullptr, info, pl, s)
-                          : mi_run<double>(values, N, L, L, nbr, K, I, nullptr, info, pl, s);
 }

@@ -1560,6 +1560,13 @@ def _gene_deviance_sparse(c, size, family):
     return tuple(out)
 
 
+def _nbr_table(who: str, nbr, N: int, dev):
+    """The (N, K) neighbour table of a gene entry as contiguous int64 on ``dev``, and K."""
+    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
+        raise ValueError(f"{who}: nbr must be an ({N}, K) integer table")
+    return nbr.to(device=dev, dtype=torch.int64).contiguous(), int(nbr.shape[1])
+
+
 def gene_morans_i_sparse(values, nbr) -> torch.Tensor:
     """(D,) fp64 Moran's I of every gene of a whole ``SparseCounts`` / ``SparseExpression`` (the offset does not change I)
     over the neighbour table nbr (N,K) int64, 1 <= K <= 32, with row-normalised weights (gpz_gene_morans_i_sparse): what
@@ -1570,10 +1577,7 @@ def gene_morans_i_sparse(values, nbr) -> torch.Tensor:
     _need_cuda(v.col_val)
     D, N = v.shape
     dev = v.device
-    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
-        raise ValueError(f"gene_morans_i_sparse: nbr must be an ({N}, K) integer table")
-    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
-    K = int(nbr.shape[1])
+    nbr, K = _nbr_table("gene_morans_i_sparse", nbr, N, dev)
     lib = _lib.load()
     nb = C.c_int64()
     if lib.gpz_gene_morans_i_sparse_plan(N, D, v.nnz, K, None, None, C.byref(nb)) != 0:
@@ -1599,43 +1603,47 @@ def _line_mode(who: str, line_mode) -> int:
     return _LINE_MODES[line_mode]
 
 
-def morans_perm_plan(N: int, D: int, K: int, P: int, nnz: Optional[int] = None, perm_batch: int = 0, line_mode=0) -> dict:
-    """How ``gene_morans_perm_sparse`` (``nnz`` stored entries) or ``morans_perm_rows`` (``nnz=None``) covers a shape
-    (gpz_gene_morans_perm_sparse_plan / gpz_morans_perm_rows_plan, host-only queries: no device needed): ``perm_batch``
-    (permutations per launch) and ``line_mode`` (1 scratch memory, 2 LDS) as resolved, ``workgroups`` (genes in flight),
-    ``partials_bytes``.  A ``line_mode`` of 2 where a line of N floats does not fit the LDS raises ValueError."""
+def _perm_plan(who: str, family: str, stat, N, D, K, P, nnz, perm_batch, line_mode) -> dict:
+    """The plan query of a permutation entry: ``family`` "morans" (``stat`` None) or "autocorr" (``stat`` 0 or 1), rows stored
+    as their non-zeros (``nnz``) or dense (``nnz=None``)."""
     lib = _lib.load()
     pb, lm, wg, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
-    mode = _line_mode("morans_perm_plan", line_mode)
-    outs = (C.byref(pb), C.byref(lm), C.byref(wg), C.byref(nb))
-    if nnz is None:
-        rc = lib.gpz_morans_perm_rows_plan(int(N), int(D), int(K), int(P), int(perm_batch), mode, *outs)
-    else:
-        rc = lib.gpz_gene_morans_perm_sparse_plan(int(N), int(D), int(nnz), int(K), int(P), int(perm_batch), mode, *outs)
+    entry = f"gpz_{family}_perm_rows_plan" if nnz is None else f"gpz_gene_{family}_perm_sparse_plan"
+    extents = [int(N), int(D)] if nnz is None else [int(N), int(D), int(nnz)]
+    batch = [int(K), int(P)] if stat is None else [int(K), int(P), stat]
+    rc = getattr(lib, entry)(*extents, *batch, int(perm_batch), _line_mode(who, line_mode), C.byref(pb), C.byref(lm), C.byref(wg),
+                             C.byref(nb))
     if rc != 0:
         raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
     return dict(perm_batch=pb.value, line_mode=lm.value, workgroups=wg.value, partials_bytes=int(nb.value))
 
 
-def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, perms, return_sims, perm_batch, line_mode, stat=None):
-    """The call behind the four permutation entries; ``stat`` (0 Moran, 1 Geary) for those that take it, None for the
-    Moran-only ones.  Returns the tensors of a ``MoransPerm`` in its order."""
-    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
-        raise ValueError(f"{who}: nbr must be an ({N}, K) integer table")
+def morans_perm_plan(N: int, D: int, K: int, P: int, nnz: Optional[int] = None, perm_batch: int = 0, line_mode=0) -> dict:
+    """How ``gene_morans_perm_sparse`` (``nnz`` stored entries) or ``morans_perm_rows`` (``nnz=None``) covers a shape
+    (gpz_gene_morans_perm_sparse_plan / gpz_morans_perm_rows_plan, host-only queries: no device needed): ``perm_batch``
+    (permutations per launch) and ``line_mode`` (1 scratch memory, 2 LDS) as resolved, ``workgroups`` (genes in flight),
+    ``partials_bytes``.  A ``line_mode`` of 2 where a line of N floats does not fit the LDS raises ValueError."""
+    return _perm_plan("morans_perm_plan", "morans", None, N, D, K, P, nnz, perm_batch, line_mode)
+
+
+def _morans_perm(who: str, family: str, stat, N: int, D: int, nnz, dev, inputs, nbr, perms, return_sims, perm_batch, line_mode):
+    """The call behind the four permutation entries, named as ``_perm_plan`` names them: ``family`` "autocorr" with ``stat``
+    0 (Moran) or 1 (Geary), "morans" with None; ``inputs`` are the entry's leading pointers.  Returns the tensors of a
+    ``MoransPerm`` in its order."""
+    nbr, K = _nbr_table(who, nbr, N, dev)
     if (not isinstance(perms, torch.Tensor) or perms.dim() != 2 or perms.shape[0] < 1 or perms.shape[1] != N
             or perms.dtype.is_floating_point or perms.dtype == torch.bool):
         raise ValueError(f"{who}: perms must be a (P, {N}) integer tensor, P >= 1")
     if isinstance(perm_batch, bool) or not isinstance(perm_batch, int) or perm_batch < 0:
         raise ValueError(f"{who}: perm_batch {perm_batch!r} must be a non-negative integer (0 = chosen by the plan)")
-    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
     if perms.dtype != torch.int32:
         perms = perms.to(device=dev, dtype=torch.int64).clamp(-1, N)                  # a wide entry stays out of range in 32 bits
     perms = perms.to(device=dev, dtype=torch.int32).contiguous()
-    K, P = int(nbr.shape[1]), int(perms.shape[0])
-    if stat is None:
-        plan = morans_perm_plan(N, D, K, P, nnz, perm_batch, _line_mode(who, line_mode))
-    else:
-        plan = autocorr_perm_plan(N, D, K, P, nnz, _STATS[stat], perm_batch, _line_mode(who, line_mode))
+    P = int(perms.shape[0])
+    plan = _perm_plan(who, family, stat, N, D, K, P, nnz, perm_batch, line_mode)
+    entry = f"gpz_{family}_perm_rows" if nnz is None else f"gpz_gene_{family}_perm_sparse"
+    extents = [N, D] if nnz is None else [N, D, nnz]
+    batch = [K, P] if stat is None else [K, P, stat]
     lib = _lib.load()
     I, mean, m2 = (torch.empty(D, dtype=torch.float64, device=dev) for _ in range(3))
     n_ge, n_le = (torch.empty(D, dtype=torch.int32, device=dev) for _ in range(2))
@@ -1643,9 +1651,8 @@ def _morans_perm(who: str, entry: str, N: int, D: int, nnz, dev, inputs, nbr, pe
     info = torch.empty(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         ws = _workspace(dev, plan["partials_bytes"])
-        rc = getattr(lib, entry)(*inputs, _ptr(nbr), _ptr(perms), N, D, *(() if nnz is None else (nnz,)), K, P,
-                                 *(() if stat is None else (stat,)), plan["perm_batch"], plan["line_mode"], _ptr(I), _ptr(sims), _ptr(n_ge), _ptr(n_le), _ptr(mean), _ptr(m2), _ptr(info),
-                                 _ptr(ws), ws.numel(), _stream(dev))
+        rc = getattr(lib, entry)(*inputs, _ptr(nbr), _ptr(perms), *extents, *batch, plan["perm_batch"], plan["line_mode"], _ptr(I),
+                                 _ptr(sims), _ptr(n_ge), _ptr(n_le), _ptr(mean), _ptr(m2), _ptr(info), _ptr(ws), ws.numel(), _stream(dev))
     _lib.check(rc, entry)
     code = int(info.item())
     if code == 1:
@@ -1680,8 +1687,7 @@ def gene_morans_perm_sparse(values, nbr, perms, *, return_sims: bool = False, pe
     _need_cuda(v.col_val)
     D, N = v.shape
     inputs = (_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val))
-    return MoransPerm(*_morans_perm(who, "gpz_gene_morans_perm_sparse", N, D, v.nnz, v.device, inputs, nbr, perms, return_sims, perm_batch,
-                                    line_mode))
+    return MoransPerm(*_morans_perm(who, "morans", None, N, D, v.nnz, v.device, inputs, nbr, perms, return_sims, perm_batch, line_mode))
 
 
 def morans_perm_rows(values, nbr, perms, *, return_sims: bool = False, perm_batch: int = 0, line_mode=0) -> MoransPerm:
@@ -1694,11 +1700,10 @@ def morans_perm_rows(values, nbr, perms, *, return_sims: bool = False, perm_batc
     _need_cuda(values)
     V = values.detach().contiguous()
     D, N = V.shape
-    return MoransPerm(*_morans_perm(who, "gpz_morans_perm_rows", N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims, perm_batch,
-                                    line_mode))
+    return MoransPerm(*_morans_perm(who, "morans", None, N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims, perm_batch, line_mode))
 
 
-_STATS = {"moran": 0, "geary": 1, 0: "moran", 1: "geary"}
+_STATS = {"moran": 0, "geary": 1}
 
 
 def _stat(who: str, stat) -> int:
@@ -1748,10 +1753,7 @@ def gene_spatial_stats_sparse(values, nbr) -> SpatialStats:
     _need_cuda(v.col_val)
     D, N = v.shape
     dev = v.device
-    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.shape[0] != N or nbr.dtype.is_floating_point:
-        raise ValueError(f"{who}: nbr must be an ({N}, K) integer table")
-    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
-    K = int(nbr.shape[1])
+    nbr, K = _nbr_table(who, nbr, N, dev)
     plan = spatial_stats_plan(N, K, D=D, nnz=v.nnz)
     lib = _lib.load()
     out = [torch.empty(D, dtype=torch.float64, device=dev) for _ in range(5)]
@@ -1797,18 +1799,7 @@ def autocorr_perm_plan(N: int, D: int, K: int, P: int, nnz: Optional[int] = None
                        line_mode=0) -> dict:
     """``morans_perm_plan`` for ``gene_autocorr_perm_sparse`` (``nnz`` stored entries) or ``autocorr_perm_rows``
     (``nnz=None``) (gpz_gene_autocorr_perm_sparse_plan / gpz_autocorr_perm_rows_plan, host-only queries)."""
-    lib = _lib.load()
-    st = _stat("autocorr_perm_plan", stat)
-    pb, lm, wg, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
-    mode = _line_mode("autocorr_perm_plan", line_mode)
-    outs = (C.byref(pb), C.byref(lm), C.byref(wg), C.byref(nb))
-    if nnz is None:
-        rc = lib.gpz_autocorr_perm_rows_plan(int(N), int(D), int(K), int(P), st, int(perm_batch), mode, *outs)
-    else:
-        rc = lib.gpz_gene_autocorr_perm_sparse_plan(int(N), int(D), int(nnz), int(K), int(P), st, int(perm_batch), mode, *outs)
-    if rc != 0:
-        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
-    return dict(perm_batch=pb.value, line_mode=lm.value, workgroups=wg.value, partials_bytes=int(nb.value))
+    return _perm_plan("autocorr_perm_plan", "autocorr", _stat("autocorr_perm_plan", stat), N, D, K, P, nnz, perm_batch, line_mode)
 
 
 @dataclass
@@ -1837,8 +1828,8 @@ def gene_autocorr_perm_sparse(values, nbr, perms, *, stat: str = "moran", return
     _need_cuda(v.col_val)
     D, N = v.shape
     inputs = (_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val))
-    return AutocorrPerm(stat, *_morans_perm(who, "gpz_gene_autocorr_perm_sparse", N, D, v.nnz, v.device, inputs, nbr, perms, return_sims,
-                                            perm_batch, line_mode, st))
+    return AutocorrPerm(stat, *_morans_perm(who, "autocorr", st, N, D, v.nnz, v.device, inputs, nbr, perms, return_sims, perm_batch,
+                                            line_mode))
 
 
 def autocorr_perm_rows(values, nbr, perms, *, stat: str = "moran", return_sims: bool = False, perm_batch: int = 0,
@@ -1852,8 +1843,8 @@ def autocorr_perm_rows(values, nbr, perms, *, stat: str = "moran", return_sims: 
     _need_cuda(values)
     V = values.detach().contiguous()
     D, N = V.shape
-    return AutocorrPerm(stat, *_morans_perm(who, "gpz_autocorr_perm_rows", N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims,
-                                            perm_batch, line_mode, st))
+    return AutocorrPerm(stat, *_morans_perm(who, "autocorr", st, N, D, None, V.device, (_ptr(V),), nbr, perms, return_sims, perm_batch,
+                                            line_mode))
 
 
 def gene_dispersion_plan(N: int, D: int, nnz: int) -> dict:

@@ -1,5 +1,5 @@
 """Seeded cases, fp64 / integer oracles and the recorded tolerances for Geary's C, the kurtosis and the randomisation moments
-(gpzoo_amd/csrc/spatial_stats.hip, geary_expr.h; ``utilities.gene_autocorr(mode="geary", assumption="randomisation")``).
+(gpzoo_amd/csrc/spatial_stats.hip, moran_expr.h; ``utilities.gene_autocorr(mode="geary", assumption="randomisation")``).
 TEST INFRASTRUCTURE ONLY; numpy, everything runs on the CPU.
 
 The data are those of tests/gene_rank_cases.py and tests/moran_perm_cases.py (D = 37 genes with their row kinds, N in NS, the

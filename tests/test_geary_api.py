@@ -40,8 +40,14 @@ def test_new_entries_are_declared_exported_and_bound():
     for n in ("gene_spatial_stats_sparse", "spatial_stats", "spatial_stats_plan", "gene_autocorr_perm_sparse", "autocorr_perm_rows",
               "autocorr_perm_plan", "SpatialStats", "AutocorrPerm"):
         assert callable(getattr(ops, n))
-    assert "spatial_stats.hip" in build.SOURCES and {"geary_expr.h", "moran_perm.h"} <= set(build.HEADERS)
-    assert "-ffp-contract=off" in build.SOURCE_FLAGS["spatial_stats.hip"]       # the bits of gene_rank.hip, moran_perm.hip, spatial.hip
+    # Geary's closing expression and the wide gene pass are moran_expr.h's; every file that includes it is a source or a
+    # header the source hash covers, and every source that does is built with fp contraction off (one kernel, one set of bits)
+    assert "spatial_stats.hip" in build.SOURCES and "moran_expr.h" in build.HEADERS
+    assert "geary_value" in open(os.path.join(build.CSRC, "moran_expr.h")).read()
+    users = [f for f in os.listdir(build.CSRC)
+             if f.endswith((".hip", ".h")) and '#include "moran_expr.h"' in open(os.path.join(build.CSRC, f)).read()]
+    assert {"spatial_stats.hip", "moran_perm.hip", "gene_rank.hip"} <= set(users) <= set(build.SOURCES + build.HEADERS)
+    assert all("-ffp-contract=off" in build.SOURCE_FLAGS[f] for f in users if f.endswith(".hip"))
 
 
 def test_scratch_is_the_explicit_argument_partials_sized_by_the_plan():

@@ -1,4 +1,4 @@
-"""GPU: Geary's C, the kurtosis and the permutation null of C (gpzoo_amd/csrc/spatial_stats.hip, geary_expr.h, the Geary
+"""GPU: Geary's C, the kurtosis and the permutation null of C (gpzoo_amd/csrc/spatial_stats.hip, moran_expr.h, the Geary
 instantiations of moran_perm.hip) against the oracles and within the recorded bounds of tests/geary_cases.py; I with the bits
 of the Moran-only entries; every output with the same bits whatever the batch, the line's home and the scratch memory's
 contents; the mean and variance over all 7! relabellings against the analytic randomisation moments."""

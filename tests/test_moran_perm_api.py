@@ -83,7 +83,9 @@ def test_new_entries_are_declared_exported_and_bound():
     assert lib.gpz_version() == 212
     assert all(callable(getattr(ops, n)) for n in ("gene_morans_perm_sparse", "morans_perm_rows", "morans_perm_plan"))
     assert "moran_perm.hip" in build.SOURCES and "moran_expr.h" in build.HEADERS
+    assert '#include "moran_expr.h"' in open(os.path.join(build.CSRC, "moran_perm.hip")).read()
     assert "-ffp-contract=off" in build.SOURCE_FLAGS["moran_perm.hip"]          # gene_rank.hip's expression, gene_rank.hip's bits
+    assert "-ffp-contract=off" in build.SOURCE_FLAGS["gene_rank.hip"]
 
 
 def _args(name):

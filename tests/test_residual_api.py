@@ -37,11 +37,15 @@ def test_new_entries_are_declared_exported_and_bound():
     assert all(n in comment for n in NEW_SYMBOLS)
     assert all(callable(getattr(ops, n)) for n in ("count_residuals", "residual_morans_i", "residual_autocorr_plan"))
     assert "residual.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "residual.hip"))
-    # the Moran pass is spatial.hip's, reached through one internal header the source hash covers; it keeps its flags
-    assert "moran_pass.h" in build.HEADERS and build.SOURCE_FLAGS["spatial.hip"] == ["-ffp-contract=off"]
+    # the Moran pass is spatial_stats.hip's, reached through one internal header the source hash covers; it is built with
+    # fp contraction off, and so is spatial.hip still (the kNN distances)
+    assert "moran_pass.h" in build.HEADERS and "spatial_stats.hip" in build.SOURCES
+    assert build.SOURCE_FLAGS["spatial_stats.hip"] == ["-ffp-contract=off"] and build.SOURCE_FLAGS["spatial.hip"] == ["-ffp-contract=off"]
     text = open(os.path.join(build.CSRC, "residual.hip")).read()
     assert '#include "moran_pass.h"' in text and '#include "gene_rows.h"' in text and "void mi_rows" not in text
-    assert '#include "moran_pass.h"' in open(os.path.join(build.CSRC, "spatial.hip")).read()
+    home = open(os.path.join(build.CSRC, "spatial_stats.hip")).read()
+    assert '#include "moran_pass.h"' in home and "void mi_rows" in home
+    assert "void mi_rows" not in open(os.path.join(build.CSRC, "spatial.hip")).read()
     # the argument counts of the bindings are the header's
     for name in NEW_SYMBOLS:
         assert len(_lib._SIGNATURES[name][1]) == len(_args(name)), name
