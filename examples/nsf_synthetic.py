@@ -12,7 +12,9 @@ cent dense) and fits through ``SparseCounts``: the same model and the same loop,
 ``--holdout FRAC`` holds that fraction of the spots out (``train_val_split``, the split of the reference's
 ``anndata_to_train_val``), fits on the rest and prints the Poisson deviance of the held-out spots under the predictive mean
 rate and the share of the null model's deviance it explains (``model.deviance``); it works with ``--sparse-counts`` too.  With ``--residual-autocorr`` it prints the ten genes with the largest
-``z`` of ``model.residual_autocorr`` after the fit: where spatial structure is left in what the model did not explain.
+``z`` of ``model.residual_autocorr`` after the fit: where spatial structure is left in what the model did not explain;
+``--residual-perms P`` (with ``--residual-mode geary`` for Geary's C) adds the permutation null and prints the ten genes
+with the smallest permutation p-value for positive autocorrelation and their Benjamini-Hochberg value (``fdr_bh``).
 
 ``--likelihood nb`` draws overdispersed (gamma-Poisson) counts with a known inverse dispersion per gene, fits the model with
 ``likelihood="nb"`` (the fused negative-binomial step) and prints the fitted theta next to the true one; with ``--holdout``
@@ -72,7 +74,13 @@ def main():
                          "constant-rate null (gene_dispersion; needs --sparse-counts)")
     ap.add_argument("--residual-autocorr", action="store_true",
                     help="after the fit, print the ten genes whose residuals are most spatially autocorrelated")
+    ap.add_argument("--residual-perms", type=int, default=None, metavar="P",
+                    help="with --residual-autocorr: P random relabellings of the spots; print the ten genes with the smallest "
+                         "permutation p-value and their fdr_bh value")
+    ap.add_argument("--residual-mode", default="moran", choices=("moran", "geary"), help="with --residual-perms: the statistic")
     a = ap.parse_args()
+    if a.residual_perms is not None and not a.residual_autocorr:
+        ap.error("--residual-perms needs --residual-autocorr")
     if a.theta0 == "mle" and (a.likelihood != "nb" or a.sparse_counts is None):
         ap.error("--theta0 mle needs --likelihood nb and --sparse-counts (gene_dispersion reads a SparseCounts)")
     dev = torch.device("cuda")
@@ -179,6 +187,24 @@ def main():
             print("  gene %5d  I %+.4f  z %+7.2f  residual mean %+.3f  variance %.3f"
                   % (i, float(ra.I[i]), float(ra.z[i]), float(ra.residual_mean[i]), float(ra.residual_var[i])))
         assert bool(torch.isfinite(ra.I).all())
+        if a.residual_perms is not None:
+            # how unusual each gene's statistic is among relabellings of its own residuals: exact for exchangeable residuals,
+            # still blind to the degrees of freedom the fit used
+            from gpzoo.utilities import fdr_bh
+            t0 = time.perf_counter()
+            rp = model.residual_autocorr(X, Y, mode=a.residual_mode, assumption="randomisation", n_perms=a.residual_perms, seed=0)
+            geary = a.residual_mode == "geary"
+            pval = rp.pval_less if geary else rp.pval_greater          # positive autocorrelation: a small C, a large I
+            q = fdr_bh(pval)
+            top = torch.argsort(pval, stable=True)[:10].cpu()
+            dt = time.perf_counter() - t0
+            print("permutation null of %s over %d relabellings  [%.1f ms]; smallest attainable p %.4f"
+                  % ("Geary's C" if geary else "Moran's I", rp.n_perms, 1e3 * dt, 1.0 / (rp.n_perms + 1)))
+            for i in top.tolist():
+                print("  gene %5d  %s %+.4f  p %.4f  fdr_bh %.4f  z (randomisation) %+7.2f  residual kurtosis %.1f"
+                      % (i, "C" if geary else "I", float(rp[0][i]), float(pval[i]), float(q[i]), float(rp.z[i]),
+                         float(rp.residual_kurtosis[i])))
+            assert bool(((pval > 0) & (pval <= 1)).all())
 
 
 if __name__ == "__main__":

@@ -136,6 +136,18 @@ _SIGNATURES = {
                               [C.c_size_t, C.c_void_p]),
     "gpz_residual_morans_i_sparse": (C.c_int, [C.c_void_p] * 11 + [C.c_int64] * 4 + [C.c_int32] * 5 + [C.c_int64] +
                                      [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "gpz_residual_autocorr_perm_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                                  C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gpz_residual_spatial_stats": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] * 3 + [C.c_int32] * 5 + [C.c_int64] +
+                                   [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_residual_spatial_stats_sparse": (C.c_int, [C.c_void_p] * 11 + [C.c_int64] * 4 + [C.c_int32] * 5 + [C.c_int64] +
+                                          [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_residual_autocorr_perm": (C.c_int, [C.c_void_p] * 9 + [C.c_int64] * 3 + [C.c_int32] * 5 +
+                                   [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p]),
+    "gpz_residual_autocorr_perm_sparse": (C.c_int, [C.c_void_p] * 12 + [C.c_int64] * 4 + [C.c_int32] * 5 +
+                                          [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11 +
+                                          [C.c_size_t, C.c_void_p]),
     "gpz_nb_nsf_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6),
     "gpz_nb_nsf_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),

@@ -31,6 +31,7 @@
 // entries that take the statistic (gpz_gene_autocorr_perm_sparse, gpz_autocorr_perm_rows) with STAT_MORAN and their own name
 // in the messages.
 #include "moran_expr.h"
+#include "moran_pass.h"
 
 namespace gpz {
 namespace grk {
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(GR_THREADS) void mp_relabel_kernel(const int64_t* _
     }
     row[m] = v;
   }
-  indeg_pi[p * N + a] = indeg[i];
+  if (indeg) indeg_pi[p * N + a] = indeg[i];                       // the column form (moran_pass.h) has no in-degrees
 }
 
 struct MpBatch {
@@ -278,11 +279,7 @@ static int mp_run(const char* who, const Rows& r, const int64_t* nbr, const int3
   if (int rc = gene.template run<WIDE>(r, nbr, N, int(K), observed, p.stats, o.info, s)) return rc;
   for (int64_t p0 = 0; p0 < P; p0 += p.perm_batch) {
     const int pb = int(P - p0 < p.perm_batch ? P - p0 : p.perm_batch);
-    const int64_t rows = int64_t(pb) * N;
-    GPZ_HIP_OK(hipMemsetAsync(p.written, 0, size_t(rows) * sizeof(int32_t), s));
-    hipLaunchKernelGGL(mp_relabel_kernel, dim3(unsigned((rows + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, nbr, gene.indeg,
-                       perms + p0 * N, N, int(K), pb, p.T, p.indeg_pi, p.written, o.info);
-    GPZ_LAUNCH_OK();
+    if (int rc = relabel_tables(nbr, gene.indeg, perms + p0 * N, N, int(K), pb, p.T, p.indeg_pi, p.written, o.info, s)) return rc;
     const MpBatch b{p.T, p.indeg_pi, p.stats, gene.lines, o.sims, o.n_ge, o.n_le, o.sim_mean, o.sim_m2, P, p0, int(K), pb};
     if (int rc = p.line_mode == 2 ? mp_launch_stat<Rows, true, STAT>(r, b, gene.workgroups, p.lds, s)
                                   : mp_launch_stat<Rows, false, STAT>(r, b, gene.workgroups, p.lds, s))
@@ -329,6 +326,18 @@ static int mp_entry(const char* who, int32_t stat, const GrRows& rows, const flo
 }
 
 }  // namespace grk
+
+// moran_pass.h: the tables of one batch, for the entries here and for the permutation column pass of spatial_stats.hip
+int relabel_tables(const int64_t* nbr, const int32_t* indeg, const int32_t* perms, int64_t N, int K, int pb, int32_t* T,
+                   int32_t* indeg_pi, int32_t* written, int32_t* info, hipStream_t s) {
+  const int64_t rows = int64_t(pb) * N;
+  GPZ_HIP_OK(hipMemsetAsync(written, 0, size_t(rows) * sizeof(int32_t), s));
+  hipLaunchKernelGGL(grk::mp_relabel_kernel, dim3(unsigned((rows + grk::GR_THREADS - 1) / grk::GR_THREADS)), dim3(grk::GR_THREADS), 0,
+                     s, nbr, indeg, perms, N, K, pb, T, indeg_pi, written, info);
+  GPZ_LAUNCH_OK();
+  return 0;
+}
+
 }  // namespace gpz
 
 using namespace gpz;

@@ -2,7 +2,7 @@
 // gene's residuals over the spots' K-neighbour graph: is spatial structure left in what the model did not explain, and in
 // which genes.  Dense counts and counts stored as their non-zeros.  The (D, B) rate and the (D, B) residuals never exist in
 // HBM: the genes are taken in slabs of at most 256 MiB of fp32 residuals, laid out spot-major, which the Moran pass of
-// spatial.hip (moran_pass.h) reads the way it reads any (B, L) array.
+// spatial_stats.hip (moran_pass.h) reads the way it reads any (B, L) array.
 //
 //   m[l,n]  = exp(mean[l,n] + scale[l,n]^2 / 2)          (exp(mean) without the flag)
 //   mu[d,n] = V[n] sum_l W[d,l] m[l,n]
@@ -38,6 +38,9 @@
 //                       dense pass; a transposed copy for this gather measured no faster.
 //   driver              per slab: the residual pass, then moran_slab_run.  No atomics, no workgroup waits on another, every
 //                       sum (all of them in the Moran pass) fp64 in a fixed order: two calls agree bit for bit.
+//   run_wide            gpz_residual_spatial_stats* and gpz_residual_autocorr_perm*: per slab the residual pass once, the wide
+//                       column pass once (Geary's C and the kurtosis beside I), then every batch of permutations over the
+//                       resident slab (moran_pass.h).  The slab is filled exactly as for the Moran entries.
 #include "common.h"
 #include "gene_rows.h"
 #include "moran_pass.h"
@@ -427,6 +430,128 @@ static int run_moran(const char* who, const Call& c, const int64_t* nbr, int K, 
   return 0;
 }
 
+// ---- the wide statistics and the permutation null -------------------------------------------------------------------
+// The scratch of the entries that need more than I: the factors and the slab as in make_plan, then the wide column pass's
+// partial sums and, for the permutation entries, the batch's relabelled tables and partial sums (moran_pass.h).
+
+constexpr int PERM_BATCH_DEFAULT = 16;          // the plan's choice where 16 tables fit; DESIGN.md section 5 says what it rests on
+constexpr int64_t TABLE_BYTES = 256ll << 20;    // the tables of a batch stay within what the slab is held to
+
+struct WidePlan {
+  Plan base;                      // SG, nslabs, mF, Vw, slab as the Moran entries lay them out (base.moran is not used)
+  void *wide, *perm;
+  int perm_batch;                 // 0: no permutations
+  int64_t batches;
+  size_t bytes;
+};
+
+// perm_in: the caller's perm_batch (0: the plan's choice); P = 0: the statistics alone
+static WidePlan make_wide_plan(int64_t B, int64_t G, int Lt, int K, int64_t P, int64_t slab_in, int perm_in, void* ws) {
+  WidePlan w{};
+  w.base = make_plan(B, G, Lt, slab_in, nullptr);
+  Carver c(ws);
+  w.base.mF = c.take<float>((size_t)Lt * B);
+  w.base.Vw = c.take<float>((size_t)w.base.Bp);
+  w.base.slab = c.take<float>((size_t)B * w.base.SG);
+  w.wide = c.take<char>(moran_slab_wide_bytes(B, w.base.SG));
+  if (P > 0) {
+    int64_t pb = perm_in;
+    if (pb == 0) {
+      const int64_t fit = TABLE_BYTES / (4 * B * K);
+      pb = fit < 1 ? 1 : (fit > PERM_BATCH_DEFAULT ? PERM_BATCH_DEFAULT : fit);
+    }
+    if (pb > P) pb = P;
+    w.perm_batch = (int)pb;
+    w.batches = (P + pb - 1) / pb;
+    w.perm = c.take<char>(moran_slab_perm_bytes(B, w.base.SG, K, w.perm_batch));
+  }
+  w.bytes = c.used();
+  return w;
+}
+
+static int check_table(const char* who, int64_t B, int K) {
+  GPZ_REQUIRE(K >= 1 && K <= KMAX && B > K, "%s: K = %d neighbours of %lld spots unsupported (1 <= K <= %d, K < B)", who, K,
+              (long long)B, KMAX);
+  return 0;
+}
+
+static int check_perm(const char* who, int64_t P, int stat, int perm_batch) {
+  GPZ_REQUIRE(P >= 1 && P < (1ll << 31), "%s: P = %lld permutations unsupported (1 <= P < 2^31)", who, (long long)P);
+  GPZ_REQUIRE(stat == 0 || stat == 1, "%s: stat %d unknown (0 Moran's I, 1 Geary's C)", who, stat);
+  GPZ_REQUIRE(perm_batch >= 0 && perm_batch <= SLAB_PERM_BATCH_MAX, "%s: perm_batch = %d unsupported (0 = chosen here, at most %d)",
+              who, perm_batch, SLAB_PERM_BATCH_MAX);
+  return 0;
+}
+
+struct PermCall {                 // perms == nullptr: the statistics alone
+  const int32_t* perms;
+  int64_t P;
+  int stat, perm_batch;
+  double *value, *sims;
+  int32_t *n_ge, *n_le;
+  double *sim_mean, *sim_m2;
+};
+
+// Per slab: the residual pass once, the wide column pass once, then every batch of permutations.  Without permutations the
+// five statistics go to I, C, res_mean, res_var, kurtosis; with them the observed statistic goes to pc.value and the other
+// of I and C into the scratch.
+static int run_wide(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, double* I, double* C,
+                    double* res_mean, double* res_var, double* kurtosis, const PermCall& pc, int32_t* info, void* partials,
+                    size_t partials_bytes, void* stream) {
+  const bool permute = pc.perms != nullptr;
+  if (int rc = check_shape(who, c.B, c.D, c.G, c.Lt, c.nnz, slab_genes)) return rc;
+  if (int rc = check_call(who, c, partials)) return rc;
+  GPZ_REQUIRE(nbr && (I || C) && (permute || (I && C)) && res_mean && res_var && kurtosis && info, "%s: null pointer", who);
+  if (int rc = check_table(who, c.B, K)) return rc;
+  const WidePlan w = make_wide_plan(c.B, c.G, c.Lt, K, permute ? pc.P : 0, slab_genes, pc.perm_batch, partials);
+  GPZ_REQUIRE(partials_bytes >= w.bytes, "%s: partials too small (%zu bytes, %zu needed)", who, partials_bytes, w.bytes);
+  const Plan& p = w.base;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  GPZ_HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t), s));
+  if (permute) {
+    GPZ_HIP_OK(hipMemsetAsync(pc.n_ge, 0, size_t(c.G) * sizeof(int32_t), s));
+    GPZ_HIP_OK(hipMemsetAsync(pc.n_le, 0, size_t(c.G) * sizeof(int32_t), s));
+    GPZ_HIP_OK(hipMemsetAsync(pc.sim_mean, 0, size_t(c.G) * sizeof(double), s));
+    GPZ_HIP_OK(hipMemsetAsync(pc.sim_m2, 0, size_t(c.G) * sizeof(double), s));
+  }
+  Args a;
+  fill_args(a, c, p);
+  a.out = p.slab; a.SN = p.SN;
+  if (int rc = launch_factors(a, s)) return rc;
+  for (int64_t sl = 0; sl < p.nslabs; ++sl) {
+    a.g0 = sl * p.SG;
+    a.ng = c.G - a.g0 < p.SG ? c.G - a.g0 : p.SG;
+    a.ld = (a.ng + 63) / 64 * 64;
+    if (int rc = residual_slab(a, c.sparse, s)) return rc;
+    if (int rc = moran_slab_wide_run(p.slab, c.B, a.ng, a.ld, nbr, K, I ? I + a.g0 : nullptr, C ? C + a.g0 : nullptr,
+                                     res_mean + a.g0, res_var + a.g0, kurtosis + a.g0, info, w.wide, s))
+      return rc;
+    if (!permute) continue;
+    const SlabPermOut o{pc.n_ge + a.g0, pc.n_le + a.g0, pc.sim_mean + a.g0, pc.sim_m2 + a.g0,
+                        pc.sims ? pc.sims + a.g0 * pc.P : nullptr, pc.P, info};
+    if (int rc = moran_slab_perm_run(p.slab, c.B, a.ng, a.ld, nbr, K, pc.stat, pc.perms, pc.P, w.perm_batch, res_mean + a.g0,
+                                     w.wide, o, w.perm, s))
+      return rc;
+  }
+  return 0;
+}
+
+static int run_stats(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, double* I, double* C,
+                     double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials, size_t partials_bytes,
+                     void* stream) {
+  return run_wide(who, c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, PermCall{}, info, partials, partials_bytes, stream);
+}
+
+// value is the observed I or C; the wide pass does not write the other of the two
+static int run_perm(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, const PermCall& pc,
+                    double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials, size_t partials_bytes,
+                    void* stream) {
+  GPZ_REQUIRE(pc.perms && pc.value && pc.n_ge && pc.n_le && pc.sim_mean && pc.sim_m2, "%s: null pointer", who);
+  if (int rc = check_perm(who, pc.P, pc.stat, pc.perm_batch)) return rc;
+  return run_wide(who, c, nbr, K, slab_genes, pc.stat == 0 ? pc.value : nullptr, pc.stat == 0 ? nullptr : pc.value, res_mean,
+                  res_var, kurtosis, pc, info, partials, partials_bytes, stream);
+}
+
 }  // namespace rsd
 }  // namespace gpz
 
@@ -491,4 +616,76 @@ extern "C" int gpz_residual_morans_i_sparse(const float* mean, const float* scal
                     kind, lognormal_mean, true};
   return rsd::run_moran("gpz_residual_morans_i_sparse", c, nbr, K, slab_genes, I, res_mean, res_var, info, partials,
                         partials_bytes, stream);
+}
+
+extern "C" int gpz_residual_autocorr_perm_plan(int64_t B, int64_t D, int32_t Lt, int32_t K, int64_t P, int64_t nnz,
+                                               int64_t slab_genes_wanted, int32_t perm_batch_wanted, int64_t* slab_genes,
+                                               int64_t* n_slabs, int32_t* perm_batch, int64_t* batches, int64_t* partials_bytes) {
+  const char* who = "gpz_residual_autocorr_perm_plan";
+  if (int rc = rsd::check_shape(who, B, D, D, Lt, nnz, slab_genes_wanted)) return rc;
+  if (int rc = rsd::check_table(who, B, K)) return rc;
+  if (P != 0)                                   // P = 0: the scratch of the stats entries, no permutation arrays
+    if (int rc = rsd::check_perm(who, P, 0, perm_batch_wanted)) return rc;
+  const rsd::WidePlan w = rsd::make_wide_plan(B, D, Lt, K, P, slab_genes_wanted, perm_batch_wanted, nullptr);
+  if (slab_genes) *slab_genes = w.base.SG;
+  if (n_slabs) *n_slabs = w.base.nslabs;
+  if (perm_batch) *perm_batch = w.perm_batch;
+  if (batches) *batches = w.batches;
+  if (partials_bytes) *partials_bytes = (int64_t)w.bytes;
+  return 0;
+}
+
+extern "C" int gpz_residual_spatial_stats(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                                          const float* y, const int32_t* genes, const int64_t* nbr, int64_t B, int64_t D, int64_t G,
+                                          int32_t Lt, int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean,
+                                          int64_t slab_genes, double* I, double* C, double* res_mean, double* res_var,
+                                          double* kurtosis, int32_t* info, void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c{mean, scale, W, V, theta, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, family, kind,
+                    lognormal_mean, false};
+  return rsd::run_stats("gpz_residual_spatial_stats", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info, partials,
+                        partials_bytes, stream);
+}
+
+extern "C" int gpz_residual_spatial_stats_sparse(const float* mean, const float* scale, const float* W, const float* V,
+                                                 const float* theta, const int64_t* row_ptr, const int32_t* row_spot,
+                                                 const int32_t* row_perm, const float* col_val, const int32_t* genes,
+                                                 const int64_t* nbr, int64_t B, int64_t D, int64_t nnz, int64_t G, int32_t Lt,
+                                                 int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean,
+                                                 int64_t slab_genes, double* I, double* C, double* res_mean, double* res_var,
+                                                 double* kurtosis, int32_t* info, void* partials, size_t partials_bytes,
+                                                 void* stream) {
+  const rsd::Call c{mean, scale, W, V, theta, nullptr, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt, family,
+                    kind, lognormal_mean, true};
+  return rsd::run_stats("gpz_residual_spatial_stats_sparse", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info,
+                        partials, partials_bytes, stream);
+}
+
+extern "C" int gpz_residual_autocorr_perm(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                                          const float* y, const int32_t* genes, const int64_t* nbr, const int32_t* perms, int64_t B,
+                                          int64_t D, int64_t G, int32_t Lt, int32_t K, int32_t family, int32_t kind,
+                                          int32_t lognormal_mean, int64_t slab_genes, int64_t P, int32_t stat, int32_t perm_batch,
+                                          double* value, int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2,
+                                          double* sims, double* res_mean, double* res_var, double* kurtosis, int32_t* info,
+                                          void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c{mean, scale, W, V, theta, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, family, kind,
+                    lognormal_mean, false};
+  const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
+  return rsd::run_perm("gpz_residual_autocorr_perm", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
+                       partials_bytes, stream);
+}
+
+extern "C" int gpz_residual_autocorr_perm_sparse(const float* mean, const float* scale, const float* W, const float* V,
+                                                 const float* theta, const int64_t* row_ptr, const int32_t* row_spot,
+                                                 const int32_t* row_perm, const float* col_val, const int32_t* genes,
+                                                 const int64_t* nbr, const int32_t* perms, int64_t B, int64_t D, int64_t nnz,
+                                                 int64_t G, int32_t Lt, int32_t K, int32_t family, int32_t kind,
+                                                 int32_t lognormal_mean, int64_t slab_genes, int64_t P, int32_t stat,
+                                                 int32_t perm_batch, double* value, int32_t* n_ge, int32_t* n_le, double* sim_mean,
+                                                 double* sim_m2, double* sims, double* res_mean, double* res_var, double* kurtosis,
+                                                 int32_t* info, void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c{mean, scale, W, V, theta, nullptr, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt, family,
+                    kind, lognormal_mean, true};
+  const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
+  return rsd::run_perm("gpz_residual_autocorr_perm_sparse", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
+                       partials_bytes, stream);
 }

@@ -12,6 +12,7 @@
 // The narrow instantiation adds what the wide one adds to its first two sums, so I has the same bits from either.
 //   gpz_morans_i             narrow, the first L columns of an (N, L) array, fp32 or fp64
 //   moran_slab_run           narrow, the columns of an fp32 residual slab wider than what is scored (moran_pass.h; residual.hip)
+//   moran_slab_wide_run      wide, the same columns; moran_slab_perm_run scores them under relabelled tables (further down)
 //   gpz_spatial_stats        wide, as gpz_morans_i takes its columns
 //   gpz_gene_spatial_stats_sparse   the by-gene arrays of a whole data set stored as its non-zeros: the wide instantiation of
 //                            the gene pass of moran_expr.h.  I has gpz_gene_morans_i_sparse's bits.
@@ -200,6 +201,190 @@ static int mi_check_args(const char* who, int64_t N, int64_t L, int32_t K, int32
   return 0;
 }
 
+// ---- the permutation column pass (moran_pass.h) ------------------------------------------------------------------------
+// For a column z, centred by the mean the wide pass left, sum z^2, sum z^4 and the mean do not change under a relabelling
+// of the rows; a_pi = sum_a z_a (1 / K) sum_m z[T_pi[a, m]] and G_pi = sum_a sum_m (z_a - z[T_pi[a, m]])^2 do.
+//   rp_rows<STAT, FULL>   block (chunk of 256 rows, column tile), the threads of mi_rows (cw columns x row slots), for a
+//                         batch of up to RP_BATCH permutations: a thread reads its row's value once per batch and gathers,
+//                         per permutation, the K neighbours named by the relabelled table -- each a row of the slab,
+//                         contiguous over the tile's columns (whole 256-byte segments at cw = 64), RP_KU of them requested
+//                         together.  One accumulator per permutation in registers; the row slots are folded as mi_rows
+//                         folds them, RP_GROUP permutations per pair of barriers.  FULL (cw = 64): a wave is one row slot,
+//                         so the table row's address is wave-uniform and can be read by scalar loads.
+//   rp_observed           per column: the observed numerators and the denominator from the wide pass's partials, in
+//                         mi_final's order (they are the sums I and C were divided from)
+//   rp_final<STAT>        block = column, wave = permutation: the chunks' partials in mi_final's order (strided over 256
+//                         virtual threads -- four registers of 64 lanes -- then its tree: registers, then shuffles), the
+//                         value by mi_final's expression; then one thread folds the batch into the column's running
+//                         n_ge, n_le, mean and M2 (Welford) in permutation order, so nothing depends on the batch size.
+// With the identity for pi every sum is the wide pass's, bit for bit.
+constexpr int RP_BATCH = SLAB_PERM_BATCH_MAX;
+constexpr int RP_GROUP = 8;
+constexpr int RP_KU = 8;
+constexpr int RP_MORAN = 0, RP_GEARY = 1;
+
+template <int STAT, bool FULL>
+__global__ __launch_bounds__(MI_THREADS) void rp_rows(const float* __restrict__ V, int64_t N, int64_t L, int64_t ld, int cw,
+                                                      const int32_t* __restrict__ T, int K, int pb, const double* __restrict__ mean,
+                                                      double* __restrict__ part) {
+  __shared__ double red[RP_GROUP][MI_THREADS];
+  const int c = FULL ? int(threadIdx.x & 63) : int(threadIdx.x) % cw;
+  const int slot = FULL ? __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)) : int(threadIdx.x) / cw;
+  const int slots = MI_THREADS / cw;
+  const int64_t l = int64_t(blockIdx.y) * cw + c;
+  const int64_t r0 = int64_t(blockIdx.x) * MI_ROWS, r1 = r0 + MI_ROWS < N ? r0 + MI_ROWS : N;
+  double acc[RP_BATCH];
+#pragma unroll
+  for (int q = 0; q < RP_BATCH; ++q) acc[q] = 0.0;
+  if (l < L) {
+    const double ref = mean[l];
+    const double w = 1.0 / K;
+    for (int64_t i = r0 + slot; i < r1; i += slots) {
+      const double z = double(V[i * ld + l]) - ref;
+#pragma unroll
+      for (int q = 0; q < RP_BATCH; ++q) {
+        if (q < pb) {
+          const int32_t* __restrict__ row = T + (int64_t(q) * N + i) * K;
+          double lag = 0.0, gi = 0.0;
+          for (int k0 = 0; k0 < K; k0 += RP_KU) {
+            int32_t j[RP_KU];
+            float v[RP_KU];
+#pragma unroll
+            for (int u = 0; u < RP_KU; ++u) j[u] = k0 + u < K ? row[k0 + u] : -1;
+#pragma unroll
+            for (int u = 0; u < RP_KU; ++u) {
+              j[u] = (j[u] >= 0 && j[u] < N) ? j[u] : -1;         // never read outside the slab; the relabel kernel has told the caller
+              v[u] = V[(j[u] >= 0 ? int64_t(j[u]) : i) * ld + l];  // no branch between the requests: a skipped entry reads row i
+            }
+#pragma unroll
+            for (int u = 0; u < RP_KU; ++u) {
+              if (j[u] < 0) continue;
+              const double zj = double(v[u]) - ref;
+              if constexpr (STAT == RP_GEARY) gi += (z - zj) * (z - zj);
+              else lag += zj;
+            }
+          }
+          if constexpr (STAT == RP_GEARY) acc[q] += gi;
+          else acc[q] += z * (lag * w);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int g0 = 0; g0 < RP_BATCH; g0 += RP_GROUP) {
+    if (g0 < pb) {                                                // the same for every thread of the block
+#pragma unroll
+      for (int u = 0; u < RP_GROUP; ++u) red[u][threadIdx.x] = acc[g0 + u];
+      __syncthreads();
+      if (slot == 0 && l < L) {
+#pragma unroll
+        for (int u = 0; u < RP_GROUP; ++u) {
+          if (g0 + u >= pb) continue;
+          double a = acc[g0 + u];
+          for (int r = 1; r < slots; ++r) a += red[u][r * cw + c];
+          part[(int64_t(g0 + u) * gridDim.x + blockIdx.x) * L + l] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// the sum of p[ch * stride], ch < chunks, as mi_final adds it: thread t of 256 takes ch = t, t + 256, ..., then the tree over
+// the 256 sums.  Lane l holds threads l, l + 64, l + 128, l + 192; the result is lane 0's.
+__device__ __forceinline__ double rp_fold(const double* __restrict__ p, int64_t stride, int64_t chunks, int lane) {
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    for (int64_t ch = lane + 64 * u; ch < chunks; ch += MI_THREADS) v[u] += p[ch * stride];
+  double t = (v[0] + v[2]) + (v[1] + v[3]);
+  for (int h = 32; h >= 1; h >>= 1) t += __shfl_down(t, h, 64);
+  return t;
+}
+
+// obs (L, 3): sum z lag / K, sum z^2, G of the unpermuted column, from the wide pass's partials (chunks, L, 5)
+__global__ __launch_bounds__(MI_THREADS) void rp_observed(const double* __restrict__ wide, int64_t chunks, int64_t L,
+                                                          double* __restrict__ obs) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t l = blockIdx.x;
+  if (wave >= 3) return;
+  const double t = rp_fold(wide + l * mi_part(true) + 1 + wave, L * mi_part(true), chunks, lane);
+  if (lane == 0) obs[l * 3 + wave] = t;
+}
+
+template <int STAT>
+__global__ __launch_bounds__(MI_THREADS) void rp_final(const double* __restrict__ part, int64_t chunks, int64_t L, int64_t N, int K,
+                                                       int pb, int64_t p0, int64_t P, const double* __restrict__ obs, SlabPermOut o) {
+  __shared__ double sV[RP_BATCH], sT[RP_BATCH];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t l = blockIdx.x;
+  const double Nd = double(N), den = obs[l * 3 + 1];
+  for (int q = wave; q < pb; q += MI_THREADS / 64) {
+    const double t = rp_fold(part + int64_t(q) * chunks * L + l, L, chunks, lane);
+    if (lane == 0) {
+      sT[q] = t;
+      sV[q] = STAT == RP_GEARY ? ((Nd - 1.0) * t) / (2.0 * Nd * double(K) * den) : t / den;      // mi_final's expressions
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double t0 = obs[l * 3 + (STAT == RP_GEARY ? 2 : 0)];
+  int32_t ge = o.n_ge[l], le = o.n_le[l];
+  double mean = o.sim_mean[l], m2 = o.sim_m2[l];
+  for (int q = 0; q < pb; ++q) {
+    const double vq = sV[q], tq = sT[q];
+    const bool ok = vq == vq;                                     // a constant column counts nothing
+    ge += (ok && tq >= t0) ? 1 : 0;
+    le += (ok && tq <= t0) ? 1 : 0;
+    const double delta = vq - mean;
+    mean += delta / double(p0 + q + 1);
+    m2 += delta * (vq - mean);
+    if (o.sims) o.sims[l * o.sims_ld + p0 + q] = vq;
+  }
+  o.n_ge[l] = ge;
+  o.n_le[l] = le;
+  o.sim_mean[l] = mean;
+  o.sim_m2[l] = m2;
+}
+
+struct RpPlan {
+  int32_t* T;         // (perm_batch, B, K)
+  int32_t* written;   // (perm_batch, B)
+  double* part;       // (perm_batch, chunks, cols)
+  double* obs;        // (cols, 3)
+  int64_t chunks;
+  size_t bytes;
+};
+
+static RpPlan rp_plan(int64_t B, int64_t cols, int K, int pb, void* scratch) {
+  Carver c(scratch);
+  RpPlan p{};
+  p.chunks = (B + MI_ROWS - 1) / MI_ROWS;
+  p.T = c.take<int32_t>(size_t(pb) * size_t(B) * size_t(K));
+  p.written = c.take<int32_t>(size_t(pb) * size_t(B));
+  p.part = c.take<double>(size_t(pb) * size_t(p.chunks) * size_t(cols));
+  p.obs = c.take<double>(size_t(cols) * 3);
+  p.bytes = c.used();
+  return p;
+}
+
+template <int STAT>
+static int rp_run(const float* slab, int64_t B, int64_t cols, int64_t ld, const int64_t* nbr, int K, const int32_t* perms, int64_t P,
+                  int perm_batch, const double* mean, const SlabPermOut& o, const RpPlan& pl, hipStream_t s) {
+  const int cw = mi_cw(cols);
+  const dim3 rows(unsigned(pl.chunks), unsigned((cols + cw - 1) / cw)), block(MI_THREADS);
+  for (int64_t p0 = 0; p0 < P; p0 += perm_batch) {
+    const int pb = int(P - p0 < perm_batch ? P - p0 : perm_batch);
+    if (int rc = relabel_tables(nbr, nullptr, perms + p0 * B, B, K, pb, pl.T, nullptr, pl.written, o.info, s)) return rc;
+    if (cw == 64) hipLaunchKernelGGL((rp_rows<STAT, true>), rows, block, 0, s, slab, B, cols, ld, cw, pl.T, K, pb, mean, pl.part);
+    else hipLaunchKernelGGL((rp_rows<STAT, false>), rows, block, 0, s, slab, B, cols, ld, cw, pl.T, K, pb, mean, pl.part);
+    GPZ_LAUNCH_OK();
+    hipLaunchKernelGGL((rp_final<STAT>), dim3(unsigned(cols)), block, 0, s, pl.part, pl.chunks, cols, B, K, pb, p0, P, pl.obs, o);
+    GPZ_LAUNCH_OK();
+  }
+  return 0;
+}
+
 }  // namespace grk
 
 // moran_pass.h: the same four launches over a residual slab, with the column means and variances as outputs
@@ -210,6 +395,31 @@ int moran_slab_run(const float* slab, int64_t B, int64_t cols, int64_t ld, const
   grk::MiPlan pl = grk::mi_plan(B, cols, false, scratch);
   pl.mean = mean;
   return grk::mi_run<float, false>(slab, B, cols, ld, nbr, K, grk::SsOut{I, nullptr, nullptr, var, nullptr}, info, pl, s);
+}
+
+// the wide instantiation over the same columns; its partials stay where moran_slab_perm_run looks for them
+size_t moran_slab_wide_bytes(int64_t B, int64_t cols) { return grk::mi_plan(B, cols, true, nullptr).bytes; }
+
+int moran_slab_wide_run(const float* slab, int64_t B, int64_t cols, int64_t ld, const int64_t* nbr, int K, double* I, double* C,
+                        double* mean, double* var, double* kurtosis, int32_t* info, void* scratch, hipStream_t s) {
+  grk::MiPlan pl = grk::mi_plan(B, cols, true, scratch);
+  pl.mean = mean;
+  return grk::mi_run<float, true>(slab, B, cols, ld, nbr, K, grk::SsOut{I, C, nullptr, var, kurtosis}, info, pl, s);
+}
+
+size_t moran_slab_perm_bytes(int64_t B, int64_t cols, int K, int perm_batch) {
+  return grk::rp_plan(B, cols, K, perm_batch, nullptr).bytes;
+}
+
+int moran_slab_perm_run(const float* slab, int64_t B, int64_t cols, int64_t ld, const int64_t* nbr, int K, int stat,
+                        const int32_t* perms, int64_t P, int perm_batch, const double* mean, const void* wide_scratch,
+                        const SlabPermOut& o, void* scratch, hipStream_t s) {
+  const grk::RpPlan pl = grk::rp_plan(B, cols, K, perm_batch, scratch);
+  const grk::MiPlan wide = grk::mi_plan(B, cols, true, const_cast<void*>(wide_scratch));
+  hipLaunchKernelGGL(grk::rp_observed, dim3(unsigned(cols)), dim3(grk::MI_THREADS), 0, s, wide.part, wide.chunks, cols, pl.obs);
+  GPZ_LAUNCH_OK();
+  return stat == grk::RP_GEARY ? grk::rp_run<grk::RP_GEARY>(slab, B, cols, ld, nbr, K, perms, P, perm_batch, mean, o, pl, s)
+                               : grk::rp_run<grk::RP_MORAN>(slab, B, cols, ld, nbr, K, perms, P, perm_batch, mean, o, pl, s);
 }
 
 }  // namespace gpz

@@ -789,12 +789,91 @@ class ResidualAutocorr(NamedTuple):
     residual_var: torch.Tensor
 
 
+class ResidualGeary(NamedTuple):
+    """``residual_autocorr(mode="geary")``: Geary's C of each gene's residuals, fp64 tensors: ``C`` (D,), ``expected`` = 1,
+    ``variance`` (0-d under normality, (D,) under randomisation), ``z`` = (C - 1) / sqrt(variance) (D,) -- C < 1, a NEGATIVE
+    z, is positive autocorrelation -- and the residuals' ``residual_mean``, ``residual_var`` and ``residual_kurtosis``
+    (m4 / m2^2; 3 for a normal sample) (D,)."""
+    C: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+    residual_mean: torch.Tensor
+    residual_var: torch.Tensor
+    residual_kurtosis: torch.Tensor
+
+
+class ResidualAutocorrPerm(NamedTuple):
+    """``residual_autocorr(n_perms=)``: the fields of ``ResidualAutocorr``, ``residual_kurtosis``, and the permutation
+    null's fields with the meaning they have in ``utilities.GeneAutocorrPerm``: ``n_perms`` = P; ``n_ge`` / ``n_le`` the
+    permutations whose I is >= / <= the observed one; ``pval_greater`` = (n_ge + 1) / (P + 1), the p-value for positive
+    autocorrelation; ``pval_less``; ``pval_sim`` the smaller of the two; ``mean_sim``, ``var_sim``, ``z_sim``,
+    ``pval_z_sim`` of the simulated I; ``sims`` (D, P) or None."""
+    I: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+    residual_mean: torch.Tensor
+    residual_var: torch.Tensor
+    residual_kurtosis: torch.Tensor
+    n_perms: int
+    n_ge: torch.Tensor
+    n_le: torch.Tensor
+    pval_greater: torch.Tensor
+    pval_less: torch.Tensor
+    pval_sim: torch.Tensor
+    mean_sim: torch.Tensor
+    var_sim: torch.Tensor
+    z_sim: torch.Tensor
+    pval_z_sim: torch.Tensor
+    sims: "torch.Tensor | None"
+
+
+class ResidualGearyPerm(NamedTuple):
+    """``residual_autocorr(mode="geary", n_perms=)``: the fields of ``ResidualGeary`` and the permutation null's, as in
+    ``ResidualAutocorrPerm`` with C for I -- so ``pval_less`` = (n_le + 1) / (P + 1) is the p-value for positive
+    autocorrelation (a small C) and ``pval_greater`` the one for negative."""
+    C: torch.Tensor
+    expected: torch.Tensor
+    variance: torch.Tensor
+    z: torch.Tensor
+    residual_mean: torch.Tensor
+    residual_var: torch.Tensor
+    residual_kurtosis: torch.Tensor
+    n_perms: int
+    n_ge: torch.Tensor
+    n_le: torch.Tensor
+    pval_greater: torch.Tensor
+    pval_less: torch.Tensor
+    pval_sim: torch.Tensor
+    mean_sim: torch.Tensor
+    var_sim: torch.Tensor
+    z_sim: torch.Tensor
+    pval_z_sim: torch.Tensor
+    sims: "torch.Tensor | None"
+
+
 def _cat_factors(qF_list, W_list):
     return (torch.cat([q.mean for q in qF_list], dim=0), torch.cat([q.scale for q in qF_list], dim=0),
             torch.cat(list(W_list), dim=1))
 
 
-def residual_autocorr(qF_list, W_list, V_pos, y, nbr, *, theta_pos=None, kind="pearson", lognormal_mean=True, slab_genes=0):
+def _residual_null_args(who, B, mode, assumption, n_perms, perms):
+    """The refusals of the new keywords that need no device: (permute, P, perms or None)."""
+    from .utilities import _autocorr_perms
+    if mode not in ("moran", "geary"):
+        raise ValueError(f"{who}: mode={mode!r} unknown ('moran', 'geary')")
+    if assumption not in ("normality", "randomisation"):
+        raise ValueError(f"{who}: assumption={assumption!r} unknown ('normality', 'randomisation')")
+    if assumption == "randomisation" and B < 4:
+        raise ValueError(f"{who}: assumption='randomisation' needs B >= 4 spots, got {B}")
+    if n_perms is None and perms is None:
+        return False, 0, None
+    return (True, *_autocorr_perms(who, B, n_perms, perms))
+
+
+def residual_autocorr(qF_list, W_list, V_pos, y, nbr, *, theta_pos=None, kind="pearson", lognormal_mean=True, slab_genes=0,
+                      mode="moran", assumption="normality", n_perms=None, seed=0, perms=None, return_sims=False):
     """Is spatial structure left in what the model did not explain, and in which genes: Moran's I of every gene's residuals
     under the predictive mean rate mu = V * sum_k W_k E_q[exp F_k] (as in ``poisson_deviance``) over the neighbour table
     ``nbr`` (B, K) of the B scored spots -- the evidence for adding factors, shortening a length scale or moving a gene to
@@ -804,15 +883,73 @@ def residual_autocorr(qF_list, W_list, V_pos, y, nbr, *, theta_pos=None, kind="p
     (``ops.residual_morans_i``).  Returns a ``ResidualAutocorr``.
 
     ``z`` uses squidpy's normal approximation of I's moments under no autocorrelation and ignores the degrees of freedom
-    the fit used: it ranks genes, it is not a calibrated test."""
+    the fit used: it ranks genes, it is not a calibrated test.
+
+    The keywords below have the meaning they have in ``utilities.gene_autocorr``; with all of them at their defaults the
+    call is the one above, bit for bit.  ``mode="geary"`` scores Geary's C (``ops.residual_spatial_stats``) and returns a
+    ``ResidualGeary``: 1 in expectation, BELOW 1 -- a negative ``z`` -- for positive autocorrelation.
+    ``assumption="randomisation"`` replaces the normality moments, which depend on the graph alone, by the randomisation
+    moments of Cliff & Ord at each gene's residual kurtosis (``utilities._autocorr_moments``; B >= 4): ``variance`` and
+    ``z`` become (D,) tensors.  Residuals of counts are far from normal -- a single large count gives a gene a kurtosis in
+    the hundreds -- so these are the moments to use.  ``n_perms=P`` (permutation p is ``torch.randperm(B, generator=g,
+    device=...)`` from one generator seeded with ``seed``, drawn one at a time in order) or ``perms=`` (a (P, B) integer
+    tensor, used as given) adds the permutation null, scored while each residual slab is resident
+    (``ops.residual_autocorr_perm``), and returns a ``ResidualAutocorrPerm`` / ``ResidualGearyPerm``; ``return_sims=True``
+    keeps the (D, P) simulated values.  For Moran ``pval_greater`` is the p-value for positive autocorrelation, for Geary
+    ``pval_less``; the smallest attainable value is 1 / (P + 1).  The comparisons are made on the fp64 numerators;
+    residuals are real-valued, so a mathematical tie may fall either way in the last bit.
+
+    What the permutation null is and is not: it is exact for exchangeable residuals, and a well-specified fit gives
+    approximately exchangeable residuals -- but residuals under a fitted rate are not exactly exchangeable (their variance
+    follows the rate, which the Pearson and deviance forms only standardise to first order), and the null still ignores
+    the degrees of freedom the fit used, like ``z``.  It calibrates against the residuals' own distribution, which the
+    normal approximation does not; it does not turn the score into a test of the model."""
+    B = int(nbr.shape[0]) if isinstance(nbr, torch.Tensor) else len(nbr)
+    null = _residual_null_args("residual_autocorr", B, mode, assumption, n_perms, perms)
+    return _residual_autocorr_checked(qF_list, W_list, V_pos, y, nbr, null, theta_pos, kind, lognormal_mean, slab_genes, mode,
+                                      assumption, seed, return_sims)
+
+
+def _residual_autocorr_checked(qF_list, W_list, V_pos, y, nbr, null, theta_pos, kind, lognormal_mean, slab_genes, mode, assumption,
+                               seed, return_sims):
+    """``residual_autocorr`` behind its refusals: ``null`` is what ``_residual_null_args`` returned for the B scored spots."""
     from . import ops
-    from .utilities import _moran_moments
+    from .utilities import _autocorr_moments, _moran_moments, _perm_fields
+    permute, P, perms = null
+    B = int(nbr.shape[0])
     with torch.no_grad():
         mean, scale, W = _cat_factors(qF_list, W_list)
-        r = ops.residual_morans_i(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes)
-        expected, variance = _moran_moments(nbr.to(device=r["I"].device, dtype=torch.int64))
-        return ResidualAutocorr(I=r["I"], expected=expected, variance=variance, z=(r["I"] - expected) / torch.sqrt(variance),
-                                residual_mean=r["residual_mean"], residual_var=r["residual_var"])
+        if mode == "moran" and assumption == "normality" and not permute:
+            r = ops.residual_morans_i(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes)
+            expected, variance = _moran_moments(nbr.to(device=r["I"].device, dtype=torch.int64))
+            return ResidualAutocorr(I=r["I"], expected=expected, variance=variance, z=(r["I"] - expected) / torch.sqrt(variance),
+                                    residual_mean=r["residual_mean"], residual_var=r["residual_var"])
+        if permute:
+            if perms is None:
+                dev = mean.device
+                g = torch.Generator(device=dev)
+                g.manual_seed(int(seed))
+                perms = torch.empty((P, B), dtype=torch.int32, device=dev)
+                for p in range(P):
+                    perms[p] = torch.randperm(B, generator=g, device=dev)
+            r, mom = ops.residual_autocorr_perm(mean, scale, W, V_pos, y, nbr, perms, theta_pos, None, kind, lognormal_mean,
+                                                stat=mode, return_sims=return_sims, slab_genes=slab_genes)
+            stat = r.value
+        else:
+            mom = ops.residual_spatial_stats(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes)
+            stat = mom["C" if mode == "geary" else "I"]
+        table = nbr.to(device=stat.device, dtype=torch.int64)
+        if mode == "moran" and assumption == "normality":
+            expected, variance = _moran_moments(table)                    # the moments of the call without the new keywords
+        else:
+            m = _autocorr_moments(table, mom["kurtosis"] if assumption == "randomisation" else None)
+            key = ("VC" if mode == "geary" else "VI") + ("_rand" if assumption == "randomisation" else "_norm")
+            expected, variance = m["EC" if mode == "geary" else "EI"], m[key]
+        base = (stat, expected, variance, (stat - expected) / torch.sqrt(variance), mom["residual_mean"], mom["residual_var"])
+        kinds = (ResidualGeary, ResidualGearyPerm) if mode == "geary" else (ResidualAutocorr, ResidualAutocorrPerm)
+        if not permute:
+            return kinds[0](*base, mom["kurtosis"]) if mode == "geary" else kinds[0](*base)
+        return kinds[1](*base, mom["kurtosis"], *_perm_fields(stat, r, P))
 
 
 def count_residuals(qF_list, W_list, V_pos, y, genes, *, theta_pos=None, kind="pearson", lognormal_mean=True):
@@ -837,18 +974,25 @@ class _ResidualScores:
         return _deviance_theta(self, self.sf.W if hasattr(self, "sf") else self.W, family, theta)
 
     def residual_autocorr(self, X, y, idx=None, V=None, *, kind="pearson", family="model", theta=None, n_neighs=6, graph=None,
-                          lognormal_mean=True, **kwargs):
+                          lognormal_mean=True, mode="moran", assumption="normality", n_perms=None, seed=0, perms=None,
+                          return_sims=False, **kwargs):
         """Moran's I of every gene's residuals at ``X`` (or ``X[idx]``) over the scored spots' ``n_neighs``-nearest-neighbour
         graph (``ops.spatial_knn``), or over ``graph=``, an (B, K) table: a ``ResidualAutocorr``.  ``y`` (D, B) dense or a
         whole ``SparseCounts``; ``V`` as in ``deviance``.  ``family`` defaults to "model", unlike ``deviance``: residuals are
         standardised by the model's own variance, so an NB fit is scored with its theta (``theta=`` overrides it, or scores
-        a Poisson fit under ``family="nb"``)."""
+        a Poisson fit under ``family="nb"``).  ``mode``, ``assumption``, ``n_perms``, ``seed``, ``perms`` and
+        ``return_sims`` as in ``likelihoods.residual_autocorr``: Geary's C, the randomisation moments and the permutation
+        null over the B scored spots; at their defaults the call is the one without them."""
         from . import ops
         theta_pos = self._residual_theta(kind, family, theta)
+        mask = idx is not None and getattr(idx, "dtype", None) == torch.bool
+        B = int(X.shape[0]) if idx is None else int(idx.sum()) if mask else len(idx)      # the scored spots: the rows of X[idx]
+        null = _residual_null_args(f"{type(self).__name__}.residual_autocorr", B, mode, assumption, n_perms, perms)
         with torch.no_grad():
             qF, W, Vp, Xb = self._score_parts(X, idx, V, kwargs)
             nbr = ops.spatial_knn(Xb, int(n_neighs)) if graph is None else torch.as_tensor(graph)
-            return residual_autocorr(qF, W, Vp, y, nbr, theta_pos=theta_pos, kind=kind, lognormal_mean=lognormal_mean)
+            return _residual_autocorr_checked(qF, W, Vp, y, nbr, null, theta_pos, kind, lognormal_mean, 0, mode, assumption, seed,
+                                              return_sims)
 
     def residuals(self, X, y, genes, idx=None, V=None, *, kind="pearson", family="model", theta=None, lognormal_mean=True,
                   **kwargs):

@@ -1626,19 +1626,29 @@ def morans_perm_plan(N: int, D: int, K: int, P: int, nnz: Optional[int] = None, 
     return _perm_plan("morans_perm_plan", "morans", None, N, D, K, P, nnz, perm_batch, line_mode)
 
 
-def _morans_perm(who: str, family: str, stat, N: int, D: int, nnz, dev, inputs, nbr, perms, return_sims, perm_batch, line_mode):
-    """The call behind the four permutation entries, named as ``_perm_plan`` names them: ``family`` "autocorr" with ``stat``
-    0 (Moran) or 1 (Geary), "morans" with None; ``inputs`` are the entry's leading pointers.  Returns the tensors of a
-    ``MoransPerm`` in its order."""
-    nbr, K = _nbr_table(who, nbr, N, dev)
+def _perm_table_check(who: str, perms, N: int, perm_batch) -> None:
+    """What the permutation entries check of ``perms`` and ``perm_batch`` before any device work."""
     if (not isinstance(perms, torch.Tensor) or perms.dim() != 2 or perms.shape[0] < 1 or perms.shape[1] != N
             or perms.dtype.is_floating_point or perms.dtype == torch.bool):
         raise ValueError(f"{who}: perms must be a (P, {N}) integer tensor, P >= 1")
     if isinstance(perm_batch, bool) or not isinstance(perm_batch, int) or perm_batch < 0:
         raise ValueError(f"{who}: perm_batch {perm_batch!r} must be a non-negative integer (0 = chosen by the plan)")
+
+
+def _perm_table(perms, N: int, dev):
+    """``perms`` as contiguous int32 on ``dev``."""
     if perms.dtype != torch.int32:
         perms = perms.to(device=dev, dtype=torch.int64).clamp(-1, N)                  # a wide entry stays out of range in 32 bits
-    perms = perms.to(device=dev, dtype=torch.int32).contiguous()
+    return perms.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _morans_perm(who: str, family: str, stat, N: int, D: int, nnz, dev, inputs, nbr, perms, return_sims, perm_batch, line_mode):
+    """The call behind the four permutation entries, named as ``_perm_plan`` names them: ``family`` "autocorr" with ``stat``
+    0 (Moran) or 1 (Geary), "morans" with None; ``inputs`` are the entry's leading pointers.  Returns the tensors of a
+    ``MoransPerm`` in its order."""
+    nbr, K = _nbr_table(who, nbr, N, dev)
+    _perm_table_check(who, perms, N, perm_batch)
+    perms = _perm_table(perms, N, dev)
     P = int(perms.shape[0])
     plan = _perm_plan(who, family, stat, N, D, K, P, nnz, perm_batch, line_mode)
     entry = f"gpz_{family}_perm_rows" if nnz is None else f"gpz_gene_{family}_perm_sparse"
@@ -2047,6 +2057,122 @@ def residual_morans_i(mean, scale, W_pos, V_pos, y, nbr, theta_pos=None, genes=N
     if int(info.item()) != 0:
         raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
     return dict(I=out[0], residual_mean=out[1], residual_var=out[2])
+
+
+def residual_autocorr_perm_plan(B: int, D: int, Lt: int, K: int, P: int, nnz: int = 0, slab_genes: int = 0,
+                                perm_batch: int = 0) -> dict:
+    """How ``residual_autocorr_perm`` covers B spots, D scored genes and P permutations over K neighbours
+    (gpz_residual_autocorr_perm_plan, a host-only query: no device needed): ``slab_genes`` and ``n_slabs`` as
+    ``residual_autocorr_plan`` gives them; ``perm_batch``, the permutations per launch as resolved (the caller's 1..32, or
+    the plan's choice, whose relabelled tables of 4 B K bytes each stay within 256 MiB); ``batches`` per slab;
+    ``partials_bytes``: the slab, plus O(perm_batch B K) table bytes, plus O(B / 256 x perm_batch x slab_genes) partial
+    sums.  ``P=0`` asks for what ``residual_spatial_stats`` needs: no tables, ``perm_batch`` = ``batches`` = 0."""
+    lib = _lib.load()
+    sg, ns, pb, nbat, nb = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
+    rc = lib.gpz_residual_autocorr_perm_plan(int(B), int(D), int(Lt), int(K), int(P), int(nnz), int(slab_genes), int(perm_batch),
+                                             C.byref(sg), C.byref(ns), C.byref(pb), C.byref(nbat), C.byref(nb))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(slab_genes=sg.value, n_slabs=ns.value, perm_batch=pb.value, batches=nbat.value, partials_bytes=int(nb.value))
+
+
+def _residual_table(who, nbr, mean, slab_genes):
+    """The checks ``residual_morans_i`` makes on its table and ``slab_genes`` before any device work; returns K."""
+    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
+        raise ValueError(f"{who}: nbr must be a (B, K) integer table")
+    K = int(nbr.shape[1])
+    if not 1 <= K <= 32:
+        raise ValueError(f"{who}: K = {K} neighbours unsupported (1..32)")
+    if int(slab_genes) != slab_genes or int(slab_genes) < 0 or int(slab_genes) % 64:
+        raise ValueError(f"{who}: slab_genes = {slab_genes!r} is not a positive multiple of 64 (or 0: the plan's choice)")
+    if nbr.shape[0] != mean.shape[-1]:
+        raise ValueError(f"{who}: nbr {tuple(nbr.shape)} for {mean.shape[-1]} spots")
+    if K >= nbr.shape[0]:
+        raise ValueError(f"{who}: {K} neighbours of {nbr.shape[0]} spots (K < B needed)")
+    return K
+
+
+def residual_spatial_stats(mean, scale, W_pos, V_pos, y, nbr, theta_pos=None, genes=None, kind="pearson",
+                           lognormal_mean: bool = True, slab_genes: int = 0) -> dict:
+    """``residual_morans_i`` with Geary's C and the kurtosis beside I (gpz_residual_spatial_stats /
+    gpz_residual_spatial_stats_sparse): a dict of fp64 (G,) tensors ``I``, ``C``, ``residual_mean``, ``residual_var`` and
+    ``kurtosis`` (m4 / m2^2 of the residuals).  ``I``, ``residual_mean`` and ``residual_var`` are ``residual_morans_i``'s at
+    the same ``slab_genes``, bit for bit.  A bad table raises ValueError (checked on the device; one synchronisation)."""
+    who = "residual_spatial_stats"
+    K = _residual_table(who, nbr, mean, slab_genes)
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
+    lib = _lib.load()
+    dev, G = a["dev"], a["G"]
+    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
+    nb = residual_autocorr_perm_plan(a["B"], G, a["Lt"], K, 0, a["nnz"], int(slab_genes))["partials_bytes"]
+    out = [torch.empty(G, dtype=torch.float64, device=dev) for _ in range(5)]
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    tail = [a["Lt"], K, a["family"], a["kind"], int(bool(lognormal_mean)), int(slab_genes), *(_ptr(t) for t in out), _ptr(info)]
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nb)
+        if a["sparse"]:
+            entry = "gpz_residual_spatial_stats_sparse"
+            rc = lib.gpz_residual_spatial_stats_sparse(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], a["nnz"], G, *tail,
+                                                       _ptr(ws), ws.numel(), _stream(dev))
+        else:
+            entry = "gpz_residual_spatial_stats"
+            rc = lib.gpz_residual_spatial_stats(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], G, *tail, _ptr(ws), ws.numel(),
+                                                _stream(dev))
+    _lib.check(rc, entry)
+    if int(info.item()) != 0:
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
+    return dict(I=out[0], C=out[1], residual_mean=out[2], residual_var=out[3], kurtosis=out[4])
+
+
+def residual_autocorr_perm(mean, scale, W_pos, V_pos, y, nbr, perms, theta_pos=None, genes=None, kind="pearson",
+                           lognormal_mean: bool = True, *, stat: str = "moran", return_sims: bool = False, perm_batch: int = 0,
+                           slab_genes: int = 0):
+    """Moran's I (``stat="moran"``) or Geary's C (``"geary"``) of every gene's residuals (``residual_morans_i``'s
+    arguments) and of their P relabellings ``perms`` (P, B) integer, r^pi[n] = r[pi[n]], scored while each residual slab is
+    resident (gpz_residual_autocorr_perm / gpz_residual_autocorr_perm_sparse): per slab the residuals are formed once, the
+    observed statistics once, then every batch of ``perm_batch`` permutations (0: ``residual_autocorr_perm_plan``'s choice).
+    Returns (``AutocorrPerm``, moments): ``value`` is ``residual_spatial_stats``' I or C, bit for bit; ``n_ge`` / ``n_le``
+    compare the fp64 numerators (residuals are real-valued: a mathematical tie may fall either way in the last bit);
+    ``sim_mean`` / ``sim_m2`` are folded in permutation order, so nothing depends on ``perm_batch``; ``sims`` (G, P) with
+    ``return_sims``.  The moments are a dict of fp64 (G,) tensors ``residual_mean``, ``residual_var`` and ``kurtosis``.  A
+    bad table and a row of ``perms`` that is no permutation raise ValueError (checked on the device; one synchronisation)."""
+    who = "residual_autocorr_perm"
+    st = _stat(who, stat)
+    K = _residual_table(who, nbr, mean, slab_genes)
+    B = int(nbr.shape[0])
+    _perm_table_check(who, perms, B, perm_batch)
+    if perm_batch > 32:
+        raise ValueError(f"{who}: perm_batch = {perm_batch} unsupported (0 = chosen by the plan, at most 32)")
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
+    lib = _lib.load()
+    dev, G = a["dev"], a["G"]
+    nbr, _ = _nbr_table(who, nbr, B, dev)
+    perms = _perm_table(perms, B, dev)
+    P = int(perms.shape[0])
+    plan = residual_autocorr_perm_plan(B, G, a["Lt"], K, P, a["nnz"], int(slab_genes), perm_batch)
+    value, mean_, m2, rmean, rvar, kurt = (torch.empty(G, dtype=torch.float64, device=dev) for _ in range(6))
+    n_ge, n_le = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
+    sims = torch.empty((G, P), dtype=torch.float64, device=dev) if return_sims else None
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    tail = [a["Lt"], K, a["family"], a["kind"], int(bool(lognormal_mean)), int(slab_genes), P, st, plan["perm_batch"], _ptr(value),
+            _ptr(n_ge), _ptr(n_le), _ptr(mean_), _ptr(m2), _ptr(sims), _ptr(rmean), _ptr(rvar), _ptr(kurt), _ptr(info)]
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, plan["partials_bytes"])
+        if a["sparse"]:
+            entry = "gpz_residual_autocorr_perm_sparse"
+            rc = lib.gpz_residual_autocorr_perm_sparse(*_residual_inputs(a), _ptr(nbr), _ptr(perms), B, a["D"], a["nnz"], G, *tail,
+                                                       _ptr(ws), ws.numel(), _stream(dev))
+        else:
+            entry = "gpz_residual_autocorr_perm"
+            rc = lib.gpz_residual_autocorr_perm(*_residual_inputs(a), _ptr(nbr), _ptr(perms), B, a["D"], G, *tail, _ptr(ws),
+                                                ws.numel(), _stream(dev))
+    _lib.check(rc, entry)
+    code = int(info.item())
+    if code == 1:
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
+    if code != 0:
+        raise ValueError(f"{who}: a row of perms is not a permutation of 0 .. B - 1 (an entry outside [0, B) or an index named twice)")
+    return AutocorrPerm(stat, value, n_ge, n_le, mean_, m2, sims), dict(residual_mean=rmean, residual_var=rvar, kurtosis=kurt)
 
 
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:

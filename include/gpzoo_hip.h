@@ -76,7 +76,11 @@
  * gpz_gene_spatial_stats_sparse, gpz_spatial_stats, gpz_gene_autocorr_perm_sparse, gpz_autocorr_perm_rows and their host-only
  * *_plan queries -- Moran's I and Geary's C (squidpy's spatial_autocorr(mode="geary")) of every gene with its mean, variance and
  * kurtosis, which the randomisation variances of both statistics need, and the permutation entries with the statistic as an
- * argument; scratch `partials`.
+ * argument; scratch `partials`;
+ * gpz_residual_spatial_stats, gpz_residual_spatial_stats_sparse, gpz_residual_autocorr_perm, gpz_residual_autocorr_perm_sparse
+ * and the host-only gpz_residual_autocorr_perm_plan -- Geary's C and the kurtosis beside Moran's I of every gene's residuals,
+ * and either statistic under P relabellings of the spots while the residual slab is resident (the permutation null after
+ * the fit); scratch `partials`.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -542,7 +546,7 @@ int gpz_morans_perm_rows(const float* values, const int64_t* nbr, const int32_t*
                          int32_t perm_batch, int32_t line_mode, double* I, double* sims, int32_t* n_ge, int32_t* n_le,
                          double* sim_mean, double* sim_m2, int32_t* info, void* partials, size_t partials_bytes, void* stream);
 
-/* Moran's I, Geary's C and the moments of every gene (csrc/spatial_stats.hip, csrc/geary_expr.h).  Over the table nbr (N, K) int64
+/* Moran's I, Geary's C and the moments of every gene (csrc/spatial_stats.hip, csrc/moran_expr.h).  Over the table nbr (N, K) int64
  * of distinct neighbours without self edges, with binary weights (both ratios are the same for weights 1 / K):
  *   C = (N - 1) G / ( 2 N K sum_i (x_i - xbar)^2 ),   G = sum_i sum_{j in nbr(i)} (x_i - x_j)^2,
  * 1 in expectation, below 1 for positive autocorrelation.  Outputs, fp64, one value per gene / column; each of the five may be
@@ -649,6 +653,64 @@ int gpz_residual_morans_i_sparse(const float* mean, const float* scale, const fl
                                  int32_t Lt, int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean, int64_t slab_genes,
                                  double* I, double* res_mean, double* res_var, int32_t* info, void* partials,
                                  size_t partials_bytes, void* stream);
+
+/* Geary's C and the permutation null of the residuals (csrc/residual.hip; the column passes of csrc/spatial_stats.hip).  The
+ * model arguments, the counts, genes, nbr, slab_genes and the slabs are those of gpz_residual_morans_i[_sparse]; the sparse
+ * forms fill the slab exactly as there.
+ *   gpz_residual_spatial_stats*   per listed gene, fp64 (G,): I, res_mean and res_var with gpz_residual_morans_i's bits; C,
+ *                                 Geary's C of the residuals, (B - 1) sum_n sum_k (z_n - z_nbr[n,k])^2 / (2 B K sum_n z_n^2);
+ *                                 kurtosis = m4 / m2^2 of the residuals, what the randomisation variances depend on.
+ *   gpz_residual_autocorr_perm*   stat 0 Moran's I, 1 Geary's C.  value (G,): the observed statistic, the stats entry's bits.
+ *                                 perms int32 (P, B): row p relabels the spots, r^pi[n] = r[pi[n]]; the slab is scored over
+ *                                 the relabelled table T_pi[pi[i], m] = pi[nbr[i, m]] instead.  Per slab: the residual pass
+ *                                 once, the wide column pass once, then every batch of perm_batch permutations (0: the
+ *                                 plan's choice; at most 32), each batch one launch per (256-row chunk, 64-column tile)
+ *                                 that reads a row of the slab once and gathers whole rows of the tile.  n_ge / n_le int32
+ *                                 (G,): the permutations whose statistic is >= / <= the observed one, decided on the fp64
+ *                                 numerators sum z lag / K (Moran) and sum (z_n - z_j)^2 (Geary) -- the denominator is
+ *                                 common; residuals are real-valued, so a mathematical tie may fall either way in the last
+ *                                 bit.  sim_mean, sim_m2 (G,): the mean of the simulated values and the sum of their squared
+ *                                 deviations (Welford, in permutation order).  sims (G, P) fp64, may be NULL.  res_mean,
+ *                                 res_var, kurtosis as above.  A partial sum of a permutation is folded in the order of the
+ *                                 observed statistic's, so an identity row of perms gives `value` bit for bit, and nothing
+ *                                 depends on perm_batch.  A gene with constant residuals has NaN values and counts nothing.
+ * info[0] (device int32): 1 a bad entry of nbr (skipped), 2 a row of perms that is no permutation (the results are then
+ * meaningless; nothing is read out of range).  No floating-point atomics; every sum fp64 in a fixed order.
+ * gpz_residual_autocorr_perm_plan (host-only; any out pointer may be NULL; D = the number of scored genes) reports slab_genes,
+ * n_slabs, perm_batch as resolved (a batch's tables, 4 B K bytes per permutation, stay within 256 MiB), the batches per slab
+ * and partials_bytes: the slab, the factors, 40 bytes per (256-row chunk, slab column), and per permutation of a batch
+ * 4 B (K + 1) bytes of tables plus 8 bytes per (chunk, slab column).  P = 0 asks for the scratch of the stats entries:
+ * no tables and no permutations' partial sums, perm_batch = batches = 0.  Limits as for gpz_residual_morans_i, and P >= 1
+ * for the permutation entries (P >= 0 for the query), stat 0 or 1, 0 <= perm_batch <= 32; refused with -1 and the reason
+ * in gpz_last_error before any launch. */
+int gpz_residual_autocorr_perm_plan(int64_t B, int64_t D, int32_t Lt, int32_t K, int64_t P, int64_t nnz, int64_t slab_genes_wanted,
+                                    int32_t perm_batch_wanted, int64_t* slab_genes, int64_t* n_slabs, int32_t* perm_batch,
+                                    int64_t* batches, int64_t* partials_bytes);
+int gpz_residual_spatial_stats(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                               const float* y, const int32_t* genes, const int64_t* nbr, int64_t B, int64_t D, int64_t G, int32_t Lt,
+                               int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean, int64_t slab_genes, double* I,
+                               double* C, double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials,
+                               size_t partials_bytes, void* stream);
+int gpz_residual_spatial_stats_sparse(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                                      const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                      const int32_t* genes, const int64_t* nbr, int64_t B, int64_t D, int64_t nnz, int64_t G,
+                                      int32_t Lt, int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean, int64_t slab_genes,
+                                      double* I, double* C, double* res_mean, double* res_var, double* kurtosis, int32_t* info,
+                                      void* partials, size_t partials_bytes, void* stream);
+int gpz_residual_autocorr_perm(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                               const float* y, const int32_t* genes, const int64_t* nbr, const int32_t* perms, int64_t B, int64_t D,
+                               int64_t G, int32_t Lt, int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean,
+                               int64_t slab_genes, int64_t P, int32_t stat, int32_t perm_batch, double* value, int32_t* n_ge,
+                               int32_t* n_le, double* sim_mean, double* sim_m2, double* sims, double* res_mean, double* res_var,
+                               double* kurtosis, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+int gpz_residual_autocorr_perm_sparse(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
+                                      const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                      const int32_t* genes, const int64_t* nbr, const int32_t* perms, int64_t B, int64_t D,
+                                      int64_t nnz, int64_t G, int32_t Lt, int32_t K, int32_t family, int32_t kind,
+                                      int32_t lognormal_mean, int64_t slab_genes, int64_t P, int32_t stat, int32_t perm_batch,
+                                      double* value, int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2, double* sims,
+                                      double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials,
+                                      size_t partials_bytes, void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
