@@ -9,8 +9,14 @@ Poisson counts with about DENSITY of the entries non-zero -> ``SparseCounts`` ->
 (log1p of size-normalised counts, centred per gene; the held-out split is centred with the training split's offset) ->
 the same fit through ``gpz_gaussian_fa_sparse`` -> held-out ``score``.  No (genes, spots) array exists on the device.
 
+With ``--residual-autocorr`` the fit is followed by ``model_residual_autocorr`` on the fitted spots: is spatial structure left
+in what the fit did not explain, and in which genes -- the ten genes with the largest z (the smallest for Geary's C), or with
+``--residual-perms P`` those with the smallest permutation p-value, each with its ``fdr_bh`` value.  With
+``--sparse-expression`` it runs from the ``SparseExpression``.
+
     PYTHONPATH=. python examples/rsf_synthetic.py [--spots 20000 --genes 1000 --factors 6 --inducing 500 --steps 300]
                                                   [--sparse-expression 0.05]
+                                                  [--residual-autocorr [--residual-perms 99] [--residual-mode geary]]
 """
 import argparse
 import math
@@ -21,8 +27,8 @@ import torch.nn as nn
 
 from gpzoo.gp import WSVGP
 from gpzoo.kernels import NSF_RBF
-from gpzoo.likelihoods import RSF, SparseCounts
-from gpzoo.utilities import log_normalize, train_batched, train_val_split
+from gpzoo.likelihoods import RSF, SparseCounts, model_residual_autocorr
+from gpzoo.utilities import fdr_bh, log_normalize, train_batched, train_val_split
 
 
 def synthetic_expression(N, D, L, gen):
@@ -60,7 +66,26 @@ def sparse_expression_data(a, gen, dev):
     return tr["X"].to(dev), fit.to(dev), val["X"].to(dev), held.to(dev)
 
 
-def main():
+def report_residual_autocorr(model, X, Y, a):
+    """The ten genes whose residuals are the most autocorrelated over the fitted spots' 6-nearest-neighbour graph."""
+    geary = a.residual_mode == "geary"
+    r = model_residual_autocorr(model, X, Y, mode=a.residual_mode, assumption="randomisation", n_perms=a.residual_perms)
+    stat = r.C if geary else r.I
+    if a.residual_perms is None:
+        p = torch.distributions.Normal(0.0, 1.0).cdf(r.z if geary else -r.z)     # one-sided, positive autocorrelation
+        order, label = torch.argsort(r.z, descending=not geary), "p (normal approximation of z)"
+    else:
+        p = r.pval_less if geary else r.pval_greater
+        order, label = torch.argsort(p, stable=True), f"p ({a.residual_perms} permutations)"
+    q = fdr_bh(p)
+    print(f"residual {'Geary C' if geary else 'Moran I'}: median {float(stat.median()):.4f}, expected {float(r.expected):.4f}; "
+          f"residual variance, median {float(r.residual_var.median()):.3f}")
+    print(f"  gene   {'C' if geary else 'I'}        z       {label}   fdr_bh")
+    for g in order[:10].tolist():
+        print(f"  {g:5d}  {float(stat[g]):7.4f}  {float(r.z[g]):7.2f}  {float(p[g]):.3g}  {float(q[g]):.3g}")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--spots", type=int, default=20000)
     ap.add_argument("--genes", type=int, default=1000)
@@ -72,7 +97,18 @@ def main():
     ap.add_argument("--lr", type=float, default=2e-2, help="Adam's learning rate")
     ap.add_argument("--sparse-expression", type=float, default=None, metavar="DENSITY",
                     help="fit log-normalised synthetic counts of this density, held as their non-zeros (SparseExpression)")
-    a = ap.parse_args()
+    ap.add_argument("--residual-autocorr", action="store_true",
+                    help="after the fit, score the spatial autocorrelation of every gene's residuals over the fitted spots")
+    ap.add_argument("--residual-perms", type=int, default=None, metavar="P", help="add a permutation null of P relabellings")
+    ap.add_argument("--residual-mode", choices=("moran", "geary"), default="moran")
+    a = ap.parse_args(argv)
+    if (a.residual_perms is not None or a.residual_mode != "moran") and not a.residual_autocorr:
+        ap.error("--residual-perms and --residual-mode belong to --residual-autocorr")
+    return a
+
+
+def main():
+    a = parse_args()
     dev = torch.device("cuda")
     gen = torch.Generator().manual_seed(0)
     sd_true = None
@@ -117,6 +153,8 @@ def main():
           % (float(fit_sd.median()), "" if sd_true is None else " (true %.3f)" % float(sd_true.median()),
              int((model.W < 0).sum()), model.W.numel()))
     assert sum(losses[-k:]) < sum(losses[:k]) and float(after.r2) > float(before.r2)
+    if a.residual_autocorr:
+        report_residual_autocorr(model, X, Y, a)
 
 
 if __name__ == "__main__":

@@ -148,6 +148,22 @@ _SIGNATURES = {
     "gpz_residual_autocorr_perm_sparse": (C.c_int, [C.c_void_p] * 12 + [C.c_int64] * 4 + [C.c_int32] * 5 +
                                           [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11 +
                                           [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_residual_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gpz_gaussian_residuals": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2 +
+                               [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_residuals_sparse": (C.c_int, [C.c_void_p] * 11 + [C.c_int64] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 2 +
+                                      [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_residual_stats": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] * 3 + [C.c_int32] * 3 + [C.c_int64] +
+                                    [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_residual_stats_sparse": (C.c_int, [C.c_void_p] * 12 + [C.c_int64] * 4 + [C.c_int32] * 3 + [C.c_int64] +
+                                           [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_residual_perm": (C.c_int, [C.c_void_p] * 9 + [C.c_int64] * 3 + [C.c_int32] * 3 +
+                                   [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11 + [C.c_size_t, C.c_void_p]),
+    "gpz_gaussian_residual_perm_sparse": (C.c_int, [C.c_void_p] * 13 + [C.c_int64] * 4 + [C.c_int32] * 3 +
+                                          [C.c_int64, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11 +
+                                          [C.c_size_t, C.c_void_p]),
     "gpz_nb_nsf_sparse_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6),
     "gpz_nb_nsf_sparse_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),

@@ -15,13 +15,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpzoo_hip.so")
 SOURCES = ["runtime.hip", "kfill.hip", "gemm.hip", "gemmw.hip", "gemmp.hip", "diag128.hip", "coop.hip", "factor.hip", "kgrad.hip", "mmops.hip", "poisson.hip", "svgp.hip", "vnngp.hip", "collective.hip", "spatial.hip", "nmf.hip", "smooth.hip", "kmeans.hip", "gram.hip", "poisson_sparse.hip", "nmf_sparse.hip", "deviance.hip", "nb.hip", "nb_sparse.hip", "nb_deviance.hip", "gaussian.hip", "gaussian_sparse.hip", "gene_rank.hip", "gene_dispersion.hip", "residual.hip", "moran_perm.hip", "spatial_stats.hip"]
-HEADERS = ["common.h", "vec.h", "sparse_rows.h", "gene_rows.h", "moran_expr.h", "nb_passes.h", "moran_pass.h", "gemm.h", "cov.h", "gemmw.h", "gemmp.h", "diag128.h", "factor.h", "kgrad.h", "mmops.h", os.path.join("..", "..", "include", "gpzoo_hip.h")]
+HEADERS = ["common.h", "vec.h", "sparse_rows.h", "gene_rows.h", "moran_expr.h", "nb_passes.h", "moran_pass.h", "residual_gaussian.h", "gemm.h", "cov.h", "gemmw.h", "gemmp.h", "diag128.h", "factor.h", "kgrad.h", "mmops.h", os.path.join("..", "..", "include", "gpzoo_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # per source, after FLAGS: the kNN distances of spatial.hip and smooth.hip, and the k-means distances of kmeans.hip, are
 # sklearn's separately rounded squares and sums (no fma); the closing formulas of gene_rank.hip (differences of large sums) are
 # the same expressions written in numpy, each product and sum rounded on its own -- its kernels wait for memory, so this is free;
 # the terms of gene_dispersion.hip likewise (its oracle is those expressions in numpy); residual.hip writes its fused
-# multiply-adds out, so that one element-wise function gives the same bits in the dense and in the sparse kernel; moran_perm.hip
+# multiply-adds out, so that one element-wise function gives the same bits in the dense and in the sparse kernel (the Gaussian
+# residual pass of residual_gaussian.h, which it includes, relies on the same); moran_perm.hip
 # and spatial_stats.hip instantiate gene_rank.hip's gene pass (moran_expr.h) and have to give its bits; spatial_stats.hip also
 # holds the column pass of Moran's I, whose bits do not depend on what is computed beside it
 SOURCE_FLAGS = {"spatial.hip": ["-ffp-contract=off"], "smooth.hip": ["-ffp-contract=off"], "kmeans.hip": ["-ffp-contract=off"],

@@ -41,6 +41,9 @@
 //   run_wide            gpz_residual_spatial_stats* and gpz_residual_autocorr_perm*: per slab the residual pass once, the wide
 //                       column pass once (Geary's C and the kurtosis beside I), then every batch of permutations over the
 //                       resident slab (moran_pass.h).  The slab is filled exactly as for the Moran entries.
+//   Gaussian family     the Gaussian factor models (gpz_gaussian_residual*): the residual pass of residual_gaussian.h behind
+//                       the same plan and the same driver (residual_slab and launch_factors dispatch on Call::gaussian); these
+//                       entries always take the wide pass.  The count kernels above do not change with it.
 #include "common.h"
 #include "gene_rows.h"
 #include "moran_pass.h"
@@ -274,6 +277,14 @@ static int spot_slices(int64_t B, int64_t cols) {
   return (int)SN;
 }
 
+}  // namespace rsd
+}  // namespace gpz
+
+#include "residual_gaussian.h"
+
+namespace gpz {
+namespace rsd {
+
 template <int KS>
 static int launch_slab(const Args& a, bool sparse, hipStream_t s) {
   const dim3 grid((unsigned)((a.ld + BG - 1) / BG), (unsigned)a.SN), block(256);
@@ -292,7 +303,7 @@ static int launch_slab(const Args& a, bool sparse, hipStream_t s) {
   return 0;
 }
 
-static int residual_slab(const Args& a, bool sparse, hipStream_t s) {
+static int count_slab(const Args& a, bool sparse, hipStream_t s) {
   switch (ksteps(a.Lt)) {
     case 1: return launch_slab<1>(a, sparse, s);
     case 2: return launch_slab<2>(a, sparse, s);
@@ -360,9 +371,23 @@ struct Call {
   int64_t B, D, nnz, G;
   int Lt, fam, kind, lognormal;
   bool sparse;
+  const float *b, *noise_sd;      // the Gaussian family: intercept and noise standard deviation (D,) in place of V and theta,
+  const double* offset;           // and the (D,) offset of expression stored as its non-zeros
+  bool gaussian;                  // set by the Gaussian entries alone: fam and lognormal mean nothing there
 };
 
+static int check_gaussian_call(const char* who, const Call& c, const void* partials) {
+  GPZ_REQUIRE(c.mean && c.scale && c.W && c.b && c.noise_sd && partials, "%s: null pointer", who);
+  GPZ_REQUIRE(c.sparse ? (c.row_ptr != nullptr && c.offset != nullptr) : c.y != nullptr, "%s: null pointer (expression)", who);
+  GPZ_REQUIRE(!c.sparse || c.nnz == 0 || (c.row_spot && c.row_perm && c.col_val), "%s: null pointer (stored entries)", who);
+  GPZ_REQUIRE(c.kind >= 0 && c.kind <= 2, "%s: kind %d unknown (0 Pearson, 1 response, 2 predictive)", who, c.kind);
+  GPZ_REQUIRE(c.genes || c.G == c.D, "%s: %lld genes of %lld without a list", who, (long long)c.G, (long long)c.D);
+  GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "%s: partials must be 16-byte aligned", who);
+  return 0;
+}
+
 static int check_call(const char* who, const Call& c, const void* partials) {
+  if (c.gaussian) return check_gaussian_call(who, c, partials);
   GPZ_REQUIRE(c.mean && c.scale && c.W && c.V && partials, "%s: null pointer", who);
   GPZ_REQUIRE(c.sparse ? c.row_ptr != nullptr : c.y != nullptr, "%s: null pointer (counts)", who);
   GPZ_REQUIRE(!c.sparse || c.nnz == 0 || (c.row_spot && c.row_perm && c.col_val), "%s: null pointer (non-zeros)", who);
@@ -382,7 +407,29 @@ static void fill_args(Args& a, const Call& c, const Plan& p) {
   a.Lt = c.Lt; a.fam = c.fam; a.kind = c.kind; a.lognormal = c.lognormal != 0;
 }
 
-static int launch_factors(const Args& a, hipStream_t s) {
+static GArgs gaussian_args(const Args& a, const Call& c) {
+  GArgs g;
+  g.mean = c.mean; g.W = c.W; g.b = c.b; g.sd = c.noise_sd; g.y = c.y; g.offset = c.offset; g.genes = c.genes;
+  g.rows = a.rows; g.s2 = a.mF; g.out = a.out;
+  g.B = a.B; g.D = a.D; g.g0 = a.g0; g.ng = a.ng; g.ld = a.ld;
+  g.Lt = a.Lt; g.SN = a.SN; g.kind = c.kind;
+  return g;
+}
+
+// the residual pass of one slab, by family
+static int residual_slab(const Args& a, const Call& c, hipStream_t s) {
+  if (c.gaussian) return gs_residual_slab(gaussian_args(a, c), c.sparse, s);
+  return count_slab(a, c.sparse, s);
+}
+
+static int launch_factors(const Args& a, const Call& c, hipStream_t s) {
+  if (c.gaussian) {                             // the means are read where they are; scale^2 for the predictive kind alone
+    if (c.kind != 2) return 0;
+    const int64_t n = (int64_t)a.Lt * a.B;
+    hipLaunchKernelGGL(gs_factors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c.scale, a.mF, n);
+    GPZ_LAUNCH_OK();
+    return 0;
+  }
   const int64_t tot = (int64_t)a.Lt * a.B > a.Bp ? (int64_t)a.Lt * a.B : a.Bp;
   hipLaunchKernelGGL(rs_factors_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a);
   GPZ_LAUNCH_OK();
@@ -400,8 +447,8 @@ static int run_residuals(const char* who, const Call& c, float* out, void* parti
   Args a;
   fill_args(a, c, p);
   a.out = out; a.g0 = 0; a.ng = c.G; a.ld = c.G; a.SN = spot_slices(c.B, c.G);
-  if (int rc = launch_factors(a, s)) return rc;
-  return residual_slab(a, c.sparse, s);
+  if (int rc = launch_factors(a, c, s)) return rc;
+  return residual_slab(a, c, s);
 }
 
 static int run_moran(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, double* I, double* res_mean,
@@ -418,12 +465,12 @@ static int run_moran(const char* who, const Call& c, const int64_t* nbr, int K, 
   Args a;
   fill_args(a, c, p);
   a.out = p.slab; a.SN = p.SN;
-  if (int rc = launch_factors(a, s)) return rc;
+  if (int rc = launch_factors(a, c, s)) return rc;
   for (int64_t sl = 0; sl < p.nslabs; ++sl) {
     a.g0 = sl * p.SG;
     a.ng = c.G - a.g0 < p.SG ? c.G - a.g0 : p.SG;
     a.ld = (a.ng + 63) / 64 * 64;               // the last slab is as wide as its genes, rounded up to a block
-    if (int rc = residual_slab(a, c.sparse, s)) return rc;
+    if (int rc = residual_slab(a, c, s)) return rc;
     if (int rc = moran_slab_run(p.slab, c.B, a.ng, a.ld, nbr, K, I + a.g0, res_mean + a.g0, res_var + a.g0, info, p.moran, s))
       return rc;
   }
@@ -517,12 +564,12 @@ static int run_wide(const char* who, const Call& c, const int64_t* nbr, int K, i
   Args a;
   fill_args(a, c, p);
   a.out = p.slab; a.SN = p.SN;
-  if (int rc = launch_factors(a, s)) return rc;
+  if (int rc = launch_factors(a, c, s)) return rc;
   for (int64_t sl = 0; sl < p.nslabs; ++sl) {
     a.g0 = sl * p.SG;
     a.ng = c.G - a.g0 < p.SG ? c.G - a.g0 : p.SG;
     a.ld = (a.ng + 63) / 64 * 64;
-    if (int rc = residual_slab(a, c.sparse, s)) return rc;
+    if (int rc = residual_slab(a, c, s)) return rc;
     if (int rc = moran_slab_wide_run(p.slab, c.B, a.ng, a.ld, nbr, K, I ? I + a.g0 : nullptr, C ? C + a.g0 : nullptr,
                                      res_mean + a.g0, res_var + a.g0, kurtosis + a.g0, info, w.wide, s))
       return rc;
@@ -687,5 +734,120 @@ extern "C" int gpz_residual_autocorr_perm_sparse(const float* mean, const float*
                     kind, lognormal_mean, true};
   const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
   return rsd::run_perm("gpz_residual_autocorr_perm_sparse", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
+                       partials_bytes, stream);
+}
+
+// ---- the Gaussian factor models ---------------------------------------------------------------------------------------
+// K = 0 (with P = 0): what gpz_gaussian_residuals* need, the factor scratch alone.
+
+extern "C" int gpz_gaussian_residual_plan(int64_t B, int64_t D, int32_t Lt, int32_t K, int64_t P, int64_t nnz,
+                                          int64_t slab_genes_wanted, int32_t perm_batch_wanted, int64_t* slab_genes,
+                                          int64_t* n_slabs, int32_t* spot_slices, int32_t* factors_padded, int32_t* perm_batch,
+                                          int64_t* batches, int64_t* partials_bytes) {
+  const char* who = "gpz_gaussian_residual_plan";
+  if (int rc = rsd::check_shape(who, B, D, D, Lt, nnz, slab_genes_wanted)) return rc;
+  if (K == 0) {
+    GPZ_REQUIRE(P == 0, "%s: P = %lld permutations without a neighbour table (K = 0)", who, (long long)P);
+    const rsd::Plan p = rsd::make_plan(B, D, Lt, 64, nullptr);
+    if (slab_genes) *slab_genes = p.SG;
+    if (n_slabs) *n_slabs = p.nslabs;
+    if (spot_slices) *spot_slices = rsd::spot_slices(B, D);
+    if (factors_padded) *factors_padded = 4 * p.KS;
+    if (perm_batch) *perm_batch = 0;
+    if (batches) *batches = 0;
+    if (partials_bytes) *partials_bytes = (int64_t)p.small;
+    return 0;
+  }
+  if (int rc = rsd::check_table(who, B, K)) return rc;
+  if (P != 0)
+    if (int rc = rsd::check_perm(who, P, 0, perm_batch_wanted)) return rc;
+  const rsd::WidePlan w = rsd::make_wide_plan(B, D, Lt, K, P, slab_genes_wanted, perm_batch_wanted, nullptr);
+  if (slab_genes) *slab_genes = w.base.SG;
+  if (n_slabs) *n_slabs = w.base.nslabs;
+  if (spot_slices) *spot_slices = w.base.SN;
+  if (factors_padded) *factors_padded = 4 * w.base.KS;
+  if (perm_batch) *perm_batch = w.perm_batch;
+  if (batches) *batches = w.batches;
+  if (partials_bytes) *partials_bytes = (int64_t)w.bytes;
+  return 0;
+}
+
+static rsd::Call gaussian_call(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                               const float* y, const double* offset, const int64_t* row_ptr, const int32_t* row_spot,
+                               const int32_t* row_perm, const float* col_val, const int32_t* genes, int64_t B, int64_t D,
+                               int64_t nnz, int64_t G, int32_t Lt, int32_t kind, bool sparse) {
+  return rsd::Call{mean, scale, W, nullptr, nullptr, y, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt,
+                   0, kind, 0, sparse, b, noise_sd, offset, true};
+}
+
+extern "C" int gpz_gaussian_residuals(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                                      const float* y, const int32_t* genes, int64_t B, int64_t D, int64_t G, int32_t Lt,
+                                      int32_t kind, float* out, void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, y, nullptr, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G,
+                                    Lt, kind, false);
+  return rsd::run_residuals("gpz_gaussian_residuals", c, out, partials, partials_bytes, stream);
+}
+
+extern "C" int gpz_gaussian_residuals_sparse(const float* mean, const float* scale, const float* W, const float* b,
+                                             const float* noise_sd, const double* offset, const int64_t* row_ptr,
+                                             const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                             const int32_t* genes, int64_t B, int64_t D, int64_t nnz, int64_t G, int32_t Lt,
+                                             int32_t kind, float* out, void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, nullptr, offset, row_ptr, row_spot, row_perm, col_val, genes, B, D,
+                                    nnz, G, Lt, kind, true);
+  return rsd::run_residuals("gpz_gaussian_residuals_sparse", c, out, partials, partials_bytes, stream);
+}
+
+extern "C" int gpz_gaussian_residual_stats(const float* mean, const float* scale, const float* W, const float* b,
+                                           const float* noise_sd, const float* y, const int32_t* genes, const int64_t* nbr,
+                                           int64_t B, int64_t D, int64_t G, int32_t Lt, int32_t K, int32_t kind, int64_t slab_genes,
+                                           double* I, double* C, double* res_mean, double* res_var, double* kurtosis, int32_t* info,
+                                           void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, y, nullptr, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G,
+                                    Lt, kind, false);
+  return rsd::run_stats("gpz_gaussian_residual_stats", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info, partials,
+                        partials_bytes, stream);
+}
+
+extern "C" int gpz_gaussian_residual_stats_sparse(const float* mean, const float* scale, const float* W, const float* b,
+                                                  const float* noise_sd, const double* offset, const int64_t* row_ptr,
+                                                  const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                                  const int32_t* genes, const int64_t* nbr, int64_t B, int64_t D, int64_t nnz,
+                                                  int64_t G, int32_t Lt, int32_t K, int32_t kind, int64_t slab_genes, double* I,
+                                                  double* C, double* res_mean, double* res_var, double* kurtosis, int32_t* info,
+                                                  void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, nullptr, offset, row_ptr, row_spot, row_perm, col_val, genes, B, D,
+                                    nnz, G, Lt, kind, true);
+  return rsd::run_stats("gpz_gaussian_residual_stats_sparse", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info,
+                        partials, partials_bytes, stream);
+}
+
+extern "C" int gpz_gaussian_residual_perm(const float* mean, const float* scale, const float* W, const float* b,
+                                          const float* noise_sd, const float* y, const int32_t* genes, const int64_t* nbr,
+                                          const int32_t* perms, int64_t B, int64_t D, int64_t G, int32_t Lt, int32_t K, int32_t kind,
+                                          int64_t slab_genes, int64_t P, int32_t stat, int32_t perm_batch, double* value,
+                                          int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2, double* sims,
+                                          double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials,
+                                          size_t partials_bytes, void* stream) {
+  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, y, nullptr, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G,
+                                    Lt, kind, false);
+  const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
+  return rsd::run_perm("gpz_gaussian_residual_perm", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
+                       partials_bytes, stream);
+}
+
+extern "C" int gpz_gaussian_residual_perm_sparse(const float* mean, const float* scale, const float* W, const float* b,
+                                                 const float* noise_sd, const double* offset, const int64_t* row_ptr,
+                                                 const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                                 const int32_t* genes, const int64_t* nbr, const int32_t* perms, int64_t B,
+                                                 int64_t D, int64_t nnz, int64_t G, int32_t Lt, int32_t K, int32_t kind,
+                                                 int64_t slab_genes, int64_t P, int32_t stat, int32_t perm_batch, double* value,
+                                                 int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2, double* sims,
+                                                 double* res_mean, double* res_var, double* kurtosis, int32_t* info,
+                                                 void* partials, size_t partials_bytes, void* stream) {
+  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, nullptr, offset, row_ptr, row_spot, row_perm, col_val, genes, B, D,
+                                    nnz, G, Lt, kind, true);
+  const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
+  return rsd::run_perm("gpz_gaussian_residual_perm_sparse", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
                        partials_bytes, stream);
 }

@@ -914,29 +914,41 @@ def _residual_autocorr_checked(qF_list, W_list, V_pos, y, nbr, null, theta_pos, 
                                seed, return_sims):
     """``residual_autocorr`` behind its refusals: ``null`` is what ``_residual_null_args`` returned for the B scored spots."""
     from . import ops
+    with torch.no_grad():
+        mean, scale, W = _cat_factors(qF_list, W_list)
+        return _autocorr_assembly(
+            lambda: ops.residual_morans_i(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes),
+            lambda: ops.residual_spatial_stats(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes),
+            lambda perms: ops.residual_autocorr_perm(mean, scale, W, V_pos, y, nbr, perms, theta_pos, None, kind, lognormal_mean,
+                                                     stat=mode, return_sims=return_sims, slab_genes=slab_genes),
+            mean.device, nbr, null, mode, assumption, seed)
+
+
+def _autocorr_assembly(narrow, stats, perm, dev, nbr, null, mode, assumption, seed):
+    """What the residual entries' outputs become: the moments of the null, z and the permutation fields, as a
+    ``ResidualAutocorr`` / ``ResidualGeary`` / ``ResidualAutocorrPerm`` / ``ResidualGearyPerm``.  ``narrow()`` is the
+    Moran-only entry (None: the family has none), ``stats()`` the wide entry, ``perm(perms)`` the permutation entry; ``dev`` is
+    where the permutations are drawn.  Shared by the count and the Gaussian residuals."""
     from .utilities import _autocorr_moments, _moran_moments, _perm_fields
     permute, P, perms = null
     B = int(nbr.shape[0])
     with torch.no_grad():
-        mean, scale, W = _cat_factors(qF_list, W_list)
-        if mode == "moran" and assumption == "normality" and not permute:
-            r = ops.residual_morans_i(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes)
+        if narrow is not None and mode == "moran" and assumption == "normality" and not permute:
+            r = narrow()
             expected, variance = _moran_moments(nbr.to(device=r["I"].device, dtype=torch.int64))
             return ResidualAutocorr(I=r["I"], expected=expected, variance=variance, z=(r["I"] - expected) / torch.sqrt(variance),
                                     residual_mean=r["residual_mean"], residual_var=r["residual_var"])
         if permute:
             if perms is None:
-                dev = mean.device
                 g = torch.Generator(device=dev)
                 g.manual_seed(int(seed))
                 perms = torch.empty((P, B), dtype=torch.int32, device=dev)
                 for p in range(P):
                     perms[p] = torch.randperm(B, generator=g, device=dev)
-            r, mom = ops.residual_autocorr_perm(mean, scale, W, V_pos, y, nbr, perms, theta_pos, None, kind, lognormal_mean,
-                                                stat=mode, return_sims=return_sims, slab_genes=slab_genes)
+            r, mom = perm(perms)
             stat = r.value
         else:
-            mom = ops.residual_spatial_stats(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes)
+            mom = stats()
             stat = mom["C" if mode == "geary" else "I"]
         table = nbr.to(device=stat.device, dtype=torch.int64)
         if mode == "moran" and assumption == "normality":
@@ -973,6 +985,9 @@ class _ResidualScores:
             raise ValueError(f'{type(self).__name__}.residual_autocorr: kind must be "pearson" or "deviance", got {kind!r}')
         return _deviance_theta(self, self.sf.W if hasattr(self, "sf") else self.W, family, theta)
 
+    def _residual_data(self, y, what):
+        """A refusal of the data's form that a model makes before anything else (``PNMF``); the entries make the rest."""
+
     def residual_autocorr(self, X, y, idx=None, V=None, *, kind="pearson", family="model", theta=None, n_neighs=6, graph=None,
                           lognormal_mean=True, mode="moran", assumption="normality", n_perms=None, seed=0, perms=None,
                           return_sims=False, **kwargs):
@@ -984,6 +999,7 @@ class _ResidualScores:
         ``return_sims`` as in ``likelihoods.residual_autocorr``: Geary's C, the randomisation moments and the permutation
         null over the B scored spots; at their defaults the call is the one without them."""
         from . import ops
+        self._residual_data(y, "residual_autocorr")
         theta_pos = self._residual_theta(kind, family, theta)
         mask = idx is not None and getattr(idx, "dtype", None) == torch.bool
         B = int(X.shape[0]) if idx is None else int(idx.sum()) if mask else len(idx)      # the scored spots: the rows of X[idx]
@@ -998,6 +1014,7 @@ class _ResidualScores:
                   **kwargs):
         """(len(genes), B) fp32 residuals of the listed genes at ``X`` (or ``X[idx]``): the rows ``residual_autocorr`` scores.
         Arguments as there."""
+        self._residual_data(y, "residuals")
         theta_pos = self._residual_theta(kind, family, theta)
         with torch.no_grad():
             qF, W, Vp, Xb = self._score_parts(X, idx, V, kwargs)
@@ -1021,7 +1038,13 @@ class PoissonFactorization(nn.Module):
 
 
 class PNMF(PoissonFactorization):
-    """Non-spatial Poisson NMF over a GaussianPrior; reference likelihoods.py:56-72."""
+    """Non-spatial Poisson NMF over a GaussianPrior; reference likelihoods.py:56-72.  ``residuals`` is that of the spatial
+    count models and ``likelihoods.model_residual_autocorr(model, X, y, ...)`` scores it as ``NSF.residual_autocorr`` scores
+    an ``NSF``; the factors exist only for the fitted spots, so ``X`` (the coordinates of the fitted spots, or of those of
+    ``idx`` after indexing) is used for the neighbour graph alone."""
+    _residual_theta = _ResidualScores._residual_theta
+    _residual_autocorr = _ResidualScores.residual_autocorr          # reached through model_residual_autocorr
+    residuals = _ResidualScores.residuals
 
     def __init__(self, prior, y, L=10, likelihood="poisson", theta0=10.0):
         super().__init__(prior=prior, y=y, L=L, likelihood=likelihood, theta0=theta0)
@@ -1044,6 +1067,23 @@ class PNMF(PoissonFactorization):
         ll = _expected_loglik(self, [qF], [torch.nn.functional.softplus(self.W)], torch.nn.functional.softplus(V), y, E,
                               with_lgamma, eps)
         return ll, qF, pF
+
+    def _residual_data(self, y, what):
+        if isinstance(y, SparseExpression):
+            raise TypeError(f"PNMF.{what}: a SparseExpression holds real-valued expression (values - offset), not counts; "
+                            "pass the counts, dense or as a whole SparseCounts")
+        if isinstance(y, SparseCounts) and y.base is not y:
+            raise TypeError(f"PNMF.{what}: a view y[:, idx]; pass the whole SparseCounts of the scored spots")
+
+    def _score_parts(self, X, idx, V, kwargs):
+        _known_kwargs("PNMF", kwargs, ())
+        Xb = X if idx is None else X[idx]
+        qF = (self.prior() if idx is None else self.prior.forward_batched(idx))[0]
+        if qF.mean.shape[-1] != Xb.shape[0]:
+            raise ValueError(f"PNMF: the factors exist only for the fitted spots ({qF.mean.shape[-1]} here), so {Xb.shape[0]} "
+                             "coordinates cannot be scored; X is used for the neighbour graph alone")
+        Vp = _deviance_size_factors(self.V, idx, V, Xb.shape[0], type(self).__name__)
+        return [qF], [torch.nn.functional.softplus(self.W)], Vp, Xb
 
 
 class NSF2(PoissonFactorization, _ResidualScores):
@@ -1444,6 +1484,112 @@ def gaussian_score(qF_list, W_list, b, noise_sd, y):
                              r2_per_gene=_explained(sse, null), r2=_explained(sse.sum(), null.sum()))
 
 
+def gaussian_residual_autocorr(qF_list, W_list, b, noise_sd, y, nbr, *, kind="pearson", slab_genes=0, mode="moran",
+                               assumption="normality", n_perms=None, seed=0, perms=None, return_sims=False):
+    """``residual_autocorr`` for the Gaussian factor models (``RSF``, ``FA``): the spatial autocorrelation of every gene's
+    residuals under the predictive mean yhat = b[:, None] + sum_k W_k E_q[F_k] over the neighbour table ``nbr`` (B, K) of the
+    B scored spots.  ``noise_sd`` (D,) positive, inside ``NOISE_SD_RANGE``.  ``y``: dense (D, B) or a whole
+    ``SparseExpression`` (the same bits as on ``y.to_dense()``).  ``kind``: "pearson" (default), (y - yhat) / noise_sd;
+    "response", y - yhat in data units, for plotting; "predictive", (y - yhat) / sqrt(noise_sd^2 + W^2 scale^2), which
+    stays a standardisation at held-out spots, where q(F) is wide.  "deviance" raises ValueError: for a Gaussian the signed
+    square root of the unit deviance is the Pearson residual.  I and C do not change under a per-gene affine map, so
+    "pearson" and "response" give the same I and C up to fp32 rounding and differ in ``residual_mean``, ``residual_var`` and
+    the maps; "predictive" differs spot by spot and gives another I.
+
+    ``mode``, ``assumption``, ``n_perms``, ``seed``, ``perms`` and ``return_sims`` as in ``residual_autocorr``, and the same
+    return types; with all of them at their defaults a ``ResidualAutocorr``.  Neither the (D, B) mean nor the residuals are
+    materialised (``ops.gaussian_residual_stats`` / ``ops.gaussian_residual_autocorr_perm``).  Like the count form, the null
+    ignores the degrees of freedom the fit used: the score ranks genes, it is not a calibrated test."""
+    from . import ops
+    who = "gaussian_residual_autocorr"
+    ops._gaussian_kind(who, kind)
+    ops._gaussian_data(who, y)
+    B = int(nbr.shape[0]) if isinstance(nbr, torch.Tensor) else len(nbr)
+    null = _residual_null_args(who, B, mode, assumption, n_perms, perms)
+    return _gaussian_autocorr_checked(qF_list, W_list, b, noise_sd, y, torch.as_tensor(nbr), null, kind, slab_genes, mode,
+                                      assumption, seed, return_sims)
+
+
+def _gaussian_autocorr_checked(qF_list, W_list, b, noise_sd, y, nbr, null, kind, slab_genes, mode, assumption, seed, return_sims):
+    """``gaussian_residual_autocorr`` behind its refusals (``_residual_autocorr_checked``'s sibling; no Moran-only entry)."""
+    from . import ops
+    with torch.no_grad():
+        mean, scale, W = _cat_factors(qF_list, W_list)
+        return _autocorr_assembly(
+            None,
+            lambda: ops.gaussian_residual_stats(mean, scale, W, b, noise_sd, y, nbr, None, kind, slab_genes),
+            lambda perms: ops.gaussian_residual_autocorr_perm(mean, scale, W, b, noise_sd, y, nbr, perms, None, kind, stat=mode,
+                                                              return_sims=return_sims, slab_genes=slab_genes),
+            mean.device, nbr, null, mode, assumption, seed)
+
+
+def gaussian_residuals(qF_list, W_list, b, noise_sd, y, genes, *, kind="pearson"):
+    """(len(genes), B) fp32 residuals of the listed genes, gene-major like ``y``, under the predictive mean of
+    ``gaussian_residual_autocorr``: one gene's residual map for plotting (``kind="response"`` is in data units).
+    ``genes``: gene indices in any order, repeats allowed."""
+    from . import ops
+    if genes is None:
+        raise ValueError("gaussian_residuals: genes (a list of gene indices) needed; the full (D, B) array is what this avoids")
+    with torch.no_grad():
+        mean, scale, W = _cat_factors(qF_list, W_list)
+        return ops.gaussian_residuals(mean, scale, W, b, noise_sd, y, genes, kind).T.contiguous()
+
+
+def model_residual_autocorr(model, X, y, idx=None, **keywords):
+    """Is spatial structure left in what ``model`` did not explain, and in which genes -- one call for every model of the
+    zoo, so that a non-spatial fit (``FA``, ``PNMF``) stands next to a spatial one (``RSF``, ``NSF``) on the same data.  For
+    the count models with a GP prior it is ``model.residual_autocorr(X, y, idx, ...)``; ``PNMF`` is scored by the same code
+    (keywords as there: ``V``, ``kind``, ``family``, ``theta``, ...); ``RSF`` and ``FA`` by the Gaussian form below
+    (``kind`` "pearson", "response" or "predictive", ``n_neighs``, ``graph``, ``mode``, ``assumption``, ``n_perms``, ``seed``,
+    ``perms``, ``return_sims``, and ``groupsX`` for an ``RSF`` over a multi-group GP).  Returns what ``residual_autocorr``
+    returns.  ``RSF`` takes q(F) from its GP at ``X[idx]``, so held-out spots work; the factors of ``FA`` and ``PNMF`` exist
+    only for the fitted spots, where ``X`` is used for the neighbour graph alone."""
+    fn = getattr(model, "residual_autocorr", None) or getattr(model, "_residual_autocorr", None)
+    if fn is None:
+        raise TypeError(f"model_residual_autocorr: {type(model).__name__} has no residual diagnostic")
+    return fn(X, y, idx, **keywords)
+
+
+class _GaussianResidualScores:
+    """``_residual_autocorr`` (behind ``model_residual_autocorr``) and ``residuals`` of the Gaussian factor models.  A model supplies
+    ``_residual_factors(X, idx, groupsX)`` -> q(F) at the scored spots."""
+
+    def _scored_spots(self, what, X, y, idx, kind):
+        """The refusals that need no device, and the number of scored spots (the rows of ``X[idx]``)."""
+        from . import ops
+        who = f"{type(self).__name__}.{what}"
+        ops._gaussian_kind(who, kind)
+        ops._gaussian_data(who, y)
+        mask = idx is not None and getattr(idx, "dtype", None) == torch.bool
+        return who, int(X.shape[0]) if idx is None else int(idx.sum()) if mask else len(idx)
+
+    def _residual_autocorr(self, X, y, idx=None, *, kind="pearson", n_neighs=6, graph=None, mode="moran", assumption="normality",
+                           n_perms=None, seed=0, perms=None, return_sims=False, groupsX=None):
+        """Is spatial structure left in what the fit did not explain, and in which genes: Moran's I (or Geary's C) of every
+        gene's residuals at ``X`` (or ``X[idx]``) over the scored spots' ``n_neighs``-nearest-neighbour graph
+        (``ops.spatial_knn``), or over ``graph=``, a (B, K) table.  ``y`` (D, B) dense or a whole ``SparseExpression`` of the
+        scored spots.  ``kind`` ("pearson", "response", "predictive"), ``mode``, ``assumption``, ``n_perms``, ``seed``,
+        ``perms`` and ``return_sims`` as in ``likelihoods.gaussian_residual_autocorr``; with all of them at their defaults the
+        result is a ``ResidualAutocorr``.  The residual Moran's I of a non-spatial fit (``FA``) next to a spatial one
+        (``RSF``) on the same data is the comparison the spatial prior is judged by."""
+        from . import ops
+        who, B = self._scored_spots("residual_autocorr", X, y, idx, kind)
+        null = _residual_null_args(who, B, mode, assumption, n_perms, perms)
+        with torch.no_grad():
+            qF = self._residual_factors(X, idx, groupsX)
+            nbr = ops.spatial_knn(X if idx is None else X[idx], int(n_neighs)) if graph is None else torch.as_tensor(graph)
+            return _gaussian_autocorr_checked([qF], [self.W], self.b, _noise_sd(self.noise), y, nbr, null, kind, 0, mode,
+                                              assumption, seed, return_sims)
+
+    def residuals(self, X, y, genes, idx=None, *, kind="pearson", groupsX=None):
+        """(len(genes), B) fp32 residuals of the listed genes at ``X`` (or ``X[idx]``): the rows ``model_residual_autocorr``
+        scores.  Arguments as there."""
+        self._scored_spots("residuals", X, y, idx, kind)
+        with torch.no_grad():
+            qF = self._residual_factors(X, idx, groupsX)
+            return gaussian_residuals([qF], [self.W], self.b, _noise_sd(self.noise), y, genes, kind=kind)
+
+
 def _call_gp(gp, X, groupsX=None):
     """q(F), q(U), p(U) of a GP at X; the multi-group GPs take the group ids as ``MGGP_NSF`` passes them."""
     if groupsX is None:
@@ -1510,7 +1656,7 @@ class _DenseNormal(distributions.Normal):
         return super().log_prob(value)
 
 
-class RSF(nn.Module):
+class RSF(nn.Module, _GaussianResidualScores):
     """Real-valued spatial factorisation: y ~ Normal(b[:, None] + W F, softplus(noise)[:, None]) with a GP prior on the
     rows of F (``gp``: SVGP, WSVGP, VNNGP or, with ``groupsX=``, a multi-group GP) -- the nsf paper's RSF, i.e. MEFISTO.
     ``W`` (D, L) is real (``signed_loadings``: the training loops do not clamp it), ``b`` (D,) the intercept, ``noise`` (D,)
@@ -1557,8 +1703,12 @@ class RSF(nn.Module):
             qF = self._qF(X, idx, kwargs)[0]
             return gaussian_score([qF], [self.W], self.b, _noise_sd(self.noise), y)
 
+    def _residual_factors(self, X, idx, groupsX):
+        """q(F) from the GP at ``X[idx]``, held-out spots included, as in ``score``."""
+        return self._qF(X, idx, {} if groupsX is None else {"groupsX": groupsX})[0]
 
-class FA(nn.Module):
+
+class FA(nn.Module, _GaussianResidualScores):
     """Factor analysis: ``RSF``'s likelihood over a ``GaussianPrior`` (i.i.d. factors per spot), with ``PNMF``'s return
     tuples ``(..., qF, pF)``."""
     signed_loadings = True
@@ -1596,3 +1746,15 @@ class FA(nn.Module):
         with torch.no_grad():
             qF = (self.prior() if idx is None else self.prior.forward_batched(idx))[0]
             return gaussian_score([qF], [self.W], self.b, _noise_sd(self.noise), y)
+
+    def _residual_factors(self, X, idx, groupsX):
+        """The factors exist only for the fitted spots (or those of ``idx``): ``X``, their coordinates, is used for the
+        neighbour graph alone."""
+        if groupsX is not None:
+            raise TypeError("FA: groupsX= has no meaning here: the factors are per spot, not a GP's")
+        qF = (self.prior() if idx is None else self.prior.forward_batched(idx))[0]
+        B = X.shape[0] if idx is None else X[idx].shape[0]
+        if qF.mean.shape[-1] != B:
+            raise ValueError(f"FA: the factors exist only for the fitted spots ({qF.mean.shape[-1]} here), so {B} coordinates "
+                             "cannot be scored; X is used for the neighbour graph alone")
+        return qF

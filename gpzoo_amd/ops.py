@@ -2175,6 +2175,191 @@ def residual_autocorr_perm(mean, scale, W_pos, V_pos, y, nbr, perms, theta_pos=N
     return AutocorrPerm(stat, value, n_ge, n_le, mean_, m2, sims), dict(residual_mean=rmean, residual_var=rvar, kurtosis=kurt)
 
 
+GAUSSIAN_RESIDUAL_KINDS = {"pearson": 0, "response": 1, "predictive": 2}
+
+
+def gaussian_residual_plan(B: int, D: int, Lt: int, K: int = 0, P: int = 0, nnz: int = 0, slab_genes: int = 0,
+                           perm_batch: int = 0) -> dict:
+    """How the Gaussian residual entries cover B spots, D scored genes, K neighbours and P permutations
+    (gpz_gaussian_residual_plan, a host-only query: no device needed): ``slab_genes``, ``n_slabs``, ``perm_batch``,
+    ``batches`` and ``partials_bytes`` as ``residual_autocorr_perm_plan`` gives them, with the residual pass's ``spot_slices``
+    and ``factors_padded``.  ``P=0``: what ``gaussian_residual_stats`` needs; ``K=0`` (with ``P=0``): what
+    ``gaussian_residuals`` needs, the factor scratch alone."""
+    lib = _lib.load()
+    sg, ns, nbat, nb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    sn, fp, pb = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = lib.gpz_gaussian_residual_plan(int(B), int(D), int(Lt), int(K), int(P), int(nnz), int(slab_genes), int(perm_batch),
+                                        C.byref(sg), C.byref(ns), C.byref(sn), C.byref(fp), C.byref(pb), C.byref(nbat), C.byref(nb))
+    if rc != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(slab_genes=sg.value, n_slabs=ns.value, spot_slices=sn.value, factors_padded=fp.value, perm_batch=pb.value,
+                batches=nbat.value, partials_bytes=int(nb.value))
+
+
+def _gaussian_kind(who, kind):
+    """The kinds of the Gaussian residuals; the deviance residual of a Gaussian is its Pearson residual."""
+    if kind == "deviance":
+        raise ValueError(f'{who}: kind="deviance" is kind="pearson" for a Gaussian -- the signed square root of the unit '
+                         'deviance is (y - yhat) / noise_sd; ask for "pearson"')
+    if kind not in GAUSSIAN_RESIDUAL_KINDS:
+        raise ValueError(f'{who}: kind must be "pearson", "response" or "predictive", got {kind!r}')
+    return GAUSSIAN_RESIDUAL_KINDS[kind]
+
+
+def _gaussian_data(who, y):
+    """The refusals of the data's form, which need no device; True for a whole ``SparseExpression``."""
+    from .likelihoods import SparseCounts, SparseExpression, TransposedCounts
+    if isinstance(y, (SparseCounts, TransposedCounts)):
+        raise TypeError(f"{who}: a {type(y).__name__} holds counts; the Gaussian models take real-valued expression, a dense "
+                        "(D, B) tensor or a whole SparseExpression")
+    if isinstance(y, SparseExpression):
+        if y.is_view:
+            raise TypeError(f"{who}: a view y[:, idx]; the whole data set is needed")
+        return True
+    if not isinstance(y, torch.Tensor):
+        raise TypeError(f"{who}: y must be a dense (D, B) tensor or a whole SparseExpression, got {type(y).__name__}")
+    return False
+
+
+def _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind):
+    """Everything the Gaussian residual entries check before any device work, and their arguments in the entries' types."""
+    from .likelihoods import NOISE_SD_RANGE
+    sparse = _gaussian_data(who, y)
+    k = _gaussian_kind(who, kind)
+    if mean.dim() != 2:
+        raise ValueError(f"{who}: mean must be (Lt, B), got shape {tuple(mean.shape)}")
+    Lt, B = mean.shape
+    D = y.shape[0]
+    if tuple(y.shape) != (D, B) or scale.shape != (Lt, B) or W.shape != (D, Lt) or b.shape != (D,) or noise_sd.shape != (D,):
+        raise ValueError(f"{who}: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, W {tuple(W.shape)}, "
+                         f"b {tuple(b.shape)}, noise_sd {tuple(noise_sd.shape)} do not fit together")
+    g = None
+    if genes is not None:
+        g = genes.detach() if isinstance(genes, torch.Tensor) else torch.as_tensor(genes)
+        if g.dim() != 1 or g.numel() < 1 or g.is_floating_point() or g.dtype == torch.bool:
+            raise ValueError(f"{who}: genes must be a non-empty 1-D list of gene indices")
+        if bool(((g < 0) | (g >= D)).any()):
+            raise IndexError(f"{who}: a gene index lies outside [0, {D})")
+    _need_cuda(mean, scale, W, b, noise_sd, None if sparse else y)
+    dev = _same_device(mean, scale, W, b, noise_sd, None if sparse else y)
+    if sparse and y.device != dev:
+        raise RuntimeError(f"gpzoo_amd: the expression lives on {y.device}, the model on {dev}: move it with expr.to(device)")
+    f32 = torch.float32
+    mean, scale, W, b, noise_sd = (t.detach().to(f32).contiguous() for t in (mean, scale, W, b, noise_sd))
+    lo, hi = NOISE_SD_RANGE
+    if not bool(((noise_sd >= lo) & (noise_sd <= hi)).all()):
+        raise ValueError(f"{who}: noise_sd must lie in [{lo:g}, {hi:g}] (likelihoods.NOISE_SD_RANGE), positive and finite")
+    if not sparse:
+        y = y.detach().to(f32).contiguous()
+    if g is not None:
+        g = g.to(device=dev, dtype=torch.int32).contiguous()
+    G = D if g is None else int(g.numel())
+    return dict(mean=mean, scale=scale, W=W, b=b, noise_sd=noise_sd, y=y, genes=g, sparse=sparse, dev=dev, B=B, D=D, G=G, Lt=Lt,
+                nnz=y.nnz if sparse else 0, kind=k)
+
+
+def _gaussian_residual_inputs(a):
+    """The leading pointer arguments of the Gaussian residual entries."""
+    head = [_ptr(a[k]) for k in ("mean", "scale", "W", "b", "noise_sd")]
+    y = a["y"]
+    if a["sparse"]:
+        v = y.values
+        return head + [_ptr(y.offset), _ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val), _ptr(a["genes"])]
+    return head + [_ptr(y), _ptr(a["genes"])]
+
+
+def _gaussian_extents(a):
+    return [a["B"], a["D"], a["nnz"], a["G"]] if a["sparse"] else [a["B"], a["D"], a["G"]]
+
+
+def gaussian_residuals(mean, scale, W, b, noise_sd, y, genes=None, kind="pearson"):
+    """(B, G) fp32 residuals, spot-major, of real-valued expression under the Gaussian factor models' predictive mean
+    yhat = b[:, None] + W mean (gpz_gaussian_residuals / gpz_gaussian_residuals_sparse).  ``kind="pearson"``:
+    (y - yhat) / noise_sd; ``"response"``: y - yhat, in data units; ``"predictive"``: (y - yhat) / sqrt(v) with
+    v = noise_sd^2 + W^2 scale^2, the standardisation that stays right where q(F) is wide.  ``"deviance"`` raises ValueError:
+    for a Gaussian it is the Pearson residual.  ``genes`` as in ``count_residuals``.  ``y``: dense (D, B), or a whole
+    ``SparseExpression`` (the same bits as on ``y.to_dense()``)."""
+    who = "gaussian_residuals"
+    a = _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind)
+    lib = _lib.load()
+    nb = gaussian_residual_plan(a["B"], a["G"], a["Lt"], 0, 0, a["nnz"])["partials_bytes"]
+    out = torch.empty((a["B"], a["G"]), dtype=torch.float32, device=a["dev"])
+    entry = lib.gpz_gaussian_residuals_sparse if a["sparse"] else lib.gpz_gaussian_residuals
+    with torch.cuda.device(a["dev"]):
+        ws = _workspace(a["dev"], nb)
+        rc = entry(*_gaussian_residual_inputs(a), *_gaussian_extents(a), a["Lt"], a["kind"], _ptr(out), _ptr(ws), ws.numel(),
+                   _stream(a["dev"]))
+    _lib.check(rc, "gpz_gaussian_residuals")
+    return out
+
+
+def gaussian_residual_stats(mean, scale, W, b, noise_sd, y, nbr, genes=None, kind="pearson", slab_genes: int = 0) -> dict:
+    """Moran's I, Geary's C and the moments of every gene's Gaussian residuals (``gaussian_residuals``' arguments) over the
+    neighbour table nbr (B, K) (gpz_gaussian_residual_stats / gpz_gaussian_residual_stats_sparse): a dict of fp64 (G,) tensors
+    ``I``, ``C``, ``residual_mean``, ``residual_var`` and ``kurtosis``, as ``residual_spatial_stats`` returns them.  I and C
+    do not change under a per-gene affine map, so "pearson" and "response" give the same I and C up to fp32 rounding and
+    differ in the moments; "predictive" differs spot by spot.  Neither the (D, B) mean nor the residuals exist: the genes are
+    taken in slabs of ``slab_genes`` columns.  A bad table raises ValueError (checked on the device; one synchronisation)."""
+    who = "gaussian_residual_stats"
+    K = _residual_table(who, nbr, mean, slab_genes)
+    a = _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind)
+    lib = _lib.load()
+    dev, G = a["dev"], a["G"]
+    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
+    nb = gaussian_residual_plan(a["B"], G, a["Lt"], K, 0, a["nnz"], int(slab_genes))["partials_bytes"]
+    out = [torch.empty(G, dtype=torch.float64, device=dev) for _ in range(5)]
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    name = "gpz_gaussian_residual_stats_sparse" if a["sparse"] else "gpz_gaussian_residual_stats"
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nb)
+        rc = getattr(lib, name)(*_gaussian_residual_inputs(a), _ptr(nbr), *_gaussian_extents(a), a["Lt"], K, a["kind"],
+                                int(slab_genes), *(_ptr(t) for t in out), _ptr(info), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, name)
+    if int(info.item()) != 0:
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
+    return dict(I=out[0], C=out[1], residual_mean=out[2], residual_var=out[3], kurtosis=out[4])
+
+
+def gaussian_residual_autocorr_perm(mean, scale, W, b, noise_sd, y, nbr, perms, genes=None, kind="pearson", *, stat: str = "moran",
+                                    return_sims: bool = False, perm_batch: int = 0, slab_genes: int = 0):
+    """``residual_autocorr_perm`` for the Gaussian residuals (gpz_gaussian_residual_perm / gpz_gaussian_residual_perm_sparse):
+    the observed I or C of every gene's residuals and of their P relabellings ``perms`` (P, B), scored while each residual
+    slab is resident.  Returns (``AutocorrPerm``, moments) as there; ``value`` is ``gaussian_residual_stats``' I or C, bit for
+    bit, and nothing depends on ``perm_batch``."""
+    who = "gaussian_residual_autocorr_perm"
+    st = _stat(who, stat)
+    K = _residual_table(who, nbr, mean, slab_genes)
+    B = int(nbr.shape[0])
+    _perm_table_check(who, perms, B, perm_batch)
+    if perm_batch > 32:
+        raise ValueError(f"{who}: perm_batch = {perm_batch} unsupported (0 = chosen by the plan, at most 32)")
+    a = _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind)
+    lib = _lib.load()
+    dev, G = a["dev"], a["G"]
+    nbr, _ = _nbr_table(who, nbr, B, dev)
+    perms = _perm_table(perms, B, dev)
+    P = int(perms.shape[0])
+    plan = gaussian_residual_plan(B, G, a["Lt"], K, P, a["nnz"], int(slab_genes), perm_batch)
+    value, mean_, m2, rmean, rvar, kurt = (torch.empty(G, dtype=torch.float64, device=dev) for _ in range(6))
+    n_ge, n_le = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
+    sims = torch.empty((G, P), dtype=torch.float64, device=dev) if return_sims else None
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    name = "gpz_gaussian_residual_perm_sparse" if a["sparse"] else "gpz_gaussian_residual_perm"
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, plan["partials_bytes"])
+        rc = getattr(lib, name)(*_gaussian_residual_inputs(a), _ptr(nbr), _ptr(perms), *_gaussian_extents(a), a["Lt"], K, a["kind"],
+                                int(slab_genes), P, st, plan["perm_batch"], _ptr(value), _ptr(n_ge), _ptr(n_le), _ptr(mean_),
+                                _ptr(m2), _ptr(sims), _ptr(rmean), _ptr(rvar), _ptr(kurt), _ptr(info), _ptr(ws), ws.numel(),
+                                _stream(dev))
+    _lib.check(rc, name)
+    code = int(info.item())
+    if code == 1:
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
+    if code != 0:
+        raise ValueError(f"{who}: a row of perms is not a permutation of 0 .. B - 1 (an entry outside [0, B) or an index named twice)")
+    return AutocorrPerm(stat, value, n_ge, n_le, mean_, m2, sims), dict(residual_mean=rmean, residual_var=rvar, kurtosis=kurt)
+
+
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
     """How ``poisson_nsf_sparse`` covers a shape (gpz_poisson_nsf_sparse_plan, a host-only query: no device needed):
     ``gene_chunk`` (non-zeros of a gene row per wave of the gene pass), ``spot_chunk`` (the same for a spot's column; 0:

@@ -80,7 +80,10 @@
  * gpz_residual_spatial_stats, gpz_residual_spatial_stats_sparse, gpz_residual_autocorr_perm, gpz_residual_autocorr_perm_sparse
  * and the host-only gpz_residual_autocorr_perm_plan -- Geary's C and the kurtosis beside Moran's I of every gene's residuals,
  * and either statistic under P relabellings of the spots while the residual slab is resident (the permutation null after
- * the fit); scratch `partials`.
+ * the fit); scratch `partials`;
+ * gpz_gaussian_residuals, gpz_gaussian_residual_stats, gpz_gaussian_residual_perm, their *_sparse forms and the host-only
+ * gpz_gaussian_residual_plan -- the same residual diagnostics for the Gaussian factor models (RSF, FA): Pearson, response or
+ * predictive residuals of real-valued expression, dense or stored as its non-zeros minus a per-gene offset; scratch `partials`.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -711,6 +714,59 @@ int gpz_residual_autocorr_perm_sparse(const float* mean, const float* scale, con
                                       double* value, int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2, double* sims,
                                       double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials,
                                       size_t partials_bytes, void* stream);
+
+/* Residuals of real-valued expression under a fitted Gaussian factor model, and the spatial autocorrelation of every gene's
+ * residuals (csrc/residual.hip with csrc/residual_gaussian.h: the plan, the slabs and the driver of the count entries above).
+ * mean, scale (Lt, B) are q(F); W (D, Lt) real; b (D,) the intercept; noise_sd (D,) positive.  With
+ *   yhat[d,n] = b[d] + sum_l W[d,l] mean[l,n]   and   v[d,n] = noise_sd[d]^2 + sum_l W[d,l]^2 scale[l,n]^2
+ * kind 0 is the Pearson residual (y - yhat) / noise_sd[d] (for a Gaussian also the deviance residual), kind 1 the response
+ * residual y - yhat, kind 2 the predictive residual (y - yhat) / sqrt(v).  I and C do not change under a per-gene affine map,
+ * so kinds 0 and 1 give the same I and C up to fp32 rounding; kind 2 differs spot by spot.  y (D, B) fp32 dense; the sparse
+ * forms take the stored entries of the WHOLE data set in the by-gene order of gpz_poisson_nsf_sparse (N = B) and the fp64
+ * offset (D,): y[d,n] = (float)((double)value - offset[d]), (float)(-offset[d]) where nothing is stored, and give the dense
+ * entry's bits on that array.  genes, nbr, slab_genes, the outputs, perms, stat, perm_batch and info are those of
+ * gpz_count_residuals, gpz_residual_spatial_stats and gpz_residual_autocorr_perm; the Gaussian entries always take the wide
+ * column pass.  No floating-point atomics, every sum fp64 in a fixed order: two calls agree bit for bit.
+ * gpz_gaussian_residual_plan (host-only; any out pointer may be NULL; D = the number of scored genes) reports what
+ * gpz_residual_autocorr_perm_plan reports, with the residual pass's spot_slices and factors_padded; K = 0 (with P = 0) asks
+ * for the scratch of gpz_gaussian_residuals[_sparse], the factors alone.  Limits: 1 <= Lt <= 64, 1 <= K <= 32 < B,
+ * B, D, G, nnz < 2^31, B < 2^27 with stored entries, kind 0..2; refused with -1 and the reason in gpz_last_error before any
+ * launch.  noise_sd is trusted to be positive and finite. */
+int gpz_gaussian_residual_plan(int64_t B, int64_t D, int32_t Lt, int32_t K, int64_t P, int64_t nnz, int64_t slab_genes_wanted,
+                               int32_t perm_batch_wanted, int64_t* slab_genes, int64_t* n_slabs, int32_t* spot_slices,
+                               int32_t* factors_padded, int32_t* perm_batch, int64_t* batches, int64_t* partials_bytes);
+int gpz_gaussian_residuals(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                           const float* y, const int32_t* genes, int64_t B, int64_t D, int64_t G, int32_t Lt, int32_t kind,
+                           float* out, void* partials, size_t partials_bytes, void* stream);
+int gpz_gaussian_residuals_sparse(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                                  const double* offset, const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
+                                  const float* col_val, const int32_t* genes, int64_t B, int64_t D, int64_t nnz, int64_t G,
+                                  int32_t Lt, int32_t kind, float* out, void* partials, size_t partials_bytes, void* stream);
+int gpz_gaussian_residual_stats(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                                const float* y, const int32_t* genes, const int64_t* nbr, int64_t B, int64_t D, int64_t G,
+                                int32_t Lt, int32_t K, int32_t kind, int64_t slab_genes, double* I, double* C, double* res_mean,
+                                double* res_var, double* kurtosis, int32_t* info, void* partials, size_t partials_bytes,
+                                void* stream);
+int gpz_gaussian_residual_stats_sparse(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                                       const double* offset, const int64_t* row_ptr, const int32_t* row_spot,
+                                       const int32_t* row_perm, const float* col_val, const int32_t* genes, const int64_t* nbr,
+                                       int64_t B, int64_t D, int64_t nnz, int64_t G, int32_t Lt, int32_t K, int32_t kind,
+                                       int64_t slab_genes, double* I, double* C, double* res_mean, double* res_var,
+                                       double* kurtosis, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+int gpz_gaussian_residual_perm(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                               const float* y, const int32_t* genes, const int64_t* nbr, const int32_t* perms, int64_t B, int64_t D,
+                               int64_t G, int32_t Lt, int32_t K, int32_t kind, int64_t slab_genes, int64_t P, int32_t stat,
+                               int32_t perm_batch, double* value, int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2,
+                               double* sims, double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials,
+                               size_t partials_bytes, void* stream);
+int gpz_gaussian_residual_perm_sparse(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                                      const double* offset, const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm,
+                                      const float* col_val, const int32_t* genes, const int64_t* nbr, const int32_t* perms,
+                                      int64_t B, int64_t D, int64_t nnz, int64_t G, int32_t Lt, int32_t K, int32_t kind,
+                                      int64_t slab_genes, int64_t P, int32_t stat, int32_t perm_batch, double* value, int32_t* n_ge,
+                                      int32_t* n_le, double* sim_mean, double* sim_m2, double* sims, double* res_mean,
+                                      double* res_var, double* kurtosis, int32_t* info, void* partials, size_t partials_bytes,
+                                      void* stream);
 
 /* gpz_poisson_nsf for counts stored as their non-zeros (csrc/poisson_sparse.hip).  The sum of the rates factorises
  * (sum_{d,n} rate = sum_n V[n] sum_l c[l] expF[e,l,n], c[l] = sum_d W[d,l]) and y log(rate) is non-zero only where y is, so
