@@ -36,17 +36,28 @@
 //                       and the gene's W in every column, so a stored entry gets the bits of the dense entry's rate; the
 //                       residual overwrites the slab's element.  The factors are gathered from the (Lt, B) array of the
 //                       dense pass; a transposed copy for this gather measured no faster.
-//   driver              per slab: the residual pass, then moran_slab_run.  No atomics, no workgroup waits on another, every
-//                       sum (all of them in the Moran pass) fp64 in a fixed order: two calls agree bit for bit.
-//   run_wide            gpz_residual_spatial_stats* and gpz_residual_autocorr_perm*: per slab the residual pass once, the wide
-//                       column pass once (Geary's C and the kurtosis beside I), then every batch of permutations over the
-//                       resident slab (moran_pass.h).  The slab is filled exactly as for the Moran entries.
+//   for_ksteps          the one list of the k-step instances; launch_slab, the one launcher of a slab's residual pass (the
+//                       tile kernel, or its ZERO instance and then the stored kernel), takes the kernels of either family.
+//   run_slabs           the driver of every entry over a neighbour table: the checks (check_shape, check_call, check_table),
+//                       make_plan (the one carve of the scratch, narrow or wide), the factors, then per slab the residual pass
+//                       and the statistic its caller passes in.  No atomics, no workgroup waits on another, every sum (all of
+//                       them in the Moran pass) fp64 in a fixed order: two calls agree bit for bit.
+//   run_moran           gpz_residual_morans_i*: run_slabs with moran_slab_run over the narrow layout.
+//   run_wide            gpz_residual_spatial_stats* and gpz_residual_autocorr_perm* (run_stats, run_perm): run_slabs over the
+//                       wide layout with the wide column pass once (Geary's C and the kurtosis beside I), then every batch of
+//                       permutations over the resident slab (moran_pass.h).  The slab is filled exactly as for the Moran
+//                       entries.
 //   Gaussian family     the Gaussian factor models (gpz_gaussian_residual*): the residual pass of residual_gaussian.h behind
 //                       the same plan and the same driver (residual_slab and launch_factors dispatch on Call::gaussian); these
 //                       entries always take the wide pass.  The count kernels above do not change with it.
+//   entries             each builds its Call (count_call or gaussian_call, .stored(...) for data held as its non-zeros) and, for
+//                       the permutation entries, its PermCall, and calls run_residuals, run_moran, run_stats or run_perm.
 #include "common.h"
 #include "gene_rows.h"
 #include "moran_pass.h"
+
+#include <type_traits>
+#include <utility>
 
 namespace gpz {
 namespace rsd {
@@ -109,8 +120,9 @@ struct Args {
   int Lt, SN, fam, kind, lognormal;
 };
 
-// the gene behind column col of the slab, -1 for a column beyond its genes (or a listed index outside [0, D))
-__device__ __forceinline__ int64_t gene_of(const Args& a, int64_t col) {
+// the gene behind column col of the slab, -1 for a column beyond its genes (or a listed index outside [0, D)); A: Args or GArgs
+template <class A>
+__device__ __forceinline__ int64_t gene_of(const A& a, int64_t col) {
   if (col >= a.ng) return -1;
   const int64_t g = a.genes ? (int64_t)a.genes[a.g0 + col] : a.g0 + col;
   return g >= 0 && g < a.D ? g : -1;
@@ -267,6 +279,19 @@ static int ksteps(int Lt) {                     // the instances of dv_tile_kern
   return k <= 10 ? k : k <= 12 ? 12 : k <= 14 ? 14 : 16;
 }
 
+// f(std::integral_constant<int, KS>) for the instance that serves Lt factors: the one place the instances are listed
+template <class F, int... KS>
+static int for_ksteps(int ks, F&& f, std::integer_sequence<int, KS...>) {
+  int rc = -1;
+  (void)((ks == KS && ((rc = f(std::integral_constant<int, KS>{})), true)) || ...);
+  return rc;
+}
+
+template <class F>
+static int for_ksteps(int Lt, F&& f) {
+  return for_ksteps(ksteps(Lt), f, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16>{});
+}
+
 static int spot_slices(int64_t B, int64_t cols) {
   // enough (gene block, spot slice) workgroups to fill the device a few times over, slices of at least 8 tiles
   const int64_t GB = (cols + BG - 1) / BG;
@@ -277,6 +302,21 @@ static int spot_slices(int64_t B, int64_t cols) {
   return (int)SN;
 }
 
+// The residual pass of one slab, for either family (A: Args or GArgs): the tile kernel over dense data; over stored data its
+// ZERO instance and then, where anything is stored, the stored kernel over the slab's gene rows.
+template <class A>
+static int launch_slab(void (*tile)(A), void (*zero)(A), void (*stored)(A), const A& a, bool sparse, hipStream_t s) {
+  const dim3 grid((unsigned)((a.ld + BG - 1) / BG), (unsigned)a.SN), block(256);
+  hipLaunchKernelGGL(sparse ? zero : tile, grid, block, 0, s, a);
+  GPZ_LAUNCH_OK();
+  if (sparse && a.rows.nnz > 0) {
+    const int64_t chunks = (a.B + CHUNK - 1) / CHUNK;             // a gene row holds at most B entries
+    hipLaunchKernelGGL(stored, dim3((unsigned)a.ng, (unsigned)((chunks + 3) / 4)), block, 0, s, a);
+    GPZ_LAUNCH_OK();
+  }
+  return 0;
+}
+
 }  // namespace rsd
 }  // namespace gpz
 
@@ -285,53 +325,34 @@ static int spot_slices(int64_t B, int64_t cols) {
 namespace gpz {
 namespace rsd {
 
-template <int KS>
-static int launch_slab(const Args& a, bool sparse, hipStream_t s) {
-  const dim3 grid((unsigned)((a.ld + BG - 1) / BG), (unsigned)a.SN), block(256);
-  if (!sparse) {
-    hipLaunchKernelGGL((rs_tile_kernel<KS, false>), grid, block, 0, s, a);
-    GPZ_LAUNCH_OK();
-    return 0;
-  }
-  hipLaunchKernelGGL((rs_tile_kernel<KS, true>), grid, block, 0, s, a);
-  GPZ_LAUNCH_OK();
-  if (a.rows.nnz > 0) {
-    const int64_t chunks = (a.B + CHUNK - 1) / CHUNK;             // a gene row holds at most B entries
-    hipLaunchKernelGGL((rs_stored_kernel<KS>), dim3((unsigned)a.ng, (unsigned)((chunks + 3) / 4)), block, 0, s, a);
-    GPZ_LAUNCH_OK();
-  }
-  return 0;
-}
-
 static int count_slab(const Args& a, bool sparse, hipStream_t s) {
-  switch (ksteps(a.Lt)) {
-    case 1: return launch_slab<1>(a, sparse, s);
-    case 2: return launch_slab<2>(a, sparse, s);
-    case 3: return launch_slab<3>(a, sparse, s);
-    case 4: return launch_slab<4>(a, sparse, s);
-    case 5: return launch_slab<5>(a, sparse, s);
-    case 6: return launch_slab<6>(a, sparse, s);
-    case 7: return launch_slab<7>(a, sparse, s);
-    case 8: return launch_slab<8>(a, sparse, s);
-    case 9: return launch_slab<9>(a, sparse, s);
-    case 10: return launch_slab<10>(a, sparse, s);
-    case 12: return launch_slab<12>(a, sparse, s);
-    case 14: return launch_slab<14>(a, sparse, s);
-    default: return launch_slab<16>(a, sparse, s);
-  }
+  return for_ksteps(a.Lt, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    return launch_slab(rs_tile_kernel<KS, false>, rs_tile_kernel<KS, true>, rs_stored_kernel<KS>, a, sparse, s);
+  });
 }
 
+constexpr int PERM_BATCH_DEFAULT = 16;          // the plan's choice where 16 tables fit; DESIGN.md section 5 says what it rests on
+constexpr int64_t TABLE_BYTES = 256ll << 20;    // the tables of a batch stay within what the slab is held to
+
+// The slabs and the scratch.  Both layouts open with the factors and the slab; the narrow one (the Moran entries) closes with
+// the Moran pass's partial sums: mF, Vw, [small], slab, moran.  The wide one (the entries that need more than I) closes with
+// the wide column pass's partial sums and, for the permutation entries, the batch's relabelled tables and partial sums
+// (moran_pass.h): mF, Vw, slab, wide, perm.
 struct Plan {
   int64_t SG, nslabs, Bp;
   int SN, KS;
   float *mF, *Vw, *slab;
-  void* moran;
-  size_t small, bytes;            // what the residual entries need; what the Moran entries need
+  void *moran, *wide, *perm;      // narrow: moran; wide: wide, and perm with permutations
+  int perm_batch;                 // 0: no permutations
+  int64_t batches;
+  size_t small, bytes;            // what the residual entries need; what the layout needs
 };
 
-// G: the scored genes; slab_in: the caller's slab_genes (0: the largest multiple of 64 within SLAB_BYTES)
-static Plan make_plan(int64_t B, int64_t G, int Lt, int64_t slab_in, void* ws) {
-  Plan p;
+// G: the scored genes; slab_in: the caller's slab_genes (0: the largest multiple of 64 within SLAB_BYTES).  Narrow without K;
+// with K neighbours wide, for P permutations (0: the statistics alone) in batches of perm_in (0: the plan's choice)
+static Plan make_plan(int64_t B, int64_t G, int Lt, int64_t slab_in, void* ws, int K = 0, int64_t P = 0, int perm_in = 0) {
+  Plan p{};
   const int64_t G64 = (G + 63) / 64 * 64;
   p.SG = slab_in > 0 ? slab_in : SLAB_BYTES / (B * 4) / 64 * 64;
   if (p.SG > SLAB_MAX) p.SG = SLAB_MAX;
@@ -346,7 +367,19 @@ static Plan make_plan(int64_t B, int64_t G, int Lt, int64_t slab_in, void* ws) {
   p.Vw = c.take<float>((size_t)p.Bp);
   p.small = c.used();
   p.slab = c.take<float>((size_t)B * p.SG);
-  p.moran = c.take<char>(moran_slab_bytes(B, p.SG));
+  if (K == 0) p.moran = c.take<char>(moran_slab_bytes(B, p.SG));
+  else p.wide = c.take<char>(moran_slab_wide_bytes(B, p.SG));
+  if (P > 0) {
+    int64_t pb = perm_in;
+    if (pb == 0) {
+      const int64_t fit = TABLE_BYTES / (4 * B * K);
+      pb = fit < 1 ? 1 : (fit > PERM_BATCH_DEFAULT ? PERM_BATCH_DEFAULT : fit);
+    }
+    if (pb > P) pb = P;
+    p.perm_batch = (int)pb;
+    p.batches = (P + pb - 1) / pb;
+    p.perm = c.take<char>(moran_slab_perm_bytes(B, p.SG, K, p.perm_batch));
+  }
   p.bytes = c.used();
   return p;
 }
@@ -374,26 +407,42 @@ struct Call {
   const float *b, *noise_sd;      // the Gaussian family: intercept and noise standard deviation (D,) in place of V and theta,
   const double* offset;           // and the (D,) offset of expression stored as its non-zeros
   bool gaussian;                  // set by the Gaussian entries alone: fam and lognormal mean nothing there
+
+  // the same call over data stored as its non-zeros (the sparse entries pass no y)
+  Call stored(const int64_t* rp, const int32_t* rs, const int32_t* rm, const float* cv, int64_t n, const double* off = nullptr) const {
+    Call c = *this;
+    c.row_ptr = rp; c.row_spot = rs; c.row_perm = rm; c.col_val = cv; c.nnz = n; c.offset = off; c.sparse = true;
+    return c;
+  }
 };
 
-static int check_gaussian_call(const char* who, const Call& c, const void* partials) {
-  GPZ_REQUIRE(c.mean && c.scale && c.W && c.b && c.noise_sd && partials, "%s: null pointer", who);
-  GPZ_REQUIRE(c.sparse ? (c.row_ptr != nullptr && c.offset != nullptr) : c.y != nullptr, "%s: null pointer (expression)", who);
-  GPZ_REQUIRE(!c.sparse || c.nnz == 0 || (c.row_spot && c.row_perm && c.col_val), "%s: null pointer (stored entries)", who);
-  GPZ_REQUIRE(c.kind >= 0 && c.kind <= 2, "%s: kind %d unknown (0 Pearson, 1 response, 2 predictive)", who, c.kind);
-  GPZ_REQUIRE(c.genes || c.G == c.D, "%s: %lld genes of %lld without a list", who, (long long)c.G, (long long)c.D);
-  GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "%s: partials must be 16-byte aligned", who);
-  return 0;
+// a dense call of the count family, and of the Gaussian family
+static Call count_call(const float* mean, const float* scale, const float* W, const float* V, const float* theta, const float* y,
+                       const int32_t* genes, int64_t B, int64_t D, int64_t G, int Lt, int fam, int kind, int lognormal) {
+  return Call{mean, scale, W, V, theta, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, fam, kind, lognormal, false,
+              nullptr, nullptr, nullptr, false};
+}
+
+static Call gaussian_call(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
+                          const float* y, const int32_t* genes, int64_t B, int64_t D, int64_t G, int Lt, int kind) {
+  return Call{mean, scale, W, nullptr, nullptr, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, 0, kind, 0, false,
+              b, noise_sd, nullptr, true};
 }
 
 static int check_call(const char* who, const Call& c, const void* partials) {
-  if (c.gaussian) return check_gaussian_call(who, c, partials);
-  GPZ_REQUIRE(c.mean && c.scale && c.W && c.V && partials, "%s: null pointer", who);
-  GPZ_REQUIRE(c.sparse ? c.row_ptr != nullptr : c.y != nullptr, "%s: null pointer (counts)", who);
-  GPZ_REQUIRE(!c.sparse || c.nnz == 0 || (c.row_spot && c.row_perm && c.col_val), "%s: null pointer (non-zeros)", who);
-  GPZ_REQUIRE(c.fam == 0 || c.fam == 1, "%s: family %d unknown (0 Poisson, 1 negative binomial)", who, c.fam);
-  GPZ_REQUIRE(c.kind == 0 || c.kind == 1, "%s: kind %d unknown (0 Pearson, 1 deviance)", who, c.kind);
-  GPZ_REQUIRE(c.fam == 0 || c.theta, "%s: the negative binomial family needs theta", who);
+  if (c.gaussian) {
+    GPZ_REQUIRE(c.mean && c.scale && c.W && c.b && c.noise_sd && partials, "%s: null pointer", who);
+    GPZ_REQUIRE(c.sparse ? (c.row_ptr != nullptr && c.offset != nullptr) : c.y != nullptr, "%s: null pointer (expression)", who);
+    GPZ_REQUIRE(!c.sparse || c.nnz == 0 || (c.row_spot && c.row_perm && c.col_val), "%s: null pointer (stored entries)", who);
+    GPZ_REQUIRE(c.kind >= 0 && c.kind <= 2, "%s: kind %d unknown (0 Pearson, 1 response, 2 predictive)", who, c.kind);
+  } else {
+    GPZ_REQUIRE(c.mean && c.scale && c.W && c.V && partials, "%s: null pointer", who);
+    GPZ_REQUIRE(c.sparse ? c.row_ptr != nullptr : c.y != nullptr, "%s: null pointer (counts)", who);
+    GPZ_REQUIRE(!c.sparse || c.nnz == 0 || (c.row_spot && c.row_perm && c.col_val), "%s: null pointer (non-zeros)", who);
+    GPZ_REQUIRE(c.fam == 0 || c.fam == 1, "%s: family %d unknown (0 Poisson, 1 negative binomial)", who, c.fam);
+    GPZ_REQUIRE(c.kind == 0 || c.kind == 1, "%s: kind %d unknown (0 Pearson, 1 deviance)", who, c.kind);
+    GPZ_REQUIRE(c.fam == 0 || c.theta, "%s: the negative binomial family needs theta", who);
+  }
   GPZ_REQUIRE(c.genes || c.G == c.D, "%s: %lld genes of %lld without a list", who, (long long)c.G, (long long)c.D);
   GPZ_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 15) == 0, "%s: partials must be 16-byte aligned", who);
   return 0;
@@ -451,14 +500,23 @@ static int run_residuals(const char* who, const Call& c, float* out, void* parti
   return residual_slab(a, c, s);
 }
 
-static int run_moran(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, double* I, double* res_mean,
-                     double* res_var, int32_t* info, void* partials, size_t partials_bytes, void* stream) {
+static int check_table(const char* who, int64_t B, int K) {
+  GPZ_REQUIRE(K >= 1 && K <= KMAX && B > K, "%s: K = %d neighbours of %lld spots unsupported (1 <= K <= %d, K < B)", who, K,
+              (long long)B, KMAX);
+  return 0;
+}
+
+// The entries over a neighbour table: the checks, the plan (wide: see make_plan; P permutations in batches of perm_batch),
+// the factors, then per slab the residual pass and stat(a, p, s), the statistic of the slab that a describes.  outs: the
+// entry's output pointers are all there.
+template <class Stat>
+static int run_slabs(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, bool wide, int64_t P,
+                     int perm_batch, bool outs, int32_t* info, void* partials, size_t partials_bytes, void* stream, Stat stat) {
   if (int rc = check_shape(who, c.B, c.D, c.G, c.Lt, c.nnz, slab_genes)) return rc;
   if (int rc = check_call(who, c, partials)) return rc;
-  GPZ_REQUIRE(nbr && I && res_mean && res_var && info, "%s: null pointer", who);
-  GPZ_REQUIRE(K >= 1 && K <= KMAX && c.B > K, "%s: K = %d neighbours of %lld spots unsupported (1 <= K <= %d, K < B)", who, K,
-              (long long)c.B, KMAX);
-  const Plan p = make_plan(c.B, c.G, c.Lt, slab_genes, partials);
+  GPZ_REQUIRE(nbr && outs && info, "%s: null pointer", who);
+  if (int rc = check_table(who, c.B, K)) return rc;
+  const Plan p = make_plan(c.B, c.G, c.Lt, slab_genes, partials, wide ? K : 0, P, perm_batch);
   GPZ_REQUIRE(partials_bytes >= p.bytes, "%s: partials too small (%zu bytes, %zu needed)", who, partials_bytes, p.bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
   GPZ_HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t), s));
@@ -471,56 +529,21 @@ static int run_moran(const char* who, const Call& c, const int64_t* nbr, int K, 
     a.ng = c.G - a.g0 < p.SG ? c.G - a.g0 : p.SG;
     a.ld = (a.ng + 63) / 64 * 64;               // the last slab is as wide as its genes, rounded up to a block
     if (int rc = residual_slab(a, c, s)) return rc;
-    if (int rc = moran_slab_run(p.slab, c.B, a.ng, a.ld, nbr, K, I + a.g0, res_mean + a.g0, res_var + a.g0, info, p.moran, s))
-      return rc;
+    if (int rc = stat(a, p, s)) return rc;
   }
   return 0;
+}
+
+static int run_moran(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, double* I, double* res_mean,
+                     double* res_var, int32_t* info, void* partials, size_t partials_bytes, void* stream) {
+  return run_slabs(who, c, nbr, K, slab_genes, false, 0, 0, I && res_mean && res_var, info, partials, partials_bytes, stream,
+                   [&](const Args& a, const Plan& p, hipStream_t s) {
+                     return moran_slab_run(p.slab, c.B, a.ng, a.ld, nbr, K, I + a.g0, res_mean + a.g0, res_var + a.g0, info,
+                                           p.moran, s);
+                   });
 }
 
 // ---- the wide statistics and the permutation null -------------------------------------------------------------------
-// The scratch of the entries that need more than I: the factors and the slab as in make_plan, then the wide column pass's
-// partial sums and, for the permutation entries, the batch's relabelled tables and partial sums (moran_pass.h).
-
-constexpr int PERM_BATCH_DEFAULT = 16;          // the plan's choice where 16 tables fit; DESIGN.md section 5 says what it rests on
-constexpr int64_t TABLE_BYTES = 256ll << 20;    // the tables of a batch stay within what the slab is held to
-
-struct WidePlan {
-  Plan base;                      // SG, nslabs, mF, Vw, slab as the Moran entries lay them out (base.moran is not used)
-  void *wide, *perm;
-  int perm_batch;                 // 0: no permutations
-  int64_t batches;
-  size_t bytes;
-};
-
-// perm_in: the caller's perm_batch (0: the plan's choice); P = 0: the statistics alone
-static WidePlan make_wide_plan(int64_t B, int64_t G, int Lt, int K, int64_t P, int64_t slab_in, int perm_in, void* ws) {
-  WidePlan w{};
-  w.base = make_plan(B, G, Lt, slab_in, nullptr);
-  Carver c(ws);
-  w.base.mF = c.take<float>((size_t)Lt * B);
-  w.base.Vw = c.take<float>((size_t)w.base.Bp);
-  w.base.slab = c.take<float>((size_t)B * w.base.SG);
-  w.wide = c.take<char>(moran_slab_wide_bytes(B, w.base.SG));
-  if (P > 0) {
-    int64_t pb = perm_in;
-    if (pb == 0) {
-      const int64_t fit = TABLE_BYTES / (4 * B * K);
-      pb = fit < 1 ? 1 : (fit > PERM_BATCH_DEFAULT ? PERM_BATCH_DEFAULT : fit);
-    }
-    if (pb > P) pb = P;
-    w.perm_batch = (int)pb;
-    w.batches = (P + pb - 1) / pb;
-    w.perm = c.take<char>(moran_slab_perm_bytes(B, w.base.SG, K, w.perm_batch));
-  }
-  w.bytes = c.used();
-  return w;
-}
-
-static int check_table(const char* who, int64_t B, int K) {
-  GPZ_REQUIRE(K >= 1 && K <= KMAX && B > K, "%s: K = %d neighbours of %lld spots unsupported (1 <= K <= %d, K < B)", who, K,
-              (long long)B, KMAX);
-  return 0;
-}
 
 static int check_perm(const char* who, int64_t P, int stat, int perm_batch) {
   GPZ_REQUIRE(P >= 1 && P < (1ll << 31), "%s: P = %lld permutations unsupported (1 <= P < 2^31)", who, (long long)P);
@@ -546,41 +569,23 @@ static int run_wide(const char* who, const Call& c, const int64_t* nbr, int K, i
                     double* res_mean, double* res_var, double* kurtosis, const PermCall& pc, int32_t* info, void* partials,
                     size_t partials_bytes, void* stream) {
   const bool permute = pc.perms != nullptr;
-  if (int rc = check_shape(who, c.B, c.D, c.G, c.Lt, c.nnz, slab_genes)) return rc;
-  if (int rc = check_call(who, c, partials)) return rc;
-  GPZ_REQUIRE(nbr && (I || C) && (permute || (I && C)) && res_mean && res_var && kurtosis && info, "%s: null pointer", who);
-  if (int rc = check_table(who, c.B, K)) return rc;
-  const WidePlan w = make_wide_plan(c.B, c.G, c.Lt, K, permute ? pc.P : 0, slab_genes, pc.perm_batch, partials);
-  GPZ_REQUIRE(partials_bytes >= w.bytes, "%s: partials too small (%zu bytes, %zu needed)", who, partials_bytes, w.bytes);
-  const Plan& p = w.base;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  GPZ_HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t), s));
-  if (permute) {
-    GPZ_HIP_OK(hipMemsetAsync(pc.n_ge, 0, size_t(c.G) * sizeof(int32_t), s));
-    GPZ_HIP_OK(hipMemsetAsync(pc.n_le, 0, size_t(c.G) * sizeof(int32_t), s));
-    GPZ_HIP_OK(hipMemsetAsync(pc.sim_mean, 0, size_t(c.G) * sizeof(double), s));
-    GPZ_HIP_OK(hipMemsetAsync(pc.sim_m2, 0, size_t(c.G) * sizeof(double), s));
-  }
-  Args a;
-  fill_args(a, c, p);
-  a.out = p.slab; a.SN = p.SN;
-  if (int rc = launch_factors(a, c, s)) return rc;
-  for (int64_t sl = 0; sl < p.nslabs; ++sl) {
-    a.g0 = sl * p.SG;
-    a.ng = c.G - a.g0 < p.SG ? c.G - a.g0 : p.SG;
-    a.ld = (a.ng + 63) / 64 * 64;
-    if (int rc = residual_slab(a, c, s)) return rc;
-    if (int rc = moran_slab_wide_run(p.slab, c.B, a.ng, a.ld, nbr, K, I ? I + a.g0 : nullptr, C ? C + a.g0 : nullptr,
-                                     res_mean + a.g0, res_var + a.g0, kurtosis + a.g0, info, w.wide, s))
-      return rc;
-    if (!permute) continue;
-    const SlabPermOut o{pc.n_ge + a.g0, pc.n_le + a.g0, pc.sim_mean + a.g0, pc.sim_m2 + a.g0,
-                        pc.sims ? pc.sims + a.g0 * pc.P : nullptr, pc.P, info};
-    if (int rc = moran_slab_perm_run(p.slab, c.B, a.ng, a.ld, nbr, K, pc.stat, pc.perms, pc.P, w.perm_batch, res_mean + a.g0,
-                                     w.wide, o, w.perm, s))
-      return rc;
-  }
-  return 0;
+  const bool outs = (I || C) && (permute || (I && C)) && res_mean && res_var && kurtosis;
+  return run_slabs(
+      who, c, nbr, K, slab_genes, true, permute ? pc.P : 0, pc.perm_batch, outs, info, partials, partials_bytes, stream,
+      [&](const Args& a, const Plan& p, hipStream_t s) {
+        if (int rc = moran_slab_wide_run(p.slab, c.B, a.ng, a.ld, nbr, K, I ? I + a.g0 : nullptr, C ? C + a.g0 : nullptr,
+                                         res_mean + a.g0, res_var + a.g0, kurtosis + a.g0, info, p.wide, s))
+          return rc;
+        if (!permute) return 0;
+        const SlabPermOut o{pc.n_ge + a.g0, pc.n_le + a.g0, pc.sim_mean + a.g0, pc.sim_m2 + a.g0,
+                            pc.sims ? pc.sims + a.g0 * pc.P : nullptr, pc.P, info};
+        GPZ_HIP_OK(hipMemsetAsync(o.n_ge, 0, size_t(a.ng) * sizeof(int32_t), s));      // the batches accumulate into these
+        GPZ_HIP_OK(hipMemsetAsync(o.n_le, 0, size_t(a.ng) * sizeof(int32_t), s));
+        GPZ_HIP_OK(hipMemsetAsync(o.sim_mean, 0, size_t(a.ng) * sizeof(double), s));
+        GPZ_HIP_OK(hipMemsetAsync(o.sim_m2, 0, size_t(a.ng) * sizeof(double), s));
+        return moran_slab_perm_run(p.slab, c.B, a.ng, a.ld, nbr, K, pc.stat, pc.perms, pc.P, p.perm_batch, res_mean + a.g0, p.wide,
+                                   o, p.perm, s);
+      });
 }
 
 static int run_stats(const char* who, const Call& c, const int64_t* nbr, int K, int64_t slab_genes, double* I, double* C,
@@ -597,6 +602,25 @@ static int run_perm(const char* who, const Call& c, const int64_t* nbr, int K, i
   if (int rc = check_perm(who, pc.P, pc.stat, pc.perm_batch)) return rc;
   return run_wide(who, c, nbr, K, slab_genes, pc.stat == 0 ? pc.value : nullptr, pc.stat == 0 ? nullptr : pc.value, res_mean,
                   res_var, kurtosis, pc, info, partials, partials_bytes, stream);
+}
+
+// What the plan queries of the entries over a table answer; K >= 1, P = 0: the scratch of the stats entries, no permutation arrays
+static int wide_plan(const char* who, int64_t B, int64_t D, int Lt, int K, int64_t P, int64_t nnz, int64_t slab_genes_wanted,
+                     int perm_batch_wanted, int64_t* slab_genes, int64_t* n_slabs, int32_t* spot_slices, int32_t* factors_padded,
+                     int32_t* perm_batch, int64_t* batches, int64_t* partials_bytes) {
+  if (int rc = check_shape(who, B, D, D, Lt, nnz, slab_genes_wanted)) return rc;
+  if (int rc = check_table(who, B, K)) return rc;
+  if (P != 0)
+    if (int rc = check_perm(who, P, 0, perm_batch_wanted)) return rc;
+  const Plan p = make_plan(B, D, Lt, slab_genes_wanted, nullptr, K, P, perm_batch_wanted);
+  if (slab_genes) *slab_genes = p.SG;
+  if (n_slabs) *n_slabs = p.nslabs;
+  if (spot_slices) *spot_slices = p.SN;
+  if (factors_padded) *factors_padded = 4 * p.KS;
+  if (perm_batch) *perm_batch = p.perm_batch;
+  if (batches) *batches = p.batches;
+  if (partials_bytes) *partials_bytes = (int64_t)p.bytes;
+  return 0;
 }
 
 }  // namespace rsd
@@ -625,8 +649,7 @@ extern "C" int gpz_count_residuals(const float* mean, const float* scale, const 
                                    const float* y, const int32_t* genes, int64_t B, int64_t D, int64_t G, int32_t Lt,
                                    int32_t family, int32_t kind, int32_t lognormal_mean, float* out, void* partials,
                                    size_t partials_bytes, void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, family, kind,
-                    lognormal_mean, false};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, y, genes, B, D, G, Lt, family, kind, lognormal_mean);
   return rsd::run_residuals("gpz_count_residuals", c, out, partials, partials_bytes, stream);
 }
 
@@ -636,8 +659,8 @@ extern "C" int gpz_count_residuals_sparse(const float* mean, const float* scale,
                                           int64_t D, int64_t nnz, int64_t G, int32_t Lt, int32_t family, int32_t kind,
                                           int32_t lognormal_mean, float* out, void* partials, size_t partials_bytes,
                                           void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, nullptr, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt, family,
-                    kind, lognormal_mean, true};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, nullptr, genes, B, D, G, Lt, family, kind, lognormal_mean)
+                          .stored(row_ptr, row_spot, row_perm, col_val, nnz);
   return rsd::run_residuals("gpz_count_residuals_sparse", c, out, partials, partials_bytes, stream);
 }
 
@@ -646,8 +669,7 @@ extern "C" int gpz_residual_morans_i(const float* mean, const float* scale, cons
                                      int32_t Lt, int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean,
                                      int64_t slab_genes, double* I, double* res_mean, double* res_var, int32_t* info,
                                      void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, family, kind,
-                    lognormal_mean, false};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, y, genes, B, D, G, Lt, family, kind, lognormal_mean);
   return rsd::run_moran("gpz_residual_morans_i", c, nbr, K, slab_genes, I, res_mean, res_var, info, partials, partials_bytes,
                         stream);
 }
@@ -659,8 +681,8 @@ extern "C" int gpz_residual_morans_i_sparse(const float* mean, const float* scal
                                             int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean, int64_t slab_genes,
                                             double* I, double* res_mean, double* res_var, int32_t* info, void* partials,
                                             size_t partials_bytes, void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, nullptr, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt, family,
-                    kind, lognormal_mean, true};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, nullptr, genes, B, D, G, Lt, family, kind, lognormal_mean)
+                          .stored(row_ptr, row_spot, row_perm, col_val, nnz);
   return rsd::run_moran("gpz_residual_morans_i_sparse", c, nbr, K, slab_genes, I, res_mean, res_var, info, partials,
                         partials_bytes, stream);
 }
@@ -668,18 +690,8 @@ extern "C" int gpz_residual_morans_i_sparse(const float* mean, const float* scal
 extern "C" int gpz_residual_autocorr_perm_plan(int64_t B, int64_t D, int32_t Lt, int32_t K, int64_t P, int64_t nnz,
                                                int64_t slab_genes_wanted, int32_t perm_batch_wanted, int64_t* slab_genes,
                                                int64_t* n_slabs, int32_t* perm_batch, int64_t* batches, int64_t* partials_bytes) {
-  const char* who = "gpz_residual_autocorr_perm_plan";
-  if (int rc = rsd::check_shape(who, B, D, D, Lt, nnz, slab_genes_wanted)) return rc;
-  if (int rc = rsd::check_table(who, B, K)) return rc;
-  if (P != 0)                                   // P = 0: the scratch of the stats entries, no permutation arrays
-    if (int rc = rsd::check_perm(who, P, 0, perm_batch_wanted)) return rc;
-  const rsd::WidePlan w = rsd::make_wide_plan(B, D, Lt, K, P, slab_genes_wanted, perm_batch_wanted, nullptr);
-  if (slab_genes) *slab_genes = w.base.SG;
-  if (n_slabs) *n_slabs = w.base.nslabs;
-  if (perm_batch) *perm_batch = w.perm_batch;
-  if (batches) *batches = w.batches;
-  if (partials_bytes) *partials_bytes = (int64_t)w.bytes;
-  return 0;
+  return rsd::wide_plan("gpz_residual_autocorr_perm_plan", B, D, Lt, K, P, nnz, slab_genes_wanted, perm_batch_wanted, slab_genes,
+                        n_slabs, nullptr, nullptr, perm_batch, batches, partials_bytes);
 }
 
 extern "C" int gpz_residual_spatial_stats(const float* mean, const float* scale, const float* W, const float* V, const float* theta,
@@ -687,8 +699,7 @@ extern "C" int gpz_residual_spatial_stats(const float* mean, const float* scale,
                                           int32_t Lt, int32_t K, int32_t family, int32_t kind, int32_t lognormal_mean,
                                           int64_t slab_genes, double* I, double* C, double* res_mean, double* res_var,
                                           double* kurtosis, int32_t* info, void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, family, kind,
-                    lognormal_mean, false};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, y, genes, B, D, G, Lt, family, kind, lognormal_mean);
   return rsd::run_stats("gpz_residual_spatial_stats", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info, partials,
                         partials_bytes, stream);
 }
@@ -701,8 +712,8 @@ extern "C" int gpz_residual_spatial_stats_sparse(const float* mean, const float*
                                                  int64_t slab_genes, double* I, double* C, double* res_mean, double* res_var,
                                                  double* kurtosis, int32_t* info, void* partials, size_t partials_bytes,
                                                  void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, nullptr, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt, family,
-                    kind, lognormal_mean, true};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, nullptr, genes, B, D, G, Lt, family, kind, lognormal_mean)
+                          .stored(row_ptr, row_spot, row_perm, col_val, nnz);
   return rsd::run_stats("gpz_residual_spatial_stats_sparse", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info,
                         partials, partials_bytes, stream);
 }
@@ -714,8 +725,7 @@ extern "C" int gpz_residual_autocorr_perm(const float* mean, const float* scale,
                                           double* value, int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2,
                                           double* sims, double* res_mean, double* res_var, double* kurtosis, int32_t* info,
                                           void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, y, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G, Lt, family, kind,
-                    lognormal_mean, false};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, y, genes, B, D, G, Lt, family, kind, lognormal_mean);
   const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
   return rsd::run_perm("gpz_residual_autocorr_perm", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
                        partials_bytes, stream);
@@ -730,8 +740,8 @@ extern "C" int gpz_residual_autocorr_perm_sparse(const float* mean, const float*
                                                  int32_t perm_batch, double* value, int32_t* n_ge, int32_t* n_le, double* sim_mean,
                                                  double* sim_m2, double* sims, double* res_mean, double* res_var, double* kurtosis,
                                                  int32_t* info, void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c{mean, scale, W, V, theta, nullptr, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt, family,
-                    kind, lognormal_mean, true};
+  const rsd::Call c = rsd::count_call(mean, scale, W, V, theta, nullptr, genes, B, D, G, Lt, family, kind, lognormal_mean)
+                          .stored(row_ptr, row_spot, row_perm, col_val, nnz);
   const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
   return rsd::run_perm("gpz_residual_autocorr_perm_sparse", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
                        partials_bytes, stream);
@@ -745,46 +755,26 @@ extern "C" int gpz_gaussian_residual_plan(int64_t B, int64_t D, int32_t Lt, int3
                                           int64_t* n_slabs, int32_t* spot_slices, int32_t* factors_padded, int32_t* perm_batch,
                                           int64_t* batches, int64_t* partials_bytes) {
   const char* who = "gpz_gaussian_residual_plan";
+  if (K != 0)
+    return rsd::wide_plan(who, B, D, Lt, K, P, nnz, slab_genes_wanted, perm_batch_wanted, slab_genes, n_slabs, spot_slices,
+                          factors_padded, perm_batch, batches, partials_bytes);
   if (int rc = rsd::check_shape(who, B, D, D, Lt, nnz, slab_genes_wanted)) return rc;
-  if (K == 0) {
-    GPZ_REQUIRE(P == 0, "%s: P = %lld permutations without a neighbour table (K = 0)", who, (long long)P);
-    const rsd::Plan p = rsd::make_plan(B, D, Lt, 64, nullptr);
-    if (slab_genes) *slab_genes = p.SG;
-    if (n_slabs) *n_slabs = p.nslabs;
-    if (spot_slices) *spot_slices = rsd::spot_slices(B, D);
-    if (factors_padded) *factors_padded = 4 * p.KS;
-    if (perm_batch) *perm_batch = 0;
-    if (batches) *batches = 0;
-    if (partials_bytes) *partials_bytes = (int64_t)p.small;
-    return 0;
-  }
-  if (int rc = rsd::check_table(who, B, K)) return rc;
-  if (P != 0)
-    if (int rc = rsd::check_perm(who, P, 0, perm_batch_wanted)) return rc;
-  const rsd::WidePlan w = rsd::make_wide_plan(B, D, Lt, K, P, slab_genes_wanted, perm_batch_wanted, nullptr);
-  if (slab_genes) *slab_genes = w.base.SG;
-  if (n_slabs) *n_slabs = w.base.nslabs;
-  if (spot_slices) *spot_slices = w.base.SN;
-  if (factors_padded) *factors_padded = 4 * w.base.KS;
-  if (perm_batch) *perm_batch = w.perm_batch;
-  if (batches) *batches = w.batches;
-  if (partials_bytes) *partials_bytes = (int64_t)w.bytes;
+  GPZ_REQUIRE(P == 0, "%s: P = %lld permutations without a neighbour table (K = 0)", who, (long long)P);
+  const rsd::Plan p = rsd::make_plan(B, D, Lt, 64, nullptr);
+  if (slab_genes) *slab_genes = p.SG;
+  if (n_slabs) *n_slabs = p.nslabs;
+  if (spot_slices) *spot_slices = rsd::spot_slices(B, D);
+  if (factors_padded) *factors_padded = 4 * p.KS;
+  if (perm_batch) *perm_batch = 0;
+  if (batches) *batches = 0;
+  if (partials_bytes) *partials_bytes = (int64_t)p.small;
   return 0;
-}
-
-static rsd::Call gaussian_call(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
-                               const float* y, const double* offset, const int64_t* row_ptr, const int32_t* row_spot,
-                               const int32_t* row_perm, const float* col_val, const int32_t* genes, int64_t B, int64_t D,
-                               int64_t nnz, int64_t G, int32_t Lt, int32_t kind, bool sparse) {
-  return rsd::Call{mean, scale, W, nullptr, nullptr, y, row_ptr, row_spot, row_perm, col_val, genes, B, D, nnz, G, Lt,
-                   0, kind, 0, sparse, b, noise_sd, offset, true};
 }
 
 extern "C" int gpz_gaussian_residuals(const float* mean, const float* scale, const float* W, const float* b, const float* noise_sd,
                                       const float* y, const int32_t* genes, int64_t B, int64_t D, int64_t G, int32_t Lt,
                                       int32_t kind, float* out, void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, y, nullptr, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G,
-                                    Lt, kind, false);
+  const rsd::Call c = rsd::gaussian_call(mean, scale, W, b, noise_sd, y, genes, B, D, G, Lt, kind);
   return rsd::run_residuals("gpz_gaussian_residuals", c, out, partials, partials_bytes, stream);
 }
 
@@ -793,8 +783,8 @@ extern "C" int gpz_gaussian_residuals_sparse(const float* mean, const float* sca
                                              const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
                                              const int32_t* genes, int64_t B, int64_t D, int64_t nnz, int64_t G, int32_t Lt,
                                              int32_t kind, float* out, void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, nullptr, offset, row_ptr, row_spot, row_perm, col_val, genes, B, D,
-                                    nnz, G, Lt, kind, true);
+  const rsd::Call c = rsd::gaussian_call(mean, scale, W, b, noise_sd, nullptr, genes, B, D, G, Lt, kind)
+                          .stored(row_ptr, row_spot, row_perm, col_val, nnz, offset);
   return rsd::run_residuals("gpz_gaussian_residuals_sparse", c, out, partials, partials_bytes, stream);
 }
 
@@ -803,8 +793,7 @@ extern "C" int gpz_gaussian_residual_stats(const float* mean, const float* scale
                                            int64_t B, int64_t D, int64_t G, int32_t Lt, int32_t K, int32_t kind, int64_t slab_genes,
                                            double* I, double* C, double* res_mean, double* res_var, double* kurtosis, int32_t* info,
                                            void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, y, nullptr, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G,
-                                    Lt, kind, false);
+  const rsd::Call c = rsd::gaussian_call(mean, scale, W, b, noise_sd, y, genes, B, D, G, Lt, kind);
   return rsd::run_stats("gpz_gaussian_residual_stats", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info, partials,
                         partials_bytes, stream);
 }
@@ -816,8 +805,8 @@ extern "C" int gpz_gaussian_residual_stats_sparse(const float* mean, const float
                                                   int64_t G, int32_t Lt, int32_t K, int32_t kind, int64_t slab_genes, double* I,
                                                   double* C, double* res_mean, double* res_var, double* kurtosis, int32_t* info,
                                                   void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, nullptr, offset, row_ptr, row_spot, row_perm, col_val, genes, B, D,
-                                    nnz, G, Lt, kind, true);
+  const rsd::Call c = rsd::gaussian_call(mean, scale, W, b, noise_sd, nullptr, genes, B, D, G, Lt, kind)
+                          .stored(row_ptr, row_spot, row_perm, col_val, nnz, offset);
   return rsd::run_stats("gpz_gaussian_residual_stats_sparse", c, nbr, K, slab_genes, I, C, res_mean, res_var, kurtosis, info,
                         partials, partials_bytes, stream);
 }
@@ -829,8 +818,7 @@ extern "C" int gpz_gaussian_residual_perm(const float* mean, const float* scale,
                                           int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2, double* sims,
                                           double* res_mean, double* res_var, double* kurtosis, int32_t* info, void* partials,
                                           size_t partials_bytes, void* stream) {
-  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, y, nullptr, nullptr, nullptr, nullptr, nullptr, genes, B, D, 0, G,
-                                    Lt, kind, false);
+  const rsd::Call c = rsd::gaussian_call(mean, scale, W, b, noise_sd, y, genes, B, D, G, Lt, kind);
   const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
   return rsd::run_perm("gpz_gaussian_residual_perm", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
                        partials_bytes, stream);
@@ -845,8 +833,8 @@ extern "C" int gpz_gaussian_residual_perm_sparse(const float* mean, const float*
                                                  int32_t* n_ge, int32_t* n_le, double* sim_mean, double* sim_m2, double* sims,
                                                  double* res_mean, double* res_var, double* kurtosis, int32_t* info,
                                                  void* partials, size_t partials_bytes, void* stream) {
-  const rsd::Call c = gaussian_call(mean, scale, W, b, noise_sd, nullptr, offset, row_ptr, row_spot, row_perm, col_val, genes, B, D,
-                                    nnz, G, Lt, kind, true);
+  const rsd::Call c = rsd::gaussian_call(mean, scale, W, b, noise_sd, nullptr, genes, B, D, G, Lt, kind)
+                          .stored(row_ptr, row_spot, row_perm, col_val, nnz, offset);
   const rsd::PermCall pc{perms, P, stat, perm_batch, value, sims, n_ge, n_le, sim_mean, sim_m2};
   return rsd::run_perm("gpz_gaussian_residual_perm_sparse", c, nbr, K, slab_genes, pc, res_mean, res_var, kurtosis, info, partials,
                        partials_bytes, stream);

@@ -1,5 +1,6 @@
 // residual_gaussian.h -- the residual pass of the Gaussian factor models (RSF, FA) for residual.hip, which includes this file
-// after its own kernels and shares its plan and its driver with it: residuals of real-valued expression under
+// after its own kernels and shares gene_of, for_ksteps, launch_slab, its plan and its driver with it; all that is host code
+// here is gs_residual_slab, which names this family's kernels to launch_slab.  Residuals of real-valued expression under
 //
 //   yhat[d,n] = b[d] + sum_l W[d,l] mean[l,n]                  v[d,n] = sd[d]^2 + sum_l W[d,l]^2 scale[l,n]^2
 //   kind 0, Pearson:     r = (y - yhat) / sd[d]
@@ -42,12 +43,6 @@ struct GArgs {
   int64_t B, D, g0, ng, ld;
   int Lt, SN, kind;
 };
-
-__device__ __forceinline__ int64_t gene_of(const GArgs& a, int64_t col) {
-  if (col >= a.ng) return -1;
-  const int64_t g = a.genes ? (int64_t)a.genes[a.g0 + col] : a.g0 + col;
-  return g >= 0 && g < a.D ? g : -1;
-}
 
 // z = sum_l W m, z2 = sum_l W^2 s^2 (read by the predictive kind alone)
 __device__ __forceinline__ float gs_residual(float y, float b, float z, float sd, float z2, int kind) {
@@ -231,45 +226,14 @@ __global__ __launch_bounds__(256) void gs_stored_kernel(GArgs a) {
   }
 }
 
-template <int KS, bool PRED>
-static int gs_launch_slab(const GArgs& a, bool sparse, hipStream_t s) {
-  const dim3 grid((unsigned)((a.ld + BG - 1) / BG), (unsigned)a.SN), block(256);
-  if (!sparse) {
-    hipLaunchKernelGGL((gs_tile_kernel<KS, PRED, false>), grid, block, 0, s, a);
-    GPZ_LAUNCH_OK();
-    return 0;
-  }
-  hipLaunchKernelGGL((gs_tile_kernel<KS, PRED, true>), grid, block, 0, s, a);
-  GPZ_LAUNCH_OK();
-  if (a.rows.nnz > 0) {
-    const int64_t chunks = (a.B + CHUNK - 1) / CHUNK;             // a gene row holds at most B entries
-    hipLaunchKernelGGL((gs_stored_kernel<KS, PRED>), dim3((unsigned)a.ng, (unsigned)((chunks + 3) / 4)), block, 0, s, a);
-    GPZ_LAUNCH_OK();
-  }
-  return 0;
-}
-
-template <int KS>
-static int gs_launch_kind(const GArgs& a, bool sparse, hipStream_t s) {
-  return a.kind == 2 ? gs_launch_slab<KS, true>(a, sparse, s) : gs_launch_slab<KS, false>(a, sparse, s);
-}
-
+// the residual pass of one slab (launch_slab of residual.hip): the predictive kind has instances of its own
 static int gs_residual_slab(const GArgs& a, bool sparse, hipStream_t s) {
-  switch (ksteps(a.Lt)) {
-    case 1: return gs_launch_kind<1>(a, sparse, s);
-    case 2: return gs_launch_kind<2>(a, sparse, s);
-    case 3: return gs_launch_kind<3>(a, sparse, s);
-    case 4: return gs_launch_kind<4>(a, sparse, s);
-    case 5: return gs_launch_kind<5>(a, sparse, s);
-    case 6: return gs_launch_kind<6>(a, sparse, s);
-    case 7: return gs_launch_kind<7>(a, sparse, s);
-    case 8: return gs_launch_kind<8>(a, sparse, s);
-    case 9: return gs_launch_kind<9>(a, sparse, s);
-    case 10: return gs_launch_kind<10>(a, sparse, s);
-    case 12: return gs_launch_kind<12>(a, sparse, s);
-    case 14: return gs_launch_kind<14>(a, sparse, s);
-    default: return gs_launch_kind<16>(a, sparse, s);
-  }
+  return for_ksteps(a.Lt, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    if (a.kind == 2)
+      return launch_slab(gs_tile_kernel<KS, true, false>, gs_tile_kernel<KS, true, true>, gs_stored_kernel<KS, true>, a, sparse, s);
+    return launch_slab(gs_tile_kernel<KS, false, false>, gs_tile_kernel<KS, false, true>, gs_stored_kernel<KS, false>, a, sparse, s);
+  });
 }
 
 }  // namespace rsd

@@ -906,22 +906,36 @@ def residual_autocorr(qF_list, W_list, V_pos, y, nbr, *, theta_pos=None, kind="p
     normal approximation does not; it does not turn the score into a test of the model."""
     B = int(nbr.shape[0]) if isinstance(nbr, torch.Tensor) else len(nbr)
     null = _residual_null_args("residual_autocorr", B, mode, assumption, n_perms, perms)
-    return _residual_autocorr_checked(qF_list, W_list, V_pos, y, nbr, null, theta_pos, kind, lognormal_mean, slab_genes, mode,
-                                      assumption, seed, return_sims)
+    entries = _count_entries(V_pos, y, nbr, theta_pos, kind, lognormal_mean, slab_genes, mode, return_sims)
+    return _residual_autocorr_checked(entries, qF_list, W_list, nbr, null, mode, assumption, seed)
 
 
-def _residual_autocorr_checked(qF_list, W_list, V_pos, y, nbr, null, theta_pos, kind, lognormal_mean, slab_genes, mode, assumption,
-                               seed, return_sims):
-    """``residual_autocorr`` behind its refusals: ``null`` is what ``_residual_null_args`` returned for the B scored spots."""
+def _count_entries(V_pos, y, nbr, theta_pos, kind, lognormal_mean, slab_genes, mode, return_sims):
+    """The count family for ``_residual_autocorr_checked``: (mean, scale, W) -> its Moran-only, wide and permutation entries."""
     from . import ops
+
+    def bind(mean, scale, W):
+        head, tail = (mean, scale, W, V_pos, y, nbr), (theta_pos, None, kind, lognormal_mean)
+        return (lambda: ops.residual_morans_i(*head, *tail, slab_genes),
+                lambda: ops.residual_spatial_stats(*head, *tail, slab_genes),
+                lambda perms: ops.residual_autocorr_perm(*head, perms, *tail, stat=mode, return_sims=return_sims,
+                                                         slab_genes=slab_genes))
+    return bind
+
+
+def _residual_autocorr_checked(entries, qF_list, W_list, nbr, null, mode, assumption, seed):
+    """``residual_autocorr`` and ``gaussian_residual_autocorr`` behind their refusals: ``entries`` is the family
+    (``_count_entries``, ``_gaussian_entries``), ``null`` what ``_residual_null_args`` returned for the B scored spots."""
     with torch.no_grad():
         mean, scale, W = _cat_factors(qF_list, W_list)
-        return _autocorr_assembly(
-            lambda: ops.residual_morans_i(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes),
-            lambda: ops.residual_spatial_stats(mean, scale, W, V_pos, y, nbr, theta_pos, None, kind, lognormal_mean, slab_genes),
-            lambda perms: ops.residual_autocorr_perm(mean, scale, W, V_pos, y, nbr, perms, theta_pos, None, kind, lognormal_mean,
-                                                     stat=mode, return_sims=return_sims, slab_genes=slab_genes),
-            mean.device, nbr, null, mode, assumption, seed)
+        return _autocorr_assembly(*entries(mean, scale, W), mean.device, nbr, null, mode, assumption, seed)
+
+
+def _scored_spot_count(X, idx):
+    """The number of scored spots, the rows of ``X[idx]``: ``idx`` None, a boolean mask or a list of indices."""
+    if idx is None:
+        return int(X.shape[0])
+    return int(idx.sum()) if getattr(idx, "dtype", None) == torch.bool else len(idx)
 
 
 def _autocorr_assembly(narrow, stats, perm, dev, nbr, null, mode, assumption, seed):
@@ -1001,14 +1015,13 @@ class _ResidualScores:
         from . import ops
         self._residual_data(y, "residual_autocorr")
         theta_pos = self._residual_theta(kind, family, theta)
-        mask = idx is not None and getattr(idx, "dtype", None) == torch.bool
-        B = int(X.shape[0]) if idx is None else int(idx.sum()) if mask else len(idx)      # the scored spots: the rows of X[idx]
-        null = _residual_null_args(f"{type(self).__name__}.residual_autocorr", B, mode, assumption, n_perms, perms)
+        null = _residual_null_args(f"{type(self).__name__}.residual_autocorr", _scored_spot_count(X, idx), mode, assumption, n_perms,
+                                   perms)
         with torch.no_grad():
             qF, W, Vp, Xb = self._score_parts(X, idx, V, kwargs)
             nbr = ops.spatial_knn(Xb, int(n_neighs)) if graph is None else torch.as_tensor(graph)
-            return _residual_autocorr_checked(qF, W, Vp, y, nbr, null, theta_pos, kind, lognormal_mean, 0, mode, assumption, seed,
-                                              return_sims)
+            entries = _count_entries(Vp, y, nbr, theta_pos, kind, lognormal_mean, 0, mode, return_sims)
+            return _residual_autocorr_checked(entries, qF, W, nbr, null, mode, assumption, seed)
 
     def residuals(self, X, y, genes, idx=None, V=None, *, kind="pearson", family="model", theta=None, lognormal_mean=True,
                   **kwargs):
@@ -1506,21 +1519,21 @@ def gaussian_residual_autocorr(qF_list, W_list, b, noise_sd, y, nbr, *, kind="pe
     ops._gaussian_data(who, y)
     B = int(nbr.shape[0]) if isinstance(nbr, torch.Tensor) else len(nbr)
     null = _residual_null_args(who, B, mode, assumption, n_perms, perms)
-    return _gaussian_autocorr_checked(qF_list, W_list, b, noise_sd, y, torch.as_tensor(nbr), null, kind, slab_genes, mode,
-                                      assumption, seed, return_sims)
+    nbr = torch.as_tensor(nbr)
+    entries = _gaussian_entries(b, noise_sd, y, nbr, kind, slab_genes, mode, return_sims)
+    return _residual_autocorr_checked(entries, qF_list, W_list, nbr, null, mode, assumption, seed)
 
 
-def _gaussian_autocorr_checked(qF_list, W_list, b, noise_sd, y, nbr, null, kind, slab_genes, mode, assumption, seed, return_sims):
-    """``gaussian_residual_autocorr`` behind its refusals (``_residual_autocorr_checked``'s sibling; no Moran-only entry)."""
+def _gaussian_entries(b, noise_sd, y, nbr, kind, slab_genes, mode, return_sims):
+    """The Gaussian family for ``_residual_autocorr_checked``: no Moran-only entry, the wide and the permutation entry."""
     from . import ops
-    with torch.no_grad():
-        mean, scale, W = _cat_factors(qF_list, W_list)
-        return _autocorr_assembly(
-            None,
-            lambda: ops.gaussian_residual_stats(mean, scale, W, b, noise_sd, y, nbr, None, kind, slab_genes),
-            lambda perms: ops.gaussian_residual_autocorr_perm(mean, scale, W, b, noise_sd, y, nbr, perms, None, kind, stat=mode,
-                                                              return_sims=return_sims, slab_genes=slab_genes),
-            mean.device, nbr, null, mode, assumption, seed)
+
+    def bind(mean, scale, W):
+        head = (mean, scale, W, b, noise_sd, y, nbr)
+        return (None, lambda: ops.gaussian_residual_stats(*head, None, kind, slab_genes),
+                lambda perms: ops.gaussian_residual_autocorr_perm(*head, perms, None, kind, stat=mode, return_sims=return_sims,
+                                                                  slab_genes=slab_genes))
+    return bind
 
 
 def gaussian_residuals(qF_list, W_list, b, noise_sd, y, genes, *, kind="pearson"):
@@ -1560,8 +1573,7 @@ class _GaussianResidualScores:
         who = f"{type(self).__name__}.{what}"
         ops._gaussian_kind(who, kind)
         ops._gaussian_data(who, y)
-        mask = idx is not None and getattr(idx, "dtype", None) == torch.bool
-        return who, int(X.shape[0]) if idx is None else int(idx.sum()) if mask else len(idx)
+        return who, _scored_spot_count(X, idx)
 
     def _residual_autocorr(self, X, y, idx=None, *, kind="pearson", n_neighs=6, graph=None, mode="moran", assumption="normality",
                            n_perms=None, seed=0, perms=None, return_sims=False, groupsX=None):
@@ -1578,8 +1590,8 @@ class _GaussianResidualScores:
         with torch.no_grad():
             qF = self._residual_factors(X, idx, groupsX)
             nbr = ops.spatial_knn(X if idx is None else X[idx], int(n_neighs)) if graph is None else torch.as_tensor(graph)
-            return _gaussian_autocorr_checked([qF], [self.W], self.b, _noise_sd(self.noise), y, nbr, null, kind, 0, mode,
-                                              assumption, seed, return_sims)
+            entries = _gaussian_entries(self.b, _noise_sd(self.noise), y, nbr, kind, 0, mode, return_sims)
+            return _residual_autocorr_checked(entries, [qF], [self.W], nbr, null, mode, assumption, seed)
 
     def residuals(self, X, y, genes, idx=None, *, kind="pearson", groupsX=None):
         """(len(genes), B) fp32 residuals of the listed genes at ``X`` (or ``X[idx]``): the rows ``model_residual_autocorr``

@@ -1919,6 +1919,18 @@ def gene_dispersion_sparse(counts, size, theta_min: float = 1e-4, theta_max: flo
 
 
 RESIDUAL_KINDS = {"pearson": 0, "deviance": 1}
+GAUSSIAN_RESIDUAL_KINDS = {"pearson": 0, "response": 1, "predictive": 2}
+
+
+def _plan_query(entry: str, args, **outs) -> dict:
+    """A host-only plan query of the library: ``entry(*args, &out ...)``.  ``outs`` names the outputs in the entry's order
+    and gives each its ctypes type; returns their values under those names.  A refusal raises ValueError with the entry's
+    message."""
+    lib = _lib.load()
+    cells = {k: t() for k, t in outs.items()}
+    if getattr(lib, entry)(*(int(x) for x in args), *(C.byref(c) for c in cells.values())) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return {k: int(c.value) for k, c in cells.items()}
 
 
 def residual_autocorr_plan(B: int, D: int, Lt: int, nnz: int = 0, slab_genes: int = 0) -> dict:
@@ -1927,18 +1939,105 @@ def residual_autocorr_plan(B: int, D: int, Lt: int, nnz: int = 0, slab_genes: in
     64 and at most D rounded up to 64, or the caller's positive multiple of 64) and ``n_slabs``; the residual pass's
     ``spots_per_tile``, ``genes_per_block``, ``spot_slices`` and ``factors_padded``; ``gene_chunk`` (stored entries of a gene
     row per wave, sparse counts); ``partials_bytes`` (the scratch, slab included)."""
-    lib = _lib.load()
-    sg, ns, nb = C.c_int64(), C.c_int64(), C.c_int64()
-    v = [C.c_int32() for _ in range(5)]
-    rc = lib.gpz_residual_morans_i_plan(int(B), int(D), int(Lt), int(nnz), int(slab_genes), C.byref(sg), C.byref(ns),
-                                        *(C.byref(x) for x in v), C.byref(nb))
-    if rc != 0:
-        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
-    return dict(slab_genes=sg.value, n_slabs=ns.value, spots_per_tile=v[0].value, genes_per_block=v[1].value,
-                spot_slices=v[2].value, gene_chunk=v[3].value, factors_padded=v[4].value, partials_bytes=int(nb.value))
+    i32, i64 = C.c_int32, C.c_int64
+    return _plan_query("gpz_residual_morans_i_plan", (B, D, Lt, nnz, slab_genes), slab_genes=i64, n_slabs=i64, spots_per_tile=i32,
+                       genes_per_block=i32, spot_slices=i32, gene_chunk=i32, factors_padded=i32, partials_bytes=i64)
 
 
-def _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind):
+def residual_autocorr_perm_plan(B: int, D: int, Lt: int, K: int, P: int, nnz: int = 0, slab_genes: int = 0,
+                                perm_batch: int = 0) -> dict:
+    """How ``residual_autocorr_perm`` covers B spots, D scored genes and P permutations over K neighbours
+    (gpz_residual_autocorr_perm_plan, a host-only query: no device needed): ``slab_genes`` and ``n_slabs`` as
+    ``residual_autocorr_plan`` gives them; ``perm_batch``, the permutations per launch as resolved (the caller's 1..32, or
+    the plan's choice, whose relabelled tables of 4 B K bytes each stay within 256 MiB); ``batches`` per slab;
+    ``partials_bytes``: the slab, plus O(perm_batch B K) table bytes, plus O(B / 256 x perm_batch x slab_genes) partial
+    sums.  ``P=0`` asks for what ``residual_spatial_stats`` needs: no tables, ``perm_batch`` = ``batches`` = 0."""
+    i32, i64 = C.c_int32, C.c_int64
+    return _plan_query("gpz_residual_autocorr_perm_plan", (B, D, Lt, K, P, nnz, slab_genes, perm_batch), slab_genes=i64,
+                       n_slabs=i64, perm_batch=i32, batches=i64, partials_bytes=i64)
+
+
+def gaussian_residual_plan(B: int, D: int, Lt: int, K: int = 0, P: int = 0, nnz: int = 0, slab_genes: int = 0,
+                           perm_batch: int = 0) -> dict:
+    """How the Gaussian residual entries cover B spots, D scored genes, K neighbours and P permutations
+    (gpz_gaussian_residual_plan, a host-only query: no device needed): ``slab_genes``, ``n_slabs``, ``perm_batch``,
+    ``batches`` and ``partials_bytes`` as ``residual_autocorr_perm_plan`` gives them, with the residual pass's ``spot_slices``
+    and ``factors_padded``.  ``P=0``: what ``gaussian_residual_stats`` needs; ``K=0`` (with ``P=0``): what
+    ``gaussian_residuals`` needs, the factor scratch alone."""
+    i32, i64 = C.c_int32, C.c_int64
+    return _plan_query("gpz_gaussian_residual_plan", (B, D, Lt, K, P, nnz, slab_genes, perm_batch), slab_genes=i64, n_slabs=i64,
+                       spot_slices=i32, factors_padded=i32, perm_batch=i32, batches=i64, partials_bytes=i64)
+
+
+@dataclass(frozen=True)
+class _ResidualFamily:
+    """What differs between the count and the Gaussian residual entries, for ``_residual_model`` and ``_residual_run``."""
+    params: tuple       # the model tensors after mean and scale, by the name the messages give them: an entry's head pointers
+    shapes: object      # (Lt, B, D) -> their shapes
+    elsewhere: str      # the refusal of sparse data on another device than the model's: .format(the data's, the model's)
+    stored: object      # a whole sparse container -> (its pointers ahead of the rows' arrays, the SparseCounts that holds them)
+    scalars: tuple      # the scalar arguments between Lt [, K] and slab_genes or the outputs, as keys of the checked arguments
+    stems: dict         # stage -> the entry's name; data stored as its non-zeros goes to the entry of that name + "_sparse"
+    plan: object        # (stage, B, G, Lt, K, P, nnz, slab_genes, perm_batch) -> the stage's plan
+
+
+def _count_plan(stage, B, G, Lt, K, P, nnz, slab_genes, perm_batch):
+    if stage in ("residuals", "morans_i"):
+        return residual_autocorr_plan(B, G, Lt, nnz, 64 if stage == "residuals" else slab_genes)
+    return residual_autocorr_perm_plan(B, G, Lt, K, P, nnz, slab_genes, perm_batch)
+
+
+def _gaussian_plan(stage, B, G, Lt, K, P, nnz, slab_genes, perm_batch):
+    return gaussian_residual_plan(B, G, Lt, K, P, nnz, slab_genes, perm_batch)
+
+
+_COUNT_RESIDUALS = _ResidualFamily(
+    params=("W", "V", "theta"), shapes=lambda Lt, B, D: ((D, Lt), (B,), (D,)),
+    elsewhere="gpzoo_amd: the counts live on {}, the model on {}: move them with counts.to(device)",
+    stored=lambda y: ([], y), scalars=("family", "kind", "lognormal"),
+    stems=dict(residuals="gpz_count_residuals", morans_i="gpz_residual_morans_i", stats="gpz_residual_spatial_stats",
+               perm="gpz_residual_autocorr_perm"),
+    plan=_count_plan)
+_GAUSSIAN_RESIDUALS = _ResidualFamily(
+    params=("W", "b", "noise_sd"), shapes=lambda Lt, B, D: ((D, Lt), (D,), (D,)),
+    elsewhere="gpzoo_amd: the expression lives on {}, the model on {}: move it with expr.to(device)",
+    stored=lambda y: ([_ptr(y.offset)], y.values), scalars=("kind",),
+    stems=dict(residuals="gpz_gaussian_residuals", stats="gpz_gaussian_residual_stats", perm="gpz_gaussian_residual_perm"),
+    plan=_gaussian_plan)
+
+
+def _residual_model(who, fam, sparse, mean, scale, y, params, genes):
+    """What the residual entries of either family check before any device work, once the form of ``y`` and the kind are
+    settled, and their arguments in the entries' types.  ``params``: the tensors of ``fam.params`` (None: an absent theta)."""
+    if mean.dim() != 2:
+        raise ValueError(f"{who}: mean must be (Lt, B), got shape {tuple(mean.shape)}")
+    Lt, B = mean.shape
+    D = y.shape[0]
+    if (tuple(y.shape) != (D, B) or scale.shape != (Lt, B)
+            or any(t is not None and t.shape != shape for t, shape in zip(params, fam.shapes(Lt, B, D)))):
+        raise ValueError(f"{who}: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, "
+                         + ", ".join(f"{k} {tuple(t.shape)}" for k, t in zip(fam.params, params) if t is not None)
+                         + " do not fit together")
+    g = None
+    if genes is not None:
+        g = genes.detach() if isinstance(genes, torch.Tensor) else torch.as_tensor(genes)
+        if g.dim() != 1 or g.numel() < 1 or g.is_floating_point() or g.dtype == torch.bool:
+            raise ValueError(f"{who}: genes must be a non-empty 1-D list of gene indices")
+        if bool(((g < 0) | (g >= D)).any()):
+            raise IndexError(f"{who}: a gene index lies outside [0, {D})")
+    dense = [mean, scale, *params, None if sparse else y]
+    _need_cuda(*dense)
+    dev = _same_device(*dense)
+    if sparse and y.device != dev:
+        raise RuntimeError(fam.elsewhere.format(y.device, dev))
+    prep = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()  # noqa: E731
+    if g is not None:
+        g = g.to(device=dev, dtype=torch.int32).contiguous()
+    return dict(zip(fam.params, map(prep, params)), mean=prep(mean), scale=prep(scale), y=y if sparse else prep(y), genes=g,
+                sparse=sparse, dev=dev, B=B, D=D, G=D if g is None else int(g.numel()), Lt=Lt, nnz=y.nnz if sparse else 0)
+
+
+def _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind, lognormal_mean):
     """Everything the residual entries check before any device work, and their arguments in the entries' types."""
     from .likelihoods import SparseCounts, TransposedCounts, _counts_expected
     if isinstance(y, TransposedCounts):
@@ -1952,248 +2051,8 @@ def _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind):
         raise TypeError(f"{who}: y must be a dense (D, B) tensor or a whole SparseCounts, got {type(y).__name__}")
     if kind not in RESIDUAL_KINDS:
         raise ValueError(f'{who}: kind must be "pearson" or "deviance", got {kind!r}')
-    if mean.dim() != 2:
-        raise ValueError(f"{who}: mean must be (Lt, B), got shape {tuple(mean.shape)}")
-    Lt, B = mean.shape
-    D = y.shape[0]
-    if (tuple(y.shape) != (D, B) or scale.shape != (Lt, B) or W_pos.shape != (D, Lt) or V_pos.shape != (B,)
-            or (theta_pos is not None and theta_pos.shape != (D,))):
-        raise ValueError(f"{who}: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, W {tuple(W_pos.shape)}, "
-                         f"V {tuple(V_pos.shape)}" + ("" if theta_pos is None else f", theta {tuple(theta_pos.shape)}")
-                         + " do not fit together")
-    g = None
-    if genes is not None:
-        g = genes.detach() if isinstance(genes, torch.Tensor) else torch.as_tensor(genes)
-        if g.dim() != 1 or g.numel() < 1 or g.is_floating_point() or g.dtype == torch.bool:
-            raise ValueError(f"{who}: genes must be a non-empty 1-D list of gene indices")
-        if bool(((g < 0) | (g >= D)).any()):
-            raise IndexError(f"{who}: a gene index lies outside [0, {D})")
-    _need_cuda(mean, scale, W_pos, V_pos, theta_pos, None if sparse else y)
-    dev = _same_device(mean, scale, W_pos, V_pos, theta_pos, None if sparse else y)
-    if sparse and y.device != dev:
-        raise RuntimeError(f"gpzoo_amd: the counts live on {y.device}, the model on {dev}: move them with counts.to(device)")
-    f32 = torch.float32
-    prep = lambda t: None if t is None else t.detach().to(f32).contiguous()  # noqa: E731
-    mean, scale, W_pos, V_pos, theta_pos = prep(mean), prep(scale), prep(W_pos), prep(V_pos), prep(theta_pos)
-    if not sparse:
-        y = prep(y)
-    if g is not None:
-        g = g.to(device=dev, dtype=torch.int32).contiguous()
-    G = D if g is None else int(g.numel())
-    return dict(mean=mean, scale=scale, W=W_pos, V=V_pos, theta=theta_pos, y=y, genes=g, sparse=sparse, dev=dev, B=B, D=D,
-                G=G, Lt=Lt, nnz=y.nnz if sparse else 0, family=int(theta_pos is not None), kind=RESIDUAL_KINDS[kind])
-
-
-def _residual_inputs(a):
-    """The leading pointer arguments of the four residual entries."""
-    head = [_ptr(a[k]) for k in ("mean", "scale", "W", "V", "theta")]
-    y = a["y"]
-    if a["sparse"]:
-        return head + [_ptr(y.row_ptr), _ptr(y.row_spot), _ptr(y.row_perm), _ptr(y.col_val), _ptr(a["genes"])]
-    return head + [_ptr(y), _ptr(a["genes"])]
-
-
-def count_residuals(mean, scale, W_pos, V_pos, y, theta_pos=None, genes=None, kind="pearson", lognormal_mean: bool = True):
-    """(B, G) fp32 residuals, spot-major, of the counts under the predictive mean rate mu = V W m of ``poisson_deviance``
-    (gpz_count_residuals / gpz_count_residuals_sparse).  ``kind="pearson"``: (y - mu) / sqrt(mu (1 + mu / theta));
-    ``"deviance"``: sign(y - mu) sqrt(unit deviance).  ``theta_pos`` (D,) selects the negative binomial, None the Poisson
-    family.  ``genes``: a list of gene indices in any order, repeats allowed (column g is gene ``genes[g]``), or None for all.
-    ``y``: dense (D, B), or a whole ``SparseCounts`` (the same bits as on its dense array)."""
-    who = "count_residuals"
-    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
-    lib = _lib.load()
-    nb = residual_autocorr_plan(a["B"], a["G"], a["Lt"], a["nnz"], 64)["partials_bytes"]
-    out = torch.empty((a["B"], a["G"]), dtype=torch.float32, device=a["dev"])
-    tail = [a["Lt"], a["family"], a["kind"], int(bool(lognormal_mean)), _ptr(out)]
-    with torch.cuda.device(a["dev"]):
-        ws = _workspace(a["dev"], nb)
-        if a["sparse"]:
-            rc = lib.gpz_count_residuals_sparse(*_residual_inputs(a), a["B"], a["D"], a["nnz"], a["G"], *tail, _ptr(ws), ws.numel(),
-                                                _stream(a["dev"]))
-        else:
-            rc = lib.gpz_count_residuals(*_residual_inputs(a), a["B"], a["D"], a["G"], *tail, _ptr(ws), ws.numel(),
-                                         _stream(a["dev"]))
-    _lib.check(rc, "gpz_count_residuals")
-    return out
-
-
-def residual_morans_i(mean, scale, W_pos, V_pos, y, nbr, theta_pos=None, genes=None, kind="pearson",
-                      lognormal_mean: bool = True, slab_genes: int = 0) -> dict:
-    """Moran's I of every gene's residuals (``count_residuals``' arguments) over the neighbour table nbr (B, K) int64 of
-    distinct neighbours, 1 <= K <= 32, with weights 1 / K (gpz_residual_morans_i / gpz_residual_morans_i_sparse): a dict of
-    fp64 (G,) tensors ``I``, ``residual_mean`` and ``residual_var`` (sum z^2 / B).  The genes are taken in slabs of
-    ``slab_genes`` columns (0: ``residual_autocorr_plan``'s choice); neither the (D, B) rate nor the (D, B) residuals exist.
-    Sums in a fixed order: repeated calls agree bit for bit.  A table entry outside [0, B) or naming its own row raises
-    ValueError (checked on the device; one synchronisation)."""
-    who = "residual_morans_i"
-    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
-        raise ValueError(f"{who}: nbr must be a (B, K) integer table")
-    K = int(nbr.shape[1])
-    if not 1 <= K <= 32:
-        raise ValueError(f"{who}: K = {K} neighbours unsupported (1..32)")
-    if int(slab_genes) != slab_genes or int(slab_genes) < 0 or int(slab_genes) % 64:
-        raise ValueError(f"{who}: slab_genes = {slab_genes!r} is not a positive multiple of 64 (or 0: the plan's choice)")
-    if nbr.shape[0] != mean.shape[-1]:
-        raise ValueError(f"{who}: nbr {tuple(nbr.shape)} for {mean.shape[-1]} spots")
-    if K >= nbr.shape[0]:
-        raise ValueError(f"{who}: {K} neighbours of {nbr.shape[0]} spots (K < B needed)")
-    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
-    lib = _lib.load()
-    dev, G = a["dev"], a["G"]
-    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
-    nb = residual_autocorr_plan(a["B"], G, a["Lt"], a["nnz"], int(slab_genes))["partials_bytes"]
-    out = [torch.empty(G, dtype=torch.float64, device=dev) for _ in range(3)]
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    tail = [a["Lt"], K, a["family"], a["kind"], int(bool(lognormal_mean)), int(slab_genes), *(_ptr(t) for t in out), _ptr(info)]
-    with torch.cuda.device(dev):
-        ws = _workspace(dev, nb)
-        if a["sparse"]:
-            rc = lib.gpz_residual_morans_i_sparse(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], a["nnz"], G, *tail, _ptr(ws),
-                                                  ws.numel(), _stream(dev))
-        else:
-            rc = lib.gpz_residual_morans_i(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], G, *tail, _ptr(ws), ws.numel(),
-                                           _stream(dev))
-    _lib.check(rc, "gpz_residual_morans_i")
-    if int(info.item()) != 0:
-        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
-    return dict(I=out[0], residual_mean=out[1], residual_var=out[2])
-
-
-def residual_autocorr_perm_plan(B: int, D: int, Lt: int, K: int, P: int, nnz: int = 0, slab_genes: int = 0,
-                                perm_batch: int = 0) -> dict:
-    """How ``residual_autocorr_perm`` covers B spots, D scored genes and P permutations over K neighbours
-    (gpz_residual_autocorr_perm_plan, a host-only query: no device needed): ``slab_genes`` and ``n_slabs`` as
-    ``residual_autocorr_plan`` gives them; ``perm_batch``, the permutations per launch as resolved (the caller's 1..32, or
-    the plan's choice, whose relabelled tables of 4 B K bytes each stay within 256 MiB); ``batches`` per slab;
-    ``partials_bytes``: the slab, plus O(perm_batch B K) table bytes, plus O(B / 256 x perm_batch x slab_genes) partial
-    sums.  ``P=0`` asks for what ``residual_spatial_stats`` needs: no tables, ``perm_batch`` = ``batches`` = 0."""
-    lib = _lib.load()
-    sg, ns, pb, nbat, nb = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
-    rc = lib.gpz_residual_autocorr_perm_plan(int(B), int(D), int(Lt), int(K), int(P), int(nnz), int(slab_genes), int(perm_batch),
-                                             C.byref(sg), C.byref(ns), C.byref(pb), C.byref(nbat), C.byref(nb))
-    if rc != 0:
-        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
-    return dict(slab_genes=sg.value, n_slabs=ns.value, perm_batch=pb.value, batches=nbat.value, partials_bytes=int(nb.value))
-
-
-def _residual_table(who, nbr, mean, slab_genes):
-    """The checks ``residual_morans_i`` makes on its table and ``slab_genes`` before any device work; returns K."""
-    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
-        raise ValueError(f"{who}: nbr must be a (B, K) integer table")
-    K = int(nbr.shape[1])
-    if not 1 <= K <= 32:
-        raise ValueError(f"{who}: K = {K} neighbours unsupported (1..32)")
-    if int(slab_genes) != slab_genes or int(slab_genes) < 0 or int(slab_genes) % 64:
-        raise ValueError(f"{who}: slab_genes = {slab_genes!r} is not a positive multiple of 64 (or 0: the plan's choice)")
-    if nbr.shape[0] != mean.shape[-1]:
-        raise ValueError(f"{who}: nbr {tuple(nbr.shape)} for {mean.shape[-1]} spots")
-    if K >= nbr.shape[0]:
-        raise ValueError(f"{who}: {K} neighbours of {nbr.shape[0]} spots (K < B needed)")
-    return K
-
-
-def residual_spatial_stats(mean, scale, W_pos, V_pos, y, nbr, theta_pos=None, genes=None, kind="pearson",
-                           lognormal_mean: bool = True, slab_genes: int = 0) -> dict:
-    """``residual_morans_i`` with Geary's C and the kurtosis beside I (gpz_residual_spatial_stats /
-    gpz_residual_spatial_stats_sparse): a dict of fp64 (G,) tensors ``I``, ``C``, ``residual_mean``, ``residual_var`` and
-    ``kurtosis`` (m4 / m2^2 of the residuals).  ``I``, ``residual_mean`` and ``residual_var`` are ``residual_morans_i``'s at
-    the same ``slab_genes``, bit for bit.  A bad table raises ValueError (checked on the device; one synchronisation)."""
-    who = "residual_spatial_stats"
-    K = _residual_table(who, nbr, mean, slab_genes)
-    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
-    lib = _lib.load()
-    dev, G = a["dev"], a["G"]
-    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
-    nb = residual_autocorr_perm_plan(a["B"], G, a["Lt"], K, 0, a["nnz"], int(slab_genes))["partials_bytes"]
-    out = [torch.empty(G, dtype=torch.float64, device=dev) for _ in range(5)]
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    tail = [a["Lt"], K, a["family"], a["kind"], int(bool(lognormal_mean)), int(slab_genes), *(_ptr(t) for t in out), _ptr(info)]
-    with torch.cuda.device(dev):
-        ws = _workspace(dev, nb)
-        if a["sparse"]:
-            entry = "gpz_residual_spatial_stats_sparse"
-            rc = lib.gpz_residual_spatial_stats_sparse(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], a["nnz"], G, *tail,
-                                                       _ptr(ws), ws.numel(), _stream(dev))
-        else:
-            entry = "gpz_residual_spatial_stats"
-            rc = lib.gpz_residual_spatial_stats(*_residual_inputs(a), _ptr(nbr), a["B"], a["D"], G, *tail, _ptr(ws), ws.numel(),
-                                                _stream(dev))
-    _lib.check(rc, entry)
-    if int(info.item()) != 0:
-        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
-    return dict(I=out[0], C=out[1], residual_mean=out[2], residual_var=out[3], kurtosis=out[4])
-
-
-def residual_autocorr_perm(mean, scale, W_pos, V_pos, y, nbr, perms, theta_pos=None, genes=None, kind="pearson",
-                           lognormal_mean: bool = True, *, stat: str = "moran", return_sims: bool = False, perm_batch: int = 0,
-                           slab_genes: int = 0):
-    """Moran's I (``stat="moran"``) or Geary's C (``"geary"``) of every gene's residuals (``residual_morans_i``'s
-    arguments) and of their P relabellings ``perms`` (P, B) integer, r^pi[n] = r[pi[n]], scored while each residual slab is
-    resident (gpz_residual_autocorr_perm / gpz_residual_autocorr_perm_sparse): per slab the residuals are formed once, the
-    observed statistics once, then every batch of ``perm_batch`` permutations (0: ``residual_autocorr_perm_plan``'s choice).
-    Returns (``AutocorrPerm``, moments): ``value`` is ``residual_spatial_stats``' I or C, bit for bit; ``n_ge`` / ``n_le``
-    compare the fp64 numerators (residuals are real-valued: a mathematical tie may fall either way in the last bit);
-    ``sim_mean`` / ``sim_m2`` are folded in permutation order, so nothing depends on ``perm_batch``; ``sims`` (G, P) with
-    ``return_sims``.  The moments are a dict of fp64 (G,) tensors ``residual_mean``, ``residual_var`` and ``kurtosis``.  A
-    bad table and a row of ``perms`` that is no permutation raise ValueError (checked on the device; one synchronisation)."""
-    who = "residual_autocorr_perm"
-    st = _stat(who, stat)
-    K = _residual_table(who, nbr, mean, slab_genes)
-    B = int(nbr.shape[0])
-    _perm_table_check(who, perms, B, perm_batch)
-    if perm_batch > 32:
-        raise ValueError(f"{who}: perm_batch = {perm_batch} unsupported (0 = chosen by the plan, at most 32)")
-    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind)
-    lib = _lib.load()
-    dev, G = a["dev"], a["G"]
-    nbr, _ = _nbr_table(who, nbr, B, dev)
-    perms = _perm_table(perms, B, dev)
-    P = int(perms.shape[0])
-    plan = residual_autocorr_perm_plan(B, G, a["Lt"], K, P, a["nnz"], int(slab_genes), perm_batch)
-    value, mean_, m2, rmean, rvar, kurt = (torch.empty(G, dtype=torch.float64, device=dev) for _ in range(6))
-    n_ge, n_le = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
-    sims = torch.empty((G, P), dtype=torch.float64, device=dev) if return_sims else None
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    tail = [a["Lt"], K, a["family"], a["kind"], int(bool(lognormal_mean)), int(slab_genes), P, st, plan["perm_batch"], _ptr(value),
-            _ptr(n_ge), _ptr(n_le), _ptr(mean_), _ptr(m2), _ptr(sims), _ptr(rmean), _ptr(rvar), _ptr(kurt), _ptr(info)]
-    with torch.cuda.device(dev):
-        ws = _workspace(dev, plan["partials_bytes"])
-        if a["sparse"]:
-            entry = "gpz_residual_autocorr_perm_sparse"
-            rc = lib.gpz_residual_autocorr_perm_sparse(*_residual_inputs(a), _ptr(nbr), _ptr(perms), B, a["D"], a["nnz"], G, *tail,
-                                                       _ptr(ws), ws.numel(), _stream(dev))
-        else:
-            entry = "gpz_residual_autocorr_perm"
-            rc = lib.gpz_residual_autocorr_perm(*_residual_inputs(a), _ptr(nbr), _ptr(perms), B, a["D"], G, *tail, _ptr(ws),
-                                                ws.numel(), _stream(dev))
-    _lib.check(rc, entry)
-    code = int(info.item())
-    if code == 1:
-        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
-    if code != 0:
-        raise ValueError(f"{who}: a row of perms is not a permutation of 0 .. B - 1 (an entry outside [0, B) or an index named twice)")
-    return AutocorrPerm(stat, value, n_ge, n_le, mean_, m2, sims), dict(residual_mean=rmean, residual_var=rvar, kurtosis=kurt)
-
-
-GAUSSIAN_RESIDUAL_KINDS = {"pearson": 0, "response": 1, "predictive": 2}
-
-
-def gaussian_residual_plan(B: int, D: int, Lt: int, K: int = 0, P: int = 0, nnz: int = 0, slab_genes: int = 0,
-                           perm_batch: int = 0) -> dict:
-    """How the Gaussian residual entries cover B spots, D scored genes, K neighbours and P permutations
-    (gpz_gaussian_residual_plan, a host-only query: no device needed): ``slab_genes``, ``n_slabs``, ``perm_batch``,
-    ``batches`` and ``partials_bytes`` as ``residual_autocorr_perm_plan`` gives them, with the residual pass's ``spot_slices``
-    and ``factors_padded``.  ``P=0``: what ``gaussian_residual_stats`` needs; ``K=0`` (with ``P=0``): what
-    ``gaussian_residuals`` needs, the factor scratch alone."""
-    lib = _lib.load()
-    sg, ns, nbat, nb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-    sn, fp, pb = C.c_int32(), C.c_int32(), C.c_int32()
-    rc = lib.gpz_gaussian_residual_plan(int(B), int(D), int(Lt), int(K), int(P), int(nnz), int(slab_genes), int(perm_batch),
-                                        C.byref(sg), C.byref(ns), C.byref(sn), C.byref(fp), C.byref(pb), C.byref(nbat), C.byref(nb))
-    if rc != 0:
-        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
-    return dict(slab_genes=sg.value, n_slabs=ns.value, spot_slices=sn.value, factors_padded=fp.value, perm_batch=pb.value,
-                batches=nbat.value, partials_bytes=int(nb.value))
+    a = _residual_model(who, _COUNT_RESIDUALS, sparse, mean, scale, y, (W_pos, V_pos, theta_pos), genes)
+    return dict(a, family=int(theta_pos is not None), kind=RESIDUAL_KINDS[kind], lognormal=int(bool(lognormal_mean)))
 
 
 def _gaussian_kind(who, kind):
@@ -2226,50 +2085,151 @@ def _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind):
     from .likelihoods import NOISE_SD_RANGE
     sparse = _gaussian_data(who, y)
     k = _gaussian_kind(who, kind)
-    if mean.dim() != 2:
-        raise ValueError(f"{who}: mean must be (Lt, B), got shape {tuple(mean.shape)}")
-    Lt, B = mean.shape
-    D = y.shape[0]
-    if tuple(y.shape) != (D, B) or scale.shape != (Lt, B) or W.shape != (D, Lt) or b.shape != (D,) or noise_sd.shape != (D,):
-        raise ValueError(f"{who}: y {tuple(y.shape)}, mean {tuple(mean.shape)}, scale {tuple(scale.shape)}, W {tuple(W.shape)}, "
-                         f"b {tuple(b.shape)}, noise_sd {tuple(noise_sd.shape)} do not fit together")
-    g = None
-    if genes is not None:
-        g = genes.detach() if isinstance(genes, torch.Tensor) else torch.as_tensor(genes)
-        if g.dim() != 1 or g.numel() < 1 or g.is_floating_point() or g.dtype == torch.bool:
-            raise ValueError(f"{who}: genes must be a non-empty 1-D list of gene indices")
-        if bool(((g < 0) | (g >= D)).any()):
-            raise IndexError(f"{who}: a gene index lies outside [0, {D})")
-    _need_cuda(mean, scale, W, b, noise_sd, None if sparse else y)
-    dev = _same_device(mean, scale, W, b, noise_sd, None if sparse else y)
-    if sparse and y.device != dev:
-        raise RuntimeError(f"gpzoo_amd: the expression lives on {y.device}, the model on {dev}: move it with expr.to(device)")
-    f32 = torch.float32
-    mean, scale, W, b, noise_sd = (t.detach().to(f32).contiguous() for t in (mean, scale, W, b, noise_sd))
+    a = _residual_model(who, _GAUSSIAN_RESIDUALS, sparse, mean, scale, y, (W, b, noise_sd), genes)
     lo, hi = NOISE_SD_RANGE
-    if not bool(((noise_sd >= lo) & (noise_sd <= hi)).all()):
+    if not bool(((a["noise_sd"] >= lo) & (a["noise_sd"] <= hi)).all()):
         raise ValueError(f"{who}: noise_sd must lie in [{lo:g}, {hi:g}] (likelihoods.NOISE_SD_RANGE), positive and finite")
-    if not sparse:
-        y = y.detach().to(f32).contiguous()
-    if g is not None:
-        g = g.to(device=dev, dtype=torch.int32).contiguous()
-    G = D if g is None else int(g.numel())
-    return dict(mean=mean, scale=scale, W=W, b=b, noise_sd=noise_sd, y=y, genes=g, sparse=sparse, dev=dev, B=B, D=D, G=G, Lt=Lt,
-                nnz=y.nnz if sparse else 0, kind=k)
+    return dict(a, kind=k)
 
 
-def _gaussian_residual_inputs(a):
-    """The leading pointer arguments of the Gaussian residual entries."""
-    head = [_ptr(a[k]) for k in ("mean", "scale", "W", "b", "noise_sd")]
-    y = a["y"]
+def _residual_table(who, nbr, mean, slab_genes):
+    """The checks ``residual_morans_i`` makes on its table and ``slab_genes`` before any device work; returns K."""
+    if not isinstance(nbr, torch.Tensor) or nbr.dim() != 2 or nbr.dtype.is_floating_point or nbr.dtype == torch.bool:
+        raise ValueError(f"{who}: nbr must be a (B, K) integer table")
+    K = int(nbr.shape[1])
+    if not 1 <= K <= 32:
+        raise ValueError(f"{who}: K = {K} neighbours unsupported (1..32)")
+    if int(slab_genes) != slab_genes or int(slab_genes) < 0 or int(slab_genes) % 64:
+        raise ValueError(f"{who}: slab_genes = {slab_genes!r} is not a positive multiple of 64 (or 0: the plan's choice)")
+    if nbr.shape[0] != mean.shape[-1]:
+        raise ValueError(f"{who}: nbr {tuple(nbr.shape)} for {mean.shape[-1]} spots")
+    if K >= nbr.shape[0]:
+        raise ValueError(f"{who}: {K} neighbours of {nbr.shape[0]} spots (K < B needed)")
+    return K
+
+
+def _residual_perms(who, nbr, perms, perm_batch):
+    """The checks the permutation entries make on ``perms`` and ``perm_batch`` before any device work."""
+    _perm_table_check(who, perms, int(nbr.shape[0]), perm_batch)
+    if perm_batch > 32:
+        raise ValueError(f"{who}: perm_batch = {perm_batch} unsupported (0 = chosen by the plan, at most 32)")
+
+
+_WIDE_KEYS = ("I", "C", "residual_mean", "residual_var", "kurtosis")
+
+
+def _residual_run(fam, who, stage, a, nbr=None, K=0, slab_genes=0, perms=None, stat=0, perm_batch=0, return_sims=False):
+    """One residual entry of the family ``fam`` on its checked arguments ``a``.  ``stage`` and what is returned: "residuals",
+    the (B, G) fp32 array; "morans_i", [I, mean, variance]; "stats", [I, C, mean, variance, kurtosis]; "perm", [value, n_ge,
+    n_le, sim_mean, sim_m2, sims or None, mean, variance, kurtosis].  A table or a permutation that the device refused raises
+    ValueError (one synchronisation)."""
+    lib = _lib.load()
+    dev, B, G = a["dev"], a["B"], a["G"]
+    tables = [] if nbr is None else [nbr.to(device=dev, dtype=torch.int64).contiguous()]
+    if stage == "perm":
+        tables.append(_perm_table(perms, B, dev))
+    P = int(tables[1].shape[0]) if stage == "perm" else 0
+    plan = fam.plan(stage, B, G, a["Lt"], K, P, a["nnz"], int(slab_genes), perm_batch)
+    f64 = lambda n: [torch.empty(G, dtype=torch.float64, device=dev) for _ in range(n)]  # noqa: E731
+    scalars = [a["Lt"], *(a[k] for k in fam.scalars)]
+    if stage == "residuals":
+        out = [torch.empty((B, G), dtype=torch.float32, device=dev)]
+        outputs = [_ptr(out[0])]
+    else:
+        scalars[1:1] = [K]
+        if stage == "perm":
+            value, sim_mean, sim_m2, *moments = f64(6)
+            n_ge, n_le = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
+            sims = torch.empty((G, P), dtype=torch.float64, device=dev) if return_sims else None
+            out = [value, n_ge, n_le, sim_mean, sim_m2, sims, *moments]
+            scalars += [int(slab_genes), P, stat, plan["perm_batch"]]
+        else:
+            out = f64(3 if stage == "morans_i" else 5)
+            scalars += [int(slab_genes)]
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+        outputs = [_ptr(t) for t in (*out, info)]
     if a["sparse"]:
-        v = y.values
-        return head + [_ptr(y.offset), _ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val), _ptr(a["genes"])]
-    return head + [_ptr(y), _ptr(a["genes"])]
+        ahead, rows = fam.stored(a["y"])
+        data = ahead + [_ptr(rows.row_ptr), _ptr(rows.row_spot), _ptr(rows.row_perm), _ptr(rows.col_val)]
+        extents = [B, a["D"], a["nnz"], G]
+    else:
+        data, extents = [_ptr(a["y"])], [B, a["D"], G]
+    entry = fam.stems[stage] + ("_sparse" if a["sparse"] else "")
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, plan["partials_bytes"])
+        rc = getattr(lib, entry)(*(_ptr(a[k]) for k in ("mean", "scale", *fam.params)), *data, _ptr(a["genes"]),
+                                 *(_ptr(t) for t in tables), *extents, *scalars, *outputs, _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, entry)
+    if stage == "residuals":
+        return out[0]
+    code = int(info.item())
+    if code == 1 or (code != 0 and stage != "perm"):
+        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
+    if code != 0:
+        raise ValueError(f"{who}: a row of perms is not a permutation of 0 .. B - 1 (an entry outside [0, B) or an index named twice)")
+    return out
 
 
-def _gaussian_extents(a):
-    return [a["B"], a["D"], a["nnz"], a["G"]] if a["sparse"] else [a["B"], a["D"], a["G"]]
+def _perm_result(stat, out):
+    """(``AutocorrPerm``, moments) of the "perm" stage's outputs."""
+    return AutocorrPerm(stat, *out[:6]), dict(zip(_WIDE_KEYS[2:], out[6:]))
+
+
+def count_residuals(mean, scale, W_pos, V_pos, y, theta_pos=None, genes=None, kind="pearson", lognormal_mean: bool = True):
+    """(B, G) fp32 residuals, spot-major, of the counts under the predictive mean rate mu = V W m of ``poisson_deviance``
+    (gpz_count_residuals / gpz_count_residuals_sparse).  ``kind="pearson"``: (y - mu) / sqrt(mu (1 + mu / theta));
+    ``"deviance"``: sign(y - mu) sqrt(unit deviance).  ``theta_pos`` (D,) selects the negative binomial, None the Poisson
+    family.  ``genes``: a list of gene indices in any order, repeats allowed (column g is gene ``genes[g]``), or None for all.
+    ``y``: dense (D, B), or a whole ``SparseCounts`` (the same bits as on its dense array)."""
+    who = "count_residuals"
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind, lognormal_mean)
+    return _residual_run(_COUNT_RESIDUALS, who, "residuals", a)
+
+
+def residual_morans_i(mean, scale, W_pos, V_pos, y, nbr, theta_pos=None, genes=None, kind="pearson",
+                      lognormal_mean: bool = True, slab_genes: int = 0) -> dict:
+    """Moran's I of every gene's residuals (``count_residuals``' arguments) over the neighbour table nbr (B, K) int64 of
+    distinct neighbours, 1 <= K <= 32, with weights 1 / K (gpz_residual_morans_i / gpz_residual_morans_i_sparse): a dict of
+    fp64 (G,) tensors ``I``, ``residual_mean`` and ``residual_var`` (sum z^2 / B).  The genes are taken in slabs of
+    ``slab_genes`` columns (0: ``residual_autocorr_plan``'s choice); neither the (D, B) rate nor the (D, B) residuals exist.
+    Sums in a fixed order: repeated calls agree bit for bit.  A table entry outside [0, B) or naming its own row raises
+    ValueError (checked on the device; one synchronisation)."""
+    who = "residual_morans_i"
+    K = _residual_table(who, nbr, mean, slab_genes)
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind, lognormal_mean)
+    return dict(zip(("I", "residual_mean", "residual_var"), _residual_run(_COUNT_RESIDUALS, who, "morans_i", a, nbr, K, slab_genes)))
+
+
+def residual_spatial_stats(mean, scale, W_pos, V_pos, y, nbr, theta_pos=None, genes=None, kind="pearson",
+                           lognormal_mean: bool = True, slab_genes: int = 0) -> dict:
+    """``residual_morans_i`` with Geary's C and the kurtosis beside I (gpz_residual_spatial_stats /
+    gpz_residual_spatial_stats_sparse): a dict of fp64 (G,) tensors ``I``, ``C``, ``residual_mean``, ``residual_var`` and
+    ``kurtosis`` (m4 / m2^2 of the residuals).  ``I``, ``residual_mean`` and ``residual_var`` are ``residual_morans_i``'s at
+    the same ``slab_genes``, bit for bit.  A bad table raises ValueError (checked on the device; one synchronisation)."""
+    who = "residual_spatial_stats"
+    K = _residual_table(who, nbr, mean, slab_genes)
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind, lognormal_mean)
+    return dict(zip(_WIDE_KEYS, _residual_run(_COUNT_RESIDUALS, who, "stats", a, nbr, K, slab_genes)))
+
+
+def residual_autocorr_perm(mean, scale, W_pos, V_pos, y, nbr, perms, theta_pos=None, genes=None, kind="pearson",
+                           lognormal_mean: bool = True, *, stat: str = "moran", return_sims: bool = False, perm_batch: int = 0,
+                           slab_genes: int = 0):
+    """Moran's I (``stat="moran"``) or Geary's C (``"geary"``) of every gene's residuals (``residual_morans_i``'s
+    arguments) and of their P relabellings ``perms`` (P, B) integer, r^pi[n] = r[pi[n]], scored while each residual slab is
+    resident (gpz_residual_autocorr_perm / gpz_residual_autocorr_perm_sparse): per slab the residuals are formed once, the
+    observed statistics once, then every batch of ``perm_batch`` permutations (0: ``residual_autocorr_perm_plan``'s choice).
+    Returns (``AutocorrPerm``, moments): ``value`` is ``residual_spatial_stats``' I or C, bit for bit; ``n_ge`` / ``n_le``
+    compare the fp64 numerators (residuals are real-valued: a mathematical tie may fall either way in the last bit);
+    ``sim_mean`` / ``sim_m2`` are folded in permutation order, so nothing depends on ``perm_batch``; ``sims`` (G, P) with
+    ``return_sims``.  The moments are a dict of fp64 (G,) tensors ``residual_mean``, ``residual_var`` and ``kurtosis``.  A
+    bad table and a row of ``perms`` that is no permutation raise ValueError (checked on the device; one synchronisation)."""
+    who = "residual_autocorr_perm"
+    st = _stat(who, stat)
+    K = _residual_table(who, nbr, mean, slab_genes)
+    _residual_perms(who, nbr, perms, perm_batch)
+    a = _residual_args(who, mean, scale, W_pos, V_pos, y, theta_pos, genes, kind, lognormal_mean)
+    return _perm_result(stat, _residual_run(_COUNT_RESIDUALS, who, "perm", a, nbr, K, slab_genes, perms, st, perm_batch, return_sims))
 
 
 def gaussian_residuals(mean, scale, W, b, noise_sd, y, genes=None, kind="pearson"):
@@ -2281,16 +2241,7 @@ def gaussian_residuals(mean, scale, W, b, noise_sd, y, genes=None, kind="pearson
     ``SparseExpression`` (the same bits as on ``y.to_dense()``)."""
     who = "gaussian_residuals"
     a = _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind)
-    lib = _lib.load()
-    nb = gaussian_residual_plan(a["B"], a["G"], a["Lt"], 0, 0, a["nnz"])["partials_bytes"]
-    out = torch.empty((a["B"], a["G"]), dtype=torch.float32, device=a["dev"])
-    entry = lib.gpz_gaussian_residuals_sparse if a["sparse"] else lib.gpz_gaussian_residuals
-    with torch.cuda.device(a["dev"]):
-        ws = _workspace(a["dev"], nb)
-        rc = entry(*_gaussian_residual_inputs(a), *_gaussian_extents(a), a["Lt"], a["kind"], _ptr(out), _ptr(ws), ws.numel(),
-                   _stream(a["dev"]))
-    _lib.check(rc, "gpz_gaussian_residuals")
-    return out
+    return _residual_run(_GAUSSIAN_RESIDUALS, who, "residuals", a)
 
 
 def gaussian_residual_stats(mean, scale, W, b, noise_sd, y, nbr, genes=None, kind="pearson", slab_genes: int = 0) -> dict:
@@ -2303,21 +2254,7 @@ def gaussian_residual_stats(mean, scale, W, b, noise_sd, y, nbr, genes=None, kin
     who = "gaussian_residual_stats"
     K = _residual_table(who, nbr, mean, slab_genes)
     a = _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind)
-    lib = _lib.load()
-    dev, G = a["dev"], a["G"]
-    nbr = nbr.to(device=dev, dtype=torch.int64).contiguous()
-    nb = gaussian_residual_plan(a["B"], G, a["Lt"], K, 0, a["nnz"], int(slab_genes))["partials_bytes"]
-    out = [torch.empty(G, dtype=torch.float64, device=dev) for _ in range(5)]
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    name = "gpz_gaussian_residual_stats_sparse" if a["sparse"] else "gpz_gaussian_residual_stats"
-    with torch.cuda.device(dev):
-        ws = _workspace(dev, nb)
-        rc = getattr(lib, name)(*_gaussian_residual_inputs(a), _ptr(nbr), *_gaussian_extents(a), a["Lt"], K, a["kind"],
-                                int(slab_genes), *(_ptr(t) for t in out), _ptr(info), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(rc, name)
-    if int(info.item()) != 0:
-        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
-    return dict(I=out[0], C=out[1], residual_mean=out[2], residual_var=out[3], kurtosis=out[4])
+    return dict(zip(_WIDE_KEYS, _residual_run(_GAUSSIAN_RESIDUALS, who, "stats", a, nbr, K, slab_genes)))
 
 
 def gaussian_residual_autocorr_perm(mean, scale, W, b, noise_sd, y, nbr, perms, genes=None, kind="pearson", *, stat: str = "moran",
@@ -2329,35 +2266,9 @@ def gaussian_residual_autocorr_perm(mean, scale, W, b, noise_sd, y, nbr, perms, 
     who = "gaussian_residual_autocorr_perm"
     st = _stat(who, stat)
     K = _residual_table(who, nbr, mean, slab_genes)
-    B = int(nbr.shape[0])
-    _perm_table_check(who, perms, B, perm_batch)
-    if perm_batch > 32:
-        raise ValueError(f"{who}: perm_batch = {perm_batch} unsupported (0 = chosen by the plan, at most 32)")
+    _residual_perms(who, nbr, perms, perm_batch)
     a = _gaussian_residual_args(who, mean, scale, W, b, noise_sd, y, genes, kind)
-    lib = _lib.load()
-    dev, G = a["dev"], a["G"]
-    nbr, _ = _nbr_table(who, nbr, B, dev)
-    perms = _perm_table(perms, B, dev)
-    P = int(perms.shape[0])
-    plan = gaussian_residual_plan(B, G, a["Lt"], K, P, a["nnz"], int(slab_genes), perm_batch)
-    value, mean_, m2, rmean, rvar, kurt = (torch.empty(G, dtype=torch.float64, device=dev) for _ in range(6))
-    n_ge, n_le = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
-    sims = torch.empty((G, P), dtype=torch.float64, device=dev) if return_sims else None
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    name = "gpz_gaussian_residual_perm_sparse" if a["sparse"] else "gpz_gaussian_residual_perm"
-    with torch.cuda.device(dev):
-        ws = _workspace(dev, plan["partials_bytes"])
-        rc = getattr(lib, name)(*_gaussian_residual_inputs(a), _ptr(nbr), _ptr(perms), *_gaussian_extents(a), a["Lt"], K, a["kind"],
-                                int(slab_genes), P, st, plan["perm_batch"], _ptr(value), _ptr(n_ge), _ptr(n_le), _ptr(mean_),
-                                _ptr(m2), _ptr(sims), _ptr(rmean), _ptr(rvar), _ptr(kurt), _ptr(info), _ptr(ws), ws.numel(),
-                                _stream(dev))
-    _lib.check(rc, name)
-    code = int(info.item())
-    if code == 1:
-        raise ValueError(f"{who}: the neighbour table has an entry outside [0, B) or naming its own row")
-    if code != 0:
-        raise ValueError(f"{who}: a row of perms is not a permutation of 0 .. B - 1 (an entry outside [0, B) or an index named twice)")
-    return AutocorrPerm(stat, value, n_ge, n_le, mean_, m2, sims), dict(residual_mean=rmean, residual_var=rvar, kurtosis=kurt)
+    return _perm_result(stat, _residual_run(_GAUSSIAN_RESIDUALS, who, "perm", a, nbr, K, slab_genes, perms, st, perm_batch, return_sims))
 
 
 def poisson_nsf_sparse_plan(N: int, B: int, D: int, Lt: int, E: int, nnz: int) -> dict:
