@@ -7,13 +7,15 @@ on synthetic counts, against the same model started from mu = 0 and random loadi
 
     PYTHONPATH=. python examples/nsf_init_chain.py [--spots 20000 --genes 500 --factors 6 --inducing 500 --steps 30
                                                    --inducing-from {subset,kmeans} --mu-from {smooth,projection}
-                                                   --sparse-counts DENSITY [--select-genes NFEAT --rank-by {deviance,moran,geary}]
+                                                   --sparse-counts DENSITY [--select-genes NFEAT --rank-by {deviance,moran,geary,gp}]
                                                    [--moran-perms P]]
 
 ``--sparse-counts DENSITY`` thins the counts to about that fraction of non-zeros and runs the whole chain on them as a
 ``SparseCounts``: the size factors and the NMF start from ``counts.T``, the fit from ``counts``.  The dense count array
 then never reaches the device.  ``--select-genes NFEAT`` ranks the genes of those counts first (``rank_genes``: Poisson deviance
-against a constant-rate null, or Moran's I / 1 - Geary's C of the log-normalised counts over the spots' 6-neighbour graph) and runs the chain
+against a constant-rate null, Moran's I / 1 - Geary's C of the log-normalised counts over the spots' 6-neighbour graph, or the
+sparse-GP likelihood ratio of ``gene_spatial_gp``, which also prints the median length scale it selects beside the one the
+model's kernel starts from) and runs the chain
 on the NFEAT best (``counts.select_genes``) -- the reference's ``ad[:, :nfeat]`` of genes sorted by importance.  The size
 factors stay those of the whole data set.  ``--moran-perms P`` then scores the genes that are left with Moran's I under P
 random relabellings of the spots (``gene_autocorr(..., n_perms=P)``) and prints how many have a Benjamini-Hochberg adjusted
@@ -28,7 +30,7 @@ import torch.nn as nn
 from gpzoo.gp import SVGP
 from gpzoo.kernels import NSF_RBF
 from gpzoo.likelihoods import NSF2, SparseCounts
-from gpzoo.utilities import (fdr_bh, gene_autocorr, init_softplus, kmeans_inducing_points, log_normalize,
+from gpzoo.utilities import (fdr_bh, gene_autocorr, gene_spatial_gp, init_softplus, kmeans_inducing_points, log_normalize,
                              project_factors_to_inducing, regularized_nmf, rank_genes, rescale_spatial_coords, scanpy_sizefactors,
                              smooth_spatial_factors, train)
 
@@ -70,7 +72,7 @@ def main():
                     help="keep about this fraction of the counts as non-zeros and run the chain through SparseCounts")
     ap.add_argument("--select-genes", "--select_genes", type=int, default=None, metavar="NFEAT",
                     help="with --sparse-counts: rank the genes and keep the NFEAT best before the NMF start")
-    ap.add_argument("--rank-by", "--rank_by", choices=("deviance", "moran", "geary"), default="deviance",
+    ap.add_argument("--rank-by", "--rank_by", choices=("deviance", "moran", "geary", "gp"), default="deviance",
                     help="the score --select-genes ranks by (rank_genes)")
     ap.add_argument("--moran-perms", "--moran_perms", type=int, default=None, metavar="P",
                     help="with --sparse-counts: Moran's I of the genes under P relabellings of the spots, and how many genes "
@@ -94,8 +96,13 @@ def main():
         sz = scanpy_sizefactors(Y.T)
         sz = np.maximum(sz, sz[sz > 0].min())           # a spot thinned to nothing says nothing about its depth; log(sz) stays finite
         if a.select_genes is not None:
-            order, score = rank_genes(Y, by=a.rank_by, coords=X if a.rank_by in ("moran", "geary") else None, nfeat=a.select_genes)
+            order, score = rank_genes(Y, by=a.rank_by, coords=X if a.rank_by in ("moran", "geary", "gp") else None, nfeat=a.select_genes)
             Y = Y.select_genes(order)
+            if a.rank_by == "gp":
+                fit = gene_spatial_gp(log_normalize(Y), X, inducing=min(256, a.spots))
+                print(f"sparse-GP length scale of the selected genes: median {float(fit.lengthscale.nanmedian()):.3g} (grid "
+                      f"{float(fit.lengthscales[0]):.3g} .. {float(fit.lengthscales[-1]):.3g}), median fraction of spatial variance "
+                      f"{float(fit.fsv.nanmedian()):.3g}; the model's kernel starts at lengthscale 0.4")
             print(f"selected {Y.shape[0]} of {a.genes} genes by {a.rank_by}: score {float(score[0]):.4g} ... {float(score[-1]):.4g}, "
                   f"{Y.nnz} non-zeros kept")
         if a.moran_perms is not None:

@@ -126,6 +126,13 @@ _SIGNATURES = {
                                                   C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "gpz_gene_dispersion_sparse": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] * 3 + [C.c_double, C.c_double, C.c_int32] +
                                    [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gpz_gene_kernel_project_sparse_plan": (C.c_int, [C.c_int64] * 4 + [C.c_int32] + [C.POINTER(C.c_int32)] * 3 +
+                                            [C.POINTER(C.c_int64)]),
+    "gpz_gene_kernel_project_sparse": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] * 4 + [C.c_int32] * 4 + [C.c_void_p] * 2 +
+                                       [C.c_size_t, C.c_void_p]),
+    "gpz_gene_gp_profile_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "gpz_gene_gp_profile": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 3 + [C.c_int32, C.c_double, C.c_double] + [C.c_void_p] * 7),
     "gpz_residual_morans_i_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
                                              C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 5 + [C.POINTER(C.c_int64)]),
     "gpz_count_residuals": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 2 +

@@ -14,7 +14,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgpzoo_hip.so")
-SOURCES = ["runtime.hip", "kfill.hip", "gemm.hip", "gemmw.hip", "gemmp.hip", "diag128.hip", "coop.hip", "factor.hip", "kgrad.hip", "mmops.hip", "poisson.hip", "svgp.hip", "vnngp.hip", "collective.hip", "spatial.hip", "nmf.hip", "smooth.hip", "kmeans.hip", "gram.hip", "poisson_sparse.hip", "nmf_sparse.hip", "deviance.hip", "nb.hip", "nb_sparse.hip", "nb_deviance.hip", "gaussian.hip", "gaussian_sparse.hip", "gene_rank.hip", "gene_dispersion.hip", "residual.hip", "moran_perm.hip", "spatial_stats.hip"]
+SOURCES = ["runtime.hip", "kfill.hip", "gemm.hip", "gemmw.hip", "gemmp.hip", "diag128.hip", "coop.hip", "factor.hip", "kgrad.hip", "mmops.hip", "poisson.hip", "svgp.hip", "vnngp.hip", "collective.hip", "spatial.hip", "nmf.hip", "smooth.hip", "kmeans.hip", "gram.hip", "poisson_sparse.hip", "nmf_sparse.hip", "deviance.hip", "nb.hip", "nb_sparse.hip", "nb_deviance.hip", "gaussian.hip", "gaussian_sparse.hip", "gene_rank.hip", "gene_dispersion.hip", "gene_gp.hip", "residual.hip", "moran_perm.hip", "spatial_stats.hip"]
 HEADERS = ["common.h", "vec.h", "sparse_rows.h", "gene_rows.h", "moran_expr.h", "nb_passes.h", "moran_pass.h", "residual_gaussian.h", "gemm.h", "cov.h", "gemmw.h", "gemmp.h", "diag128.h", "factor.h", "kgrad.h", "mmops.h", os.path.join("..", "..", "include", "gpzoo_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
 # per source, after FLAGS: the kNN distances of spatial.hip and smooth.hip, and the k-means distances of kmeans.hip, are
@@ -24,9 +24,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # multiply-adds out, so that one element-wise function gives the same bits in the dense and in the sparse kernel (the Gaussian
 # residual pass of residual_gaussian.h, which it includes, relies on the same); moran_perm.hip
 # and spatial_stats.hip instantiate gene_rank.hip's gene pass (moran_expr.h) and have to give its bits; spatial_stats.hip also
-# holds the column pass of Moran's I, whose bits do not depend on what is computed beside it
+# holds the column pass of Moran's I, whose bits do not depend on what is computed beside it; the sums of gene_gp.hip are the
+# sequential sums of separately rounded products its numpy oracle emulates (its covariance expressions, cov.h's CovF64, write
+# their fused multiply-adds out, so they stay the bits of gram.hip)
 SOURCE_FLAGS = {"spatial.hip": ["-ffp-contract=off"], "smooth.hip": ["-ffp-contract=off"], "kmeans.hip": ["-ffp-contract=off"],
                 "gene_rank.hip": ["-ffp-contract=off"], "gene_dispersion.hip": ["-ffp-contract=off"],
+                "gene_gp.hip": ["-ffp-contract=off"],
                 "residual.hip": ["-ffp-contract=off"], "moran_perm.hip": ["-ffp-contract=off"],
                 "spatial_stats.hip": ["-ffp-contract=off"]}
 

@@ -73,4 +73,30 @@ __device__ __forceinline__ float cov_value(float s, float amp, float c0, float c
   return amp * __builtin_amdgcn_exp2f(c0 * s);                   // sigma^2 exp(-d^2 / (2 ell^2))
 }
 
+// fp64 covariance of UNIT amplitude of one (point, point) pair, for the per-gene projection (gene_gp.hip): the operations of
+// gram.hip's GramCov<double, KIND> in its order, so that with sigma = 1 (amp = 1 multiplies exactly) both generate the same
+// bits -- the collapsed bound of gene_gp.hip needs K_zx y and K_zx K_xz to come from one K_zx.  coef() is the per-latent
+// constant, radial() the part that does not depend on the latent (d^2 for RBF, r = sqrt(d^2) for the Matern kinds; unused
+// coordinates are 0 on both sides), unit() the covariance at it.  Every fused multiply-add is written out, so the bits do not
+// depend on the contraction setting of the file that includes this.
+template <int KIND> struct CovF64 {
+  static __device__ __forceinline__ double coef(double e) {
+    return (KIND == 1) ? 1.7320508075688772935 / e : (KIND == 4) ? 1.0 / e : (KIND == 5) ? 2.2360679774997896964 / e : -0.5 / (e * e);
+  }
+  static __device__ __forceinline__ double radial(const double* z, const double* x, bool low_d) {
+    double acc = 0.0;
+    const int nd = low_d ? 2 : 4;
+    for (int k = 0; k < nd; ++k) { const double df = z[k] - x[k]; acc = fma(df, df, acc); }
+    return KIND == 0 ? acc : sqrt(acc);
+  }
+  static __device__ __forceinline__ double unit(double cf, double rad) {
+    if (KIND == 0) return exp(cf * rad);
+    const double t = cf * rad;
+    if (KIND == 4) return exp(-t);
+    const double lin = fma(cf, rad, 1.0);          // gram.hip's 1.0 + t, which its -ffp-contract=fast fuses with t = cf * rad
+    if (KIND == 1) return lin * exp(-t);
+    return (lin + t * t / 3.0) * exp(-t);
+  }
+};
+
 }  // namespace gpz

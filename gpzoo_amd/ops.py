@@ -1918,6 +1918,130 @@ def gene_dispersion_sparse(counts, size, theta_min: float = 1e-4, theta_max: flo
     return tuple(out)
 
 
+GENE_GP_KINDS = {"rbf": _lib.KERNEL_RBF, "matern12": _lib.KERNEL_MATERN12, "matern32": _lib.KERNEL_MATERN32,
+                 "matern52": _lib.KERNEL_MATERN52}
+
+
+def gene_kernel_project_plan(N: int, D: int, nnz: int, M: int, n_ell: int) -> dict:
+    """How ``gene_kernel_project_sparse`` covers a shape (gpz_gene_kernel_project_sparse_plan, a host-only query: no device
+    needed): ``gene_chunk`` (a gene row longer than this many stored entries is cut into chunks of that many, whose sums
+    are folded in order), ``workgroups`` (along the genes), ``generate`` (True while generating the covariances in the
+    kernel is the faster way; above 290 N stored entries ``gene_kernel_project_gather`` is), ``partials_bytes``."""
+    lib = _lib.load()
+    gc, wg, gen, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    if lib.gpz_gene_kernel_project_sparse_plan(int(N), int(D), int(nnz), int(M), int(n_ell), C.byref(gc), C.byref(wg),
+                                               C.byref(gen), C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(gene_chunk=gc.value, workgroups=wg.value, generate=bool(gen.value), partials_bytes=int(nb.value))
+
+
+def _gene_gp_kind(who, kernel):
+    if kernel not in GENE_GP_KINDS:
+        raise ValueError(f"{who}: kernel {kernel!r} unknown ({', '.join(repr(k) for k in GENE_GP_KINDS)})")
+    return GENE_GP_KINDS[kernel]
+
+
+def gene_kernel_project_sparse(values, coords, Z, lengthscales, kernel: str = "rbf", *, workgroups: int = 0, partials=None):
+    """``out[l, g, m] = sum_{stored (g, n)} v_gn k_l(z_m, x_n)``, fp64 (n_ell, D, M): K_zx Y^T of every gene of a whole
+    ``SparseCounts`` / ``SparseExpression`` (its stored values; the offset is the caller's) for the unit-variance ``kernel``
+    ("rbf", "matern12", "matern32", "matern52") at every length scale (gpz_gene_kernel_project_sparse).  ``coords`` (N, d),
+    ``Z`` (M, d), ``lengthscales`` (n_ell,) fp64 tensors on the values' device; d <= 4, M <= 1024, n_ell <= 16.  The
+    covariances are generated in the kernel and never stored.  ``workgroups`` (0: the plan's) does not change a bit of the
+    result.  ``partials``: a uint8 scratch tensor of the plan's ``partials_bytes`` to use in place of the shared one."""
+    who = "gene_kernel_project_sparse"
+    kind = _gene_gp_kind(who, kernel)
+    v = _whole_values(values, who)
+    D, N = v.shape
+    for name, t in (("coords", coords), ("Z", Z), ("lengthscales", lengthscales)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"{who}: {name} must be a float64 tensor")
+    if coords.dim() != 2 or Z.dim() != 2 or lengthscales.dim() != 1 or coords.shape[0] != N or Z.shape[1] != coords.shape[1]:
+        raise ValueError(f"{who}: coords ({N}, d), Z (M, d) and lengthscales (n_ell,) expected, got {tuple(coords.shape)}, "
+                         f"{tuple(Z.shape)} and {tuple(lengthscales.shape)}")
+    _need_cuda(v.col_val)
+    dev = v.device
+    for name, t in (("coords", coords), ("Z", Z), ("lengthscales", lengthscales)):
+        if t.device != dev:
+            raise RuntimeError(f"gpzoo_amd: the values live on {dev}, {name} on {t.device}")
+    X, Zc, ell = coords.detach().contiguous(), Z.detach().contiguous(), lengthscales.detach().contiguous()
+    M, d, nl = int(Zc.shape[0]), int(Zc.shape[1]), int(ell.numel())
+    lib = _lib.load()
+    nb = C.c_int64()
+    if lib.gpz_gene_kernel_project_sparse_plan(N, D, v.nnz, M, nl, None, None, None, C.byref(nb)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    out = torch.empty((nl, D, M), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nb.value) if partials is None else partials
+        rc = lib.gpz_gene_kernel_project_sparse(_ptr(v.row_ptr), _ptr(v.row_spot), _ptr(v.row_perm), _ptr(v.col_val), _ptr(X),
+                                                _ptr(Zc), _ptr(ell), N, D, v.nnz, M, d, nl, kind, int(workgroups), _ptr(out),
+                                                _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(rc, "gpz_gene_kernel_project_sparse")
+    return out
+
+
+def gene_kernel_project_gather(values, coords, Z, lengthscales, kernel: str = "rbf"):
+    """What ``gene_kernel_project_sparse`` computes, composed from a stored K_xz: per length scale ``kfill`` of the fp64
+    (N, M) covariance and ``counts_matmul`` of the stored values with it in column blocks of 128.  It allocates N x M x 8
+    bytes at a time and adds in ``counts_matmul``'s order; above the density where the plan's ``generate`` turns False it
+    is the faster of the two (one multiply-add per gathered covariance instead of an exp)."""
+    who = "gene_kernel_project_gather"
+    kind = _gene_gp_kind(who, kernel)
+    v = _whole_values(values, who)
+    _need_cuda(v.col_val)
+    D = v.shape[0]
+    X, Zc, ell = coords.detach().contiguous(), Z.detach().contiguous(), lengthscales.detach().contiguous()
+    M, nl = int(Zc.shape[0]), int(ell.numel())
+    out = torch.empty((nl, D, M), dtype=torch.float64, device=v.device)
+    one = torch.ones(1, dtype=torch.float64, device=v.device)
+    for l in range(nl):
+        Kxz = kfill(KernelSpec(kind, one, ell[l:l + 1], False), X, Zc)
+        for m0 in range(0, M, 128):
+            out[l, :, m0:m0 + 128] = counts_matmul(v, Kxz[:, m0:m0 + 128].contiguous(), transpose=True)
+    return out
+
+
+def gene_gp_profile_plan(D: int, M: int, n_ell: int) -> dict:
+    """How ``gene_gp_profile`` maximises (gpz_gene_gp_profile_plan, a host-only query): ``grid_points`` (values of log
+    delta the bound is evaluated at first), ``workgroups``, ``tol_t`` (the refinement stops at a step or bracket of this
+    size in log delta), ``max_iter``."""
+    lib = _lib.load()
+    gp, wg, tol, mi = C.c_int32(), C.c_int32(), C.c_double(), C.c_int32()
+    if lib.gpz_gene_gp_profile_plan(int(D), int(M), int(n_ell), C.byref(gp), C.byref(wg), C.byref(tol), C.byref(mi)) != 0:
+        raise ValueError(lib.gpz_last_error().decode("utf-8", "replace"))
+    return dict(grid_points=gp.value, workgroups=wg.value, tol_t=tol.value, max_iter=mi.value)
+
+
+def gene_gp_profile(p, lam, yty, N: int, delta_min: float = 1e-3, delta_max: float = 1e6):
+    """Per (gene, length scale) the maximum over delta = tau / s of the collapsed sparse-GP bound with s profiled out
+    (gpz_gene_gp_profile; include/gpzoo_hip.h has the statistic): ``p`` (n_ell, D, M) the rotated projections U^T Phi y,
+    ``lam`` (n_ell, M) the eigenvalues of Phi Phi^T, ``yty`` (D,), fp64 on one device; N spots.  Returns ``(loglik, delta,
+    s2, tau2, status, iterations)``, (D, n_ell) each, fp64 and int32: status 0 interior, 1 no spatial variance in range
+    (the values at ``delta_max``), 2 at ``delta_min``, 3 degenerate (NaN)."""
+    import math
+    who = "gene_gp_profile"
+    for name, t in (("p", p), ("lam", lam), ("yty", yty)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"{who}: {name} must be a float64 tensor")
+    if p.dim() != 3 or tuple(lam.shape) != (p.shape[0], p.shape[2]) or tuple(yty.shape) != (p.shape[1],):
+        raise ValueError(f"{who}: p (n_ell, D, M), lam (n_ell, M) and yty (D,) expected, got {tuple(p.shape)}, {tuple(lam.shape)} "
+                         f"and {tuple(yty.shape)}")
+    delta_min, delta_max = float(delta_min), float(delta_max)
+    if not (0.0 < delta_min < delta_max and math.isfinite(delta_max)):
+        raise ValueError(f"{who}: delta range ({delta_min}, {delta_max}) unsupported (0 < delta_min < delta_max, both finite)")
+    _need_cuda(p, lam, yty)
+    dev = _same_device(p, lam, yty)
+    nl, D, M = (int(s) for s in p.shape)
+    p, lam, yty = p.detach().contiguous(), lam.detach().contiguous(), yty.detach().contiguous()
+    lib = _lib.load()
+    out = [torch.empty((D, nl), dtype=torch.float64, device=dev) for _ in range(4)]
+    out += [torch.empty((D, nl), dtype=torch.int32, device=dev) for _ in range(2)]
+    with torch.cuda.device(dev):
+        rc = lib.gpz_gene_gp_profile(_ptr(p), _ptr(lam), _ptr(yty), int(N), D, M, nl, delta_min, delta_max,
+                                     *(_ptr(t) for t in out), _stream(dev))
+    _lib.check(rc, "gpz_gene_gp_profile")
+    return tuple(out)
+
+
 RESIDUAL_KINDS = {"pearson": 0, "deviance": 1}
 GAUSSIAN_RESIDUAL_KINDS = {"pearson": 0, "response": 1, "predictive": 2}
 

@@ -691,6 +691,173 @@ def gene_dispersion(counts, size_factors=None, *, theta_range=(1e-4, 1e6), max_i
     return GeneDispersion(theta, pl + gain, pl, 2.0 * gain, pvalue, status, iterations)
 
 
+class GeneSpatialGP(NamedTuple):
+    """``gene_spatial_gp``: the sparse-GP fit of every gene, tensors on the values' device.  (D,) at each gene's best length
+    scale: ``lengthscale`` fp64 and ``ell_index`` int64 into ``lengthscales``; ``loglik`` the collapsed bound there,
+    ``null_loglik`` the model without a spatial term, ``lr`` = 2 (loglik - null_loglik) >= 0, ``pvalue`` = erfc(sqrt(lr / 2));
+    ``s2`` and ``tau2`` the spatial and the noise variance, ``delta`` = tau2 / s2, ``fsv`` the fraction of spatial variance
+    s2 gamma / (s2 gamma + tau2); ``status`` int32 (0 interior, 1 no spatial variance in the delta range, 2 at its lower
+    end, 3 degenerate: a constant gene, NaN in every value).  ``loglik_grid`` (D, n_ell) the bound at every length scale,
+    ``lengthscales`` (n_ell,), ``Z`` (M, d)."""
+    lengthscale: torch.Tensor
+    ell_index: torch.Tensor
+    loglik: torch.Tensor
+    null_loglik: torch.Tensor
+    lr: torch.Tensor
+    pvalue: torch.Tensor
+    s2: torch.Tensor
+    tau2: torch.Tensor
+    delta: torch.Tensor
+    fsv: torch.Tensor
+    status: torch.Tensor
+    loglik_grid: torch.Tensor
+    lengthscales: torch.Tensor
+    Z: torch.Tensor
+
+
+def _default_lengthscales(X, M, n=8):
+    """n geometric steps from the inducing-point spacing h = (bounding-box volume / M)^(1/d) to half the longest side."""
+    import math
+    side = (X.max(dim=0).values - X.min(dim=0).values).clamp_min(torch.finfo(torch.float64).tiny)
+    d = X.shape[1]
+    h = float(torch.exp(torch.log(side).sum() / d)) / float(M) ** (1.0 / d)
+    top = 0.5 * float(side.max())
+    if not h < top:
+        return torch.tensor([top], dtype=torch.float64, device=X.device)
+    return torch.exp(torch.linspace(math.log(h), math.log(top), n, dtype=torch.float64, device=X.device))
+
+
+def _eigh(B):
+    """``torch.linalg.eigh`` where B lives, on the host if the device build lacks it."""
+    try:
+        return torch.linalg.eigh(B)
+    except RuntimeError:
+        lam, U = torch.linalg.eigh(B.cpu())
+        return lam.to(B.device), U.to(B.device)
+
+
+def gene_spatial_gp(values, coords, *, inducing=256, kernel="rbf", lengthscales=None, delta_range=(1e-3, 1e6), jitter=1e-6,
+                    seed=0):
+    """Is a gene spatially variable under a Gaussian process, at what length scale, and with what fraction of its variance
+    -- SpatialDE's and nnSVG's question, for every gene at once on the values' device and at sparse-GP cost.  One gene is
+    y (N,), centred expression; the model is y = f + eps, f ~ GP(0, s2 k_l), eps ~ N(0, tau2 I) with a unit-variance
+    stationary ``kernel`` ("rbf", "matern12", "matern32", "matern52") and inducing points Z, scored by Titsias' collapsed
+    variational bound -- the ELBO of this library's ``SVGP`` with a Gaussian likelihood at the optimal q(u), a lower bound of
+    the exact marginal likelihood.  s2 is profiled out in closed form, delta = tau2 / s2 is maximised per (gene, length
+    scale) over ``delta_range`` (``ops.gene_gp_profile``), the length scale over the grid ``lengthscales``.  The answers are
+    also a model's set-up: ``lengthscale=`` of its kernel, which genes belong in the spatial half of a hybrid, how many
+    inducing points resolve the structure that is there.
+
+    ``values``: a whole ``SparseExpression`` (``log_normalize(counts)``), or a dense (D, N) tensor, whose non-zeros are stored
+    and which is centred per gene.  A ``SparseCounts`` raises TypeError (normalise it with ``log_normalize``), as do views
+    and ``.T``.  ``coords`` (N, d), d <= 4.  ``inducing``: an (M, d) tensor used as Z, or an int M for
+    ``kmeans_inducing_points(coords, M, random_state=seed)``; M <= 1024.  ``lengthscales``: up to 16 values; default 8
+    geometric steps from the inducing-point spacing h = (bounding-box volume / M)^(1/d) to half the longest side of the
+    bounding box.  A sparse GP cannot see structure finer than h: a gene that varies below it looks like noise here, and a
+    length scale under h only weakens the bound -- take more inducing points to look finer.
+
+    The N-dependent work is two passes: K_zx K_xz and K_zx 1 from ``ops.kernel_gram`` (fp64,
+    one "latent" per length scale) and K_zx Y^T over the stored entries from ``ops.gene_kernel_project_sparse`` (above 290 N
+    stored entries, where the plan finds it faster, from a K_xz filled per length scale and gathered by
+    ``ops.counts_matmul``: N x M x 8 bytes at a time); the rest is
+    M x M algebra in fp64 (``ops.cholesky``, triangular solves, ``torch.linalg.eigh`` of the n_ell matrices Phi Phi^T --
+    on the host if the device build lacks it -- and one matmul for the rotation).  A gene then costs M terms per
+    evaluation of the bound, whatever N is.
+
+    Returns a ``GeneSpatialGP``.  ``pvalue`` = erfc(sqrt(lr / 2)) is the chi2_1 tail SpatialDE uses.  It ignores that lr is
+    a maximum over the length-scale grid, that s2 >= 0 is a boundary of the parameter space, and that a bound stands in place
+    of the likelihood: it ranks and screens genes (put ``fdr_bh`` on top of it), it is not a calibrated test.  ``fsv`` uses
+    the Gower factor gamma = (sum lam - |Phi 1|^2 / N) / (N - 1) of Phi^T Phi.  y.y is formed as sum z^2 - 2 offset sum z +
+    N offset^2: for a nearly constant gene it loses digits in proportion to mean^2 / variance, as Moran's I does here."""
+    import math
+    from . import ops
+    from .likelihoods import SparseCounts, SparseExpression, TransposedCounts, _gene_moments
+    who = "gene_spatial_gp"
+    if isinstance(values, TransposedCounts):
+        raise TypeError(f"{who}: values is a .T (obs x feat); pass the (genes x spots) SparseExpression itself")
+    if isinstance(values, SparseCounts):
+        raise TypeError(f"{who}: a SparseCounts holds counts; pass log_normalize(counts), a SparseExpression")
+    if isinstance(values, SparseExpression):
+        if values.is_view:
+            raise TypeError(f"{who}: values is a view y[:, idx]; the whole SparseExpression is needed")
+        expr = values
+    elif isinstance(values, torch.Tensor):
+        if values.dim() != 2 or not values.is_floating_point():
+            raise TypeError(f"{who}: a dense (D, N) floating-point tensor expected, got {values.dtype} of shape {tuple(values.shape)}")
+        stored = SparseCounts(values.detach())                     # fp32 values; the means are those of what is stored
+        zero = torch.zeros(stored.shape[0], dtype=torch.float64, device=stored.device)
+        expr = SparseExpression(stored, _gene_moments(SparseExpression(stored, zero))[0] / stored.shape[1])
+    else:
+        raise TypeError(f"{who}: a whole SparseExpression or a dense (D, N) tensor expected, got {type(values).__name__}")
+    kind = ops._gene_gp_kind(who, kernel)
+    D, N = expr.shape
+    X = torch.as_tensor(coords).detach()
+    if X.dim() != 2 or X.shape[0] != N or not 1 <= X.shape[1] <= 4:
+        raise ValueError(f"{who}: coords ({N}, d) with 1 <= d <= 4 expected, got {tuple(X.shape)}")
+    if N < 2:
+        raise ValueError(f"{who}: {N} spot; at least 2 are needed")
+    try:
+        d_lo, d_hi = (float(v) for v in delta_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: delta_range {delta_range!r} must be (delta_min, delta_max)") from None
+    if not (0.0 < d_lo < d_hi and math.isfinite(d_hi)):
+        raise ValueError(f"{who}: delta_range ({d_lo}, {d_hi}) unsupported (0 < delta_min < delta_max, both finite)")
+    if not float(jitter) >= 0.0:
+        raise ValueError(f"{who}: jitter={jitter!r} must be >= 0")
+    dev = expr.device
+    X = X.to(device=dev, dtype=torch.float64).contiguous()
+    if isinstance(inducing, torch.Tensor):
+        Z = inducing.detach().to(device=dev, dtype=torch.float64).contiguous()
+        if Z.dim() != 2 or Z.shape[1] != X.shape[1]:
+            raise ValueError(f"{who}: inducing (M, {X.shape[1]}) expected, got {tuple(Z.shape)}")
+    elif isinstance(inducing, int) and not isinstance(inducing, bool):
+        if not 1 <= inducing <= min(N, 1024):
+            raise ValueError(f"{who}: inducing={inducing} outside [1, min(N, 1024)]")
+        Z = kmeans_inducing_points(X, inducing, random_state=seed).contiguous()
+    else:
+        raise TypeError(f"{who}: inducing must be an int or an (M, d) tensor, got {type(inducing).__name__}")
+    M = int(Z.shape[0])
+    if not 1 <= M <= 1024:
+        raise ValueError(f"{who}: M={M} inducing points unsupported (1..1024)")
+    if lengthscales is None:
+        ell = _default_lengthscales(X, M)
+    else:
+        ell = torch.as_tensor(lengthscales).detach().reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+        if not 1 <= ell.numel() <= 16 or not bool((ell > 0).all() & torch.isfinite(ell).all()):
+            raise ValueError(f"{who}: lengthscales must be 1..16 positive finite values")
+    nl = int(ell.numel())
+
+    spec = ops.KernelSpec(kind, torch.ones(nl, dtype=torch.float64, device=dev), ell, True)
+    G, b = ops.kernel_gram(spec, Z, X, torch.ones((nl, N), dtype=torch.float64, device=dev), 0.0)     # K_zx K_xz, K_zx 1
+    Kzz = ops.kfill(spec, Z, Z) + float(jitter) * torch.eye(M, dtype=torch.float64, device=dev)
+    Lz = torch.tril(ops.cholesky(Kzz))
+    B = ops.solve_triangular_lower(Lz, ops.solve_triangular_lower(Lz, G).transpose(-1, -2).contiguous())   # Lz^-1 G Lz^-T
+    lam, U = _eigh(0.5 * (B + B.transpose(-1, -2)))
+    lam = lam.clamp_min(0.0).contiguous()
+    W = torch.linalg.solve_triangular(Lz.transpose(-1, -2), U, upper=True)                            # Lz^-T U
+    phi1 = ops.solve_triangular_lower(Lz, b.transpose(-1, -2).contiguous())[:, :, 0]                   # Phi 1, (n_ell, M)
+
+    generate = ops.gene_kernel_project_plan(N, D, expr.nnz, M, nl)["generate"]          # the plan's rule: which way is faster
+    P = (ops.gene_kernel_project_sparse if generate else ops.gene_kernel_project_gather)(expr, X, Z, ell, kernel)   # K_zx z^T
+    P -= expr.offset[None, :, None] * b                                                               # K_zx y^T
+    p = torch.matmul(P, W)                                                                            # U^T Phi y
+    del P
+    sz, szz = _gene_moments(expr)
+    yty = (szz - 2.0 * expr.offset * sz + N * expr.offset * expr.offset).contiguous()
+    F, delta, s2, tau2, status, _ = ops.gene_gp_profile(p, lam, yty, N, d_lo, d_hi)
+
+    best = torch.where(torch.isnan(F), torch.full_like(F, -float("inf")), F).argmax(dim=1)
+    pick = lambda t: t.gather(1, best[:, None])[:, 0]
+    loglik = pick(F)
+    null = -0.5 * N * (torch.log(2.0 * math.pi * yty / N) + 1.0)
+    null = torch.where(yty > 0, null, torch.full_like(null, float("nan")))
+    lr = (2.0 * (loglik - null)).clamp_min(0.0)
+    gamma = ((lam.sum(dim=1) - (phi1 * phi1).sum(dim=1) / N) / (N - 1))[best]
+    s2b, tau2b = pick(s2), pick(tau2)
+    return GeneSpatialGP(ell[best], best, loglik, null, lr, torch.erfc(torch.sqrt(0.5 * lr)), s2b, tau2b, pick(delta),
+                         s2b * gamma / (s2b * gamma + tau2b), pick(status), F, ell, Z)
+
+
 class GeneAutocorr(NamedTuple):
     """``gene_autocorr``: Moran's I per gene and the moments squidpy reports beside it under the normality assumption
     (they depend on the graph alone), all fp64 tensors: ``I`` (D,), ``expected`` = -1 / (N - 1), ``variance`` (scalars) and
@@ -1030,8 +1197,9 @@ def rank_genes(counts, by="deviance", *, coords=None, nfeat=None, **kw):
     ``ad[:, :nfeat]`` of a data set sorted by importance.  ``by``: "deviance" (``gene_deviance``, Poisson),
     "binomial_deviance", "moran" (``gene_autocorr`` of ``log_normalize(counts, center=False)`` over ``coords``), "geary"
     (1 - C of the same values, ``gene_autocorr(mode="geary")``: larger is more autocorrelated, as with every score), or
-    "overdispersion" (``gene_dispersion(counts).lr``, the likelihood-ratio statistic of NB against Poisson).  Extra
-    keywords go to the scorer."""
+    "overdispersion" (``gene_dispersion(counts).lr``, the likelihood-ratio statistic of NB against Poisson), or "gp"
+    (``gene_spatial_gp(log_normalize(counts), coords).lr``, the sparse-GP likelihood ratio against no spatial term;
+    ``size_factors=`` goes to ``log_normalize``).  Extra keywords go to the scorer."""
     if by == "deviance":
         score = gene_deviance(counts, "poisson", **kw)
     elif by == "binomial_deviance":
@@ -1048,8 +1216,13 @@ def rank_genes(counts, by="deviance", *, coords=None, nfeat=None, **kw):
         score = 1.0 - gene_autocorr(log_normalize(counts, center=False), coords, mode="geary", **kw).C
     elif by == "overdispersion":
         score = gene_dispersion(counts, **kw).lr
+    elif by == "gp":
+        _whole_counts_only(counts, "rank_genes")
+        if coords is None:
+            raise ValueError("rank_genes: by='gp' needs coords")
+        score = gene_spatial_gp(log_normalize(counts, kw.pop("size_factors", None)), coords, **kw).lr
     else:
-        raise ValueError(f"rank_genes: by={by!r} unknown ('deviance', 'binomial_deviance', 'moran', 'geary', 'overdispersion')")
+        raise ValueError(f"rank_genes: by={by!r} unknown ('deviance', 'binomial_deviance', 'moran', 'geary', 'overdispersion', 'gp')")
     order = _rank_order(score, nfeat)
     return order, score[order]
 

@@ -83,7 +83,11 @@
  * the fit); scratch `partials`;
  * gpz_gaussian_residuals, gpz_gaussian_residual_stats, gpz_gaussian_residual_perm, their *_sparse forms and the host-only
  * gpz_gaussian_residual_plan -- the same residual diagnostics for the Gaussian factor models (RSF, FA): Pearson, response or
- * predictive residuals of real-valued expression, dense or stored as its non-zeros minus a per-gene offset; scratch `partials`.
+ * predictive residuals of real-valued expression, dense or stored as its non-zeros minus a per-gene offset; scratch `partials`;
+ * gpz_gene_kernel_project_sparse, gpz_gene_gp_profile and their host-only *_plan queries -- the two device steps of the sparse-GP
+ * test for spatially variable genes (SpatialDE / nnSVG's question, scored by Titsias' collapsed bound): K_zx Y^T of every gene
+ * over its stored entries for a grid of length scales with K_zx generated and never stored, and the per-gene maximum of the
+ * bound over the noise-to-signal ratio; scratch `partials` for the first, none for the second.
  */
 #ifndef GPZOO_HIP_H
 #define GPZOO_HIP_H
@@ -501,6 +505,54 @@ int gpz_gene_dispersion_sparse(const int64_t* row_ptr, const int32_t* row_spot, 
                                const double* size, int64_t N, int64_t D, int64_t nnz, double theta_min, double theta_max,
                                int32_t max_iter, double* theta, double* gain, double* poisson_loglik, int32_t* status,
                                int32_t* iterations, int32_t* info, void* partials, size_t partials_bytes, void* stream);
+
+/* The sparse-GP test for spatially variable genes (csrc/gene_gp.hip; gpzoo.utilities.gene_spatial_gp assembles it), fp64
+ * throughout.  One gene is y (N,), a row of centred expression; the model y = f + eps, f ~ GP(0, s k_l), eps ~ N(0, tau I) with a
+ * unit-variance stationary kernel k_l and inducing points Z (M, d) is scored by Titsias' collapsed bound.  With Lz = chol(K_zz +
+ * jitter I), Phi = Lz^-1 K_zx, B = Phi Phi^T = U diag(lam) U^T, p = U^T Phi y, delta = tau / s and s profiled out:
+ *   Q(delta) = y.y - sum_i p_i^2 / (delta + lam_i),   R = Q / delta,   s = R / N,   tau = s delta,
+ *   F(delta) = -1/2 [ N log 2 pi + N log(R / N) + N + (N - M) log delta + sum_i log(delta + lam_i) + (N - sum_i lam_i) / delta ],
+ * which tends to the null model's F_0 = -1/2 N (log(2 pi y.y / N) + 1) as delta -> inf.
+ *
+ * gpz_gene_kernel_project_sparse: out[l, g, m] = sum_{stored (g, n)} v_gn k_l(z_m, x_n), out (n_ell, D, M) -- K_zx Y^T of every
+ * gene of a WHOLE data set stored as its non-zeros (the by-gene arrays of gpz_gene_deviance_sparse; the centring is the
+ * caller's: K_zx y = K_zx z - offset K_zx 1), for n_ell length scales (device array, fp64), X (N, d) and Z (M, d) fp64 device
+ * arrays, 1 <= d <= 4, 1 <= M <= 1024, 1 <= n_ell <= 16, kind GPZ_KERNEL_RBF, _MATERN12, _MATERN32 or _MATERN52.  The covariances
+ * are generated in the kernel with the fp64 operations of gpz_kernel_gram at sigma = 1 (the same bits) and never stored: nothing
+ * of N x M or nnz elements is allocated.  The distance of a pair is computed once for all length scales.  A row longer than
+ * gene_chunk entries (the plan: a multiple of 256, at least N / 4) is cut into chunks of that many; a sum runs over the
+ * entries of a chunk in row order, each term the rounded product added to the running sum, then over the chunks in order: it
+ * depends on N (through gene_chunk) and on nothing else -- not on `workgroups` (0: the plan's; any value up to 65535 gives the
+ * same bits).  No atomics.  An entry whose spot or position is out of range counts as a stored zero.  The scratch is `partials`
+ * (the sums of the chunks after a row's first: nnz / gene_chunk + 1 slots of n_ell x M values), sized by the plan query; it
+ * need not be cleared.  The plan's `generate` is 1 while this entry is the faster way to the result and 0 above 290 N stored
+ * entries, where filling K_xz per length scale (gpz_kfill) and gathering its rows (gpz_counts_matmul) costs less than the
+ * exp per (entry, inducing point, length scale) generated here (measured on an MI355X; csrc/gene_gp.hip has the figures); the
+ * entry computes either way.
+ *
+ * gpz_gene_gp_profile: per (gene, length scale) the maximum of F over t = log delta in [log delta_min, log delta_max].  p (n_ell,
+ * D, M), lam (n_ell, M) >= 0, yty (D,) = y.y, device arrays.  F is evaluated on a uniform grid of grid_points (33) values of t;
+ * the best point, ties to the lower index, starts a Newton iteration on dF/dt between its two grid neighbours, kept inside a
+ * bracket and bisecting when a step leaves it or does not halve the derivative; it stops at a step or bracket <= tol_t (1e-9)
+ * or after max_iter (100) evaluations.  Outputs (D, n_ell): loglik = F at the optimum, delta, s2 = R / N, tau2 = s2 delta there,
+ * status int32 (0 interior; 1 the best grid point is the last and F still rises there: no spatial variance in range, the
+ * values at delta_max; 2 the best is the first and F falls from there: the lower bound; 3 degenerate: y.y <= 0 or not finite,
+ * or Q <= 0 or F not finite on the grid -- NaN in the four values) and iterations int32 (evaluations after the grid; max_iter:
+ * not converged).  One wave per pair, every sum in a fixed order: two calls agree bit for bit.  No scratch.
+ *
+ * Argument errors (null pointers, extents or limits above, a bad kind or delta range, misaligned or short partials) return -1
+ * before any launch with the reason in gpz_last_error.  The plan queries are host-only; any out pointer may be NULL. */
+int gpz_gene_kernel_project_sparse_plan(int64_t N, int64_t D, int64_t nnz, int64_t M, int32_t n_ell, int32_t* gene_chunk,
+                                        int32_t* workgroups, int32_t* generate, int64_t* partials_bytes);
+int gpz_gene_kernel_project_sparse(const int64_t* row_ptr, const int32_t* row_spot, const int32_t* row_perm, const float* col_val,
+                                   const double* X, const double* Z, const double* lengthscales, int64_t N, int64_t D, int64_t nnz,
+                                   int64_t M, int32_t d, int32_t n_ell, int32_t kind, int32_t workgroups, double* out,
+                                   void* partials, size_t partials_bytes, void* stream);
+int gpz_gene_gp_profile_plan(int64_t D, int64_t M, int32_t n_ell, int32_t* grid_points, int32_t* workgroups, double* tol_t,
+                             int32_t* max_iter);
+int gpz_gene_gp_profile(const double* p, const double* lam, const double* yty, int64_t N, int64_t D, int64_t M, int32_t n_ell,
+                        double delta_min, double delta_max, double* loglik, double* delta, double* s2, double* tau2,
+                        int32_t* status, int32_t* iterations, void* stream);
 
 /* Moran's I of every gene under P relabellings of the spots (csrc/moran_perm.hip): the permutation null of squidpy's
  * spatial_autocorr(..., n_perms=) and of PySAL's Moran.  perms (P, N) int32, row p a permutation pi of 0 .. N - 1; the permuted
